@@ -223,6 +223,46 @@ def rehearse(args):
         dist.destroy_process_group()
 
 
+DUMP_BYTES = 64 << 20  # --dump-outputs: the most one dump may write
+DUMP_MASK_FOVS = 4      # label planes kept (the rest of the budget goes to feature rows)
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, rows, table, labels):
+    """`--dump-outputs DIR`: what the timed path handed its caller in the last step — the feature rows (mono, multi), the
+    (tile, label) key of every row and the label planes — as DIR/<name>.npy in float64 / float32, at most DUMP_BYTES in all.
+    When the whole output is larger, a fixed sample is written: DUMP_MASK_FOVS label planes and a seeded subset of the rows
+    (same seed, same inputs -> same sample), with `row_index` / `mask_fov` saying which rows and planes they are.
+    A feature column that is NaN for every object of the step (undefined by definition: the normalised moments of order < 2,
+    as in skimage) carries nothing and is left out; `features_<name>_columns` lists the indices of the columns written.  Any
+    other NaN is written as it is."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    masks = labels.cpu().numpy()
+    masks = masks.reshape((-1,) + masks.shape[-2:])
+    fovs = np.arange(masks.shape[0]) if masks.shape[0] <= DUMP_MASK_FOVS else np.sort(
+        rng.choice(masks.shape[0], DUMP_MASK_FOVS, replace=False))
+    out = {"masks": masks[fovs].astype(np.float32), "mask_fov": fovs.astype(np.float64)}
+    feats = {f"features_{name}": np.asarray(r, dtype=np.float64) for name, r in zip(("mono", "multi"), rows)}
+    cols = {k: (np.nonzero(~np.isnan(a).all(axis=0))[0] if len(a) else np.arange(a.shape[1])) for k, a in feats.items()}
+    out.update({f"{k}_columns": c.astype(np.float64) for k, c in cols.items()})
+    n = table.n_obj
+    budget = DUMP_BYTES - 4096 - sum(a.nbytes for a in out.values())  # (4 KiB: the .npy headers)
+    per_row = 8 * (3 + sum(len(c) for c in cols.values()))  # + tile, label, row_index
+    keep = min(n, max(budget // per_row, 0))
+    idx = np.arange(n) if keep == n else np.sort(rng.choice(n, keep, replace=False))
+    out.update({k: a[idx][:, cols[k]] for k, a in feats.items()})
+    out["object_tile"] = table.host["tile"][idx].astype(np.float64)
+    out["object_label"] = table.host["label"][idx].astype(np.float64)
+    out["row_index"] = idx.astype(np.float64)
+    assert sum(a.nbytes for a in out.values()) <= DUMP_BYTES - 4096
+    for k, a in out.items():
+        np.save(out_dir / f"{k}.npy", np.ascontiguousarray(a))
+    return {"dir": str(out_dir), "rows": int(n), "rows_written": int(keep), "mask_fovs": [int(f) for f in fovs],
+            "all_nan_columns_left_out": {k: [int(i) for i in np.setdiff1d(np.arange(a.shape[1]), cols[k])] for k, a in feats.items()}}
+
+
 def build_rooflines(prof, model, args, B, C, Z, Y, X, n_obj, n_tiles_net, steps):
     """The roofline objects of a bench line from the per-group HIP-event timings (`prof`): the dominant hand-written group against
     HBM peak (algorithmic bytes per launch / average launch time), the deep K-loop conv group against the dense MFMA peak, every
@@ -328,6 +368,8 @@ def main():
                     "wires, SURVEY.md 8(d).5): every Z plane segmented, planes stitched along Z (IoU >= 0.01), 3-D intensity features; "
                     "a tile is one [C,Z,Y,X] stack.  Without it config 5 is the reference-faithful projected form")
     ap.add_argument("--host-procs", type=int, default=0, help="host processes for input generation / the CPU baseline (default: all)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last step computed (feature "
+                    "rows, their (tile, label) keys, label planes) as DIR/<name>.npy, at most 64 MB (a fixed, seeded sample when larger)")
     args = ap.parse_args()
     global BSIZE
     BSIZE = args.bsize
@@ -337,6 +379,10 @@ def main():
         sys.exit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={os.environ.get('WORLD_SIZE', 1)}: start one rank per GPU "
                  f"(torch.distributed.run --nproc-per-node {args.gpus}), or run `python bench.py --gpus {args.gpus}` from a plain "
                  "environment and let it start the ranks")
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be at least 1")
+    if args.dump_outputs and (args.rehearse or args.config == 4 or args.true_3d):
+        sys.exit("bench.py: --dump-outputs covers the per-FOV workloads (configs 1, 2, 5 without --true-3d)")
     if args.rehearse:
         return rehearse(args)
     if args.config == 4:
@@ -450,6 +496,7 @@ def main():
         # rows -> pinned host memory on a side stream: the download of step k overlaps the start of step k+1
         pending = eng.to_host_async(tuple(out), slot=step.parity)
         step.parity ^= 1
+        step.labels = labels
         return pending, table, model.last_counts
 
     step.parity = 0
@@ -484,6 +531,7 @@ def main():
             m2, names2, _ = extract_batch(eng, labels, planes, multi_tree, multi=True, table=table)
             pending = eng.to_host_async((m1, m2), slot=step.parity)
             step.parity ^= 1
+            step.labels = labels
         return pending, table, counts
 
     def barrier():
@@ -536,6 +584,9 @@ def main():
     prof = eng.collect_profile()
     eng.profile = None
     tiles_per_s = world * B * steps / dt
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, rows, table, step.labels)
     n_cols = sum(r.shape[1] for r in rows)
 
     # ---- the one exchange step: gather the last step's rows on rank 0 (RCCL over xGMI) ------------------
@@ -599,6 +650,8 @@ def main():
         }
         if api is not None:
             line.update(api)
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         print(json.dumps(line))
     if dist is not None:
         dist.destroy_process_group()

@@ -17,7 +17,7 @@ def test_tiff_decoder_survives_corrupted_files_under_asan(tmp_path):
     root = Path(__file__).resolve().parents[1]
     exe = tmp_path / "tiff_fuzz"
     src = [root / "aliby_amd" / "csrc" / "ingest.hip", root / "aliby_amd" / "csrc" / "ctx.hip", root / "tests" / "tools" / "tiff_fuzz_harness.cpp"]
-    build = subprocess.run(["/opt/rocm/bin/hipcc", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
+    build = subprocess.run(["/opt/rocm/bin/hipcc", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-gpu-sanitize", "-fno-omit-frame-pointer",
                             "--offload-arch=gfx950", "-I", str(root / "include"), "-I", str(root / "aliby_amd" / "csrc"), *map(str, src),
                             "-o", str(exe), "-lz", "-ldl", "-lpthread"], capture_output=True, text=True, timeout=600)
     assert build.returncode == 0, build.stderr[-2000:]
@@ -39,7 +39,7 @@ def test_blosc_decoder_survives_corrupted_frames_under_asan(tmp_path):
     root = Path(__file__).resolve().parents[1]
     exe = tmp_path / "blosc_fuzz"
     src = [root / "aliby_amd" / "csrc" / "ingest.hip", root / "aliby_amd" / "csrc" / "ctx.hip", root / "tests" / "tools" / "blosc_fuzz_harness.cpp"]
-    build = subprocess.run(["/opt/rocm/bin/hipcc", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
+    build = subprocess.run(["/opt/rocm/bin/hipcc", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-gpu-sanitize", "-fno-omit-frame-pointer",
                             "--offload-arch=gfx950", "-I", str(root / "include"), "-I", str(root / "aliby_amd" / "csrc"), *map(str, src),
                             "-o", str(exe), "-lz", "-ldl", "-lpthread"], capture_output=True, text=True, timeout=600)
     assert build.returncode == 0, build.stderr[-2000:]
