@@ -59,6 +59,7 @@ OBJECT_DTYPE = np.dtype(
 )
 
 _vp, _i, _sz = C.c_void_p, C.c_int, C.c_size_t
+_ll = C.c_longlong
 _ip = C.POINTER(C.c_int32)
 
 # name -> (restype, argtypes); mirrors include/aliby_hip.h one to one
@@ -83,6 +84,10 @@ _SIGNATURES = {
     "aliby_normalize99_u16": (_i, [_vp, _vp, _i, _i, _i, C.c_double, C.c_double, _vp, _vp, _vp]),
     "aliby_make_tiles": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "aliby_average_tiles": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "aliby_make_tiles_strided": (_i, [_vp, _vp, _i, _i, _ll, _ll, _ll, _ll, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i,
+                                      _vp, _vp]),
+    "aliby_average_tiles_strided": (_i, [_vp, _vp, _i, _i, _ll, _ll, _ll, _ll, _ll, _ll, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
+                                         _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "aliby_nn_fused_act_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "aliby_nn_conv3x3_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "aliby_nn_conv3x3_deep_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
@@ -120,6 +125,8 @@ _SIGNATURES = {
     "aliby_masks_workspace_bytes": (_sz, [_i, _i, _i]),
     "aliby_masks_from_flows": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, C.c_float, C.c_float, _i, C.c_float, _vp, _sz,
                                     _vp, _vp, _vp, _vp]),
+    "aliby_masks3d_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "aliby_masks_from_flows_3d": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_float, _i, C.c_float, _vp, _sz, _vp, _vp, _vp, _vp]),
     "aliby_features_intensity": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _i, _i, _vp]),
     "aliby_features_sizeshape": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "aliby_features_feret": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _i, _vp]),

@@ -213,6 +213,78 @@ __global__ void k_average_tiles(const float* __restrict__ ytiles, TileGeom g, co
   }
 }
 
+// ---- strided tiling / blending (cellpose's do_3D: three orthogonal stacks of slices of one volume) -----------------------------
+// Image n of a pass starts at (n / S) * vol_stride + (n % S) * slice_stride and walks its rows / columns with its own strides, so one
+// kernel reads the YX, ZY and ZX slices of a batch of volumes [F,Z,Y,X] in place, without a transposed copy.  Per pixel the
+// arithmetic is k_make_tiles' / k_average_tiles' for a 2-D image of that shape.
+struct SliceMap {
+  long long vol_stride, slice_stride, row_stride, col_stride;
+  int S;  // slices per volume
+};
+
+__device__ __forceinline__ size_t slice_offset(const SliceMap& m, int n, int r, int c) {
+  return (size_t)((long long)(n / m.S) * m.vol_stride + (long long)(n % m.S) * m.slice_stride + (long long)r * m.row_stride +
+                  (long long)c * m.col_stride);
+}
+
+__global__ void k_make_tiles_strided(const float* __restrict__ vol, TileGeom g, SliceMap m, const int* __restrict__ ystart,
+                                     const int* __restrict__ xstart, float* __restrict__ tiles) {
+  const size_t per_tile = (size_t)g.nchan * g.by * g.bx;
+  const size_t total = (size_t)g.F * g.ny * g.nx * per_tile;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t t = i / per_tile, rem = i % per_tile;
+    const int ch = (int)(rem / ((size_t)g.by * g.bx));
+    const int r = (int)((rem / g.bx) % g.by), c = (int)(rem % g.bx);
+    const int n = (int)(t / (g.ny * g.nx)), k = (int)(t % (g.ny * g.nx));
+    float v = 0.0f;
+    if (ch == 0) {
+      const int y = ystart[k / g.nx] + r - g.ypad1, x = xstart[k % g.nx] + c - g.xpad1;
+      if (y >= 0 && y < g.Y && x >= 0 && x < g.X) v = vol[slice_offset(m, n, y, x)];
+    }
+    tiles[i] = v;
+  }
+}
+
+// net output tiles [N*ny*nx, 3, by, bx] -> channel 0 / 1 into components comp0 / comp1 of dP [F,3,...] (comp_stride apart, the
+// volume's spatial layout given by m with vol_stride = one volume of dP), channel 2 into cellprob (m with prob_vol_stride).
+// add_mask bit k: channel k is added to what is there (float32, after the blend) instead of written.
+__global__ void k_average_tiles_strided(const float* __restrict__ ytiles, TileGeom g, SliceMap m, long long prob_vol_stride,
+                                        long long comp_stride, int comp0, int comp1, int add_mask,
+                                        const int* __restrict__ ystart, const int* __restrict__ xstart,
+                                        const float* __restrict__ taper, float* __restrict__ dP, float* __restrict__ prob) {
+  const size_t P = (size_t)g.Y * g.X;
+  const size_t total = (size_t)g.F * P;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int n = (int)(i / P);
+    const int y = (int)((i % P) / g.X), x = (int)(i % g.X);
+    const int yp = y + g.ypad1, xp = x + g.xpad1;
+    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, nav = 0.0f;
+    for (int j = 0; j < g.ny; ++j) {
+      const int r = yp - ystart[j];
+      if (r < 0 || r >= g.by) continue;
+      for (int q = 0; q < g.nx; ++q) {
+        const int c = xp - xstart[q];
+        if (c < 0 || c >= g.bx) continue;
+        const float w = taper[r * g.bx + c];
+        const size_t base = (((size_t)n * g.ny * g.nx + (size_t)j * g.nx + q) * 3) * g.by * g.bx + (size_t)r * g.bx + c;
+        a0 = a0 + ytiles[base] * w;
+        a1 = a1 + ytiles[base + (size_t)g.by * g.bx] * w;
+        a2 = a2 + ytiles[base + 2 * (size_t)g.by * g.bx] * w;
+        nav = nav + w;
+      }
+    }
+    const float v0 = a0 / nav, v1 = a1 / nav, v2 = a2 / nav;
+    const size_t od = slice_offset(m, n, y, x);
+    const size_t spatial = (size_t)((long long)(n % m.S) * m.slice_stride + (long long)y * m.row_stride + (long long)x * m.col_stride);
+    const size_t op = (size_t)((long long)(n / m.S) * prob_vol_stride) + spatial;
+    float* d0 = dP + od + (size_t)((long long)comp0 * comp_stride);
+    float* d1 = dP + od + (size_t)((long long)comp1 * comp_stride);
+    *d0 = (add_mask & 1) ? *d0 + v0 : v0;
+    *d1 = (add_mask & 2) ? *d1 + v1 : v1;
+    prob[op] = (add_mask & 4) ? prob[op] + v2 : v2;
+  }
+}
+
 // Z max-projection of one channel: pixels [F,C,Z,Y,X] u16 -> [F,Y,X]  (dispatch.py:192,199-206)
 __global__ void k_select_project(const u16* __restrict__ px, int F, int C, int Z, size_t plane, int channel,
                                  u16* __restrict__ out) {
@@ -307,6 +379,46 @@ int aliby_average_tiles(aliby_ctx* ctx, const float* ytiles, int F, int Y, int X
   TileGeom g{F, Y, X, ypad1, xpad1, Ly, Lx, by, bx, ny, nx, 3};
   hipLaunchKernelGGL(k_average_tiles, dim3(grid_for((size_t)F * Y * X)), dim3(256), 0, as_stream(stream), ytiles, g,
                      ystart_dev, xstart_dev, taper_dev, dP, cellprob);
+  KERNEL_CHECK();
+  return ALIBY_OK;
+}
+
+int aliby_make_tiles_strided(aliby_ctx* ctx, const float* vol, int N, int S, long long vol_stride, long long slice_stride,
+                             long long row_stride, long long col_stride, int Y, int X, int ypad1, int xpad1, int Ly, int Lx,
+                             int by, int bx, int ny, int nx, const int32_t* ystart_dev, const int32_t* xstart_dev, int nchan,
+                             float* tiles, void* stream) {
+  ARG_CHECK(ctx != nullptr, "ctx is NULL");
+  ARG_CHECK(N >= 0 && S > 0 && Y > 0 && X > 0, "bad shape");
+  if (N == 0) return ALIBY_OK;
+  ARG_CHECK(vol && ystart_dev && xstart_dev && tiles, "NULL argument");
+  ARG_CHECK(by > 0 && bx > 0 && ny > 0 && nx > 0 && nchan > 0 && by <= Ly && bx <= Lx, "bad tile geometry");
+  ARG_CHECK(vol_stride >= 0 && slice_stride >= 0 && row_stride >= 0 && col_stride >= 0, "negative stride");
+  TileGeom g{N, Y, X, ypad1, xpad1, Ly, Lx, by, bx, ny, nx, nchan};
+  SliceMap m{vol_stride, slice_stride, row_stride, col_stride, S};
+  const size_t total = (size_t)N * ny * nx * nchan * by * bx;
+  hipLaunchKernelGGL(k_make_tiles_strided, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), vol, g, m, ystart_dev, xstart_dev,
+                     tiles);
+  KERNEL_CHECK();
+  return ALIBY_OK;
+}
+
+int aliby_average_tiles_strided(aliby_ctx* ctx, const float* ytiles, int N, int S, long long dP_vol_stride,
+                                long long prob_vol_stride, long long slice_stride, long long row_stride, long long col_stride,
+                                long long comp_stride, int comp0, int comp1, int add_mask, int Y, int X, int ypad1, int xpad1,
+                                int Ly, int Lx, int by, int bx, int ny, int nx, const int32_t* ystart_dev,
+                                const int32_t* xstart_dev, const float* taper_dev, float* dP, float* cellprob, void* stream) {
+  ARG_CHECK(ctx != nullptr, "ctx is NULL");
+  ARG_CHECK(N >= 0 && S > 0 && Y > 0 && X > 0, "bad shape");
+  if (N == 0) return ALIBY_OK;
+  ARG_CHECK(ytiles && ystart_dev && xstart_dev && taper_dev && dP && cellprob, "NULL argument");
+  ARG_CHECK(by > 0 && bx > 0 && ny > 0 && nx > 0, "bad tile geometry");
+  ARG_CHECK(comp0 >= 0 && comp1 >= 0 && comp0 != comp1 && add_mask >= 0 && add_mask < 8, "bad components / add mask");
+  ARG_CHECK(dP_vol_stride >= 0 && prob_vol_stride >= 0 && slice_stride >= 0 && row_stride >= 0 && col_stride >= 0 &&
+                comp_stride >= 0, "negative stride");
+  TileGeom g{N, Y, X, ypad1, xpad1, Ly, Lx, by, bx, ny, nx, 3};
+  SliceMap m{dP_vol_stride, slice_stride, row_stride, col_stride, S};
+  hipLaunchKernelGGL(k_average_tiles_strided, dim3(grid_for((size_t)N * Y * X)), dim3(256), 0, as_stream(stream), ytiles, g, m,
+                     prob_vol_stride, comp_stride, comp0, comp1, add_mask, ystart_dev, xstart_dev, taper_dev, dP, cellprob);
   KERNEL_CHECK();
   return ALIBY_OK;
 }

@@ -12,6 +12,10 @@ Per batch of tiles [F,Y,X]:
 (the network still runs when `run_network_with_override=True`): Cellpose weights cannot be fetched
 offline, so tests and bench.py feed analytic flows derived from the synthetic
 ground truth into the same dynamics.
+
+`eval(x, do_3D=True)` is cellpose's 3-D mode for volumes [Z,Y,X] / [F,Z,Y,X]: the network over the YX, ZY and ZX slices
+(strided tiling / blending, HIP), flows summed per axis, then the 3-D dynamics (csrc/dynamics3d.hip).  Its flows_override
+takes [F,Z,Y,X] and returns (dP [F,3,Z,Y,X], cellprob [F,Z,Y,X]).
 """
 
 from __future__ import annotations
@@ -233,6 +237,20 @@ class CellposeModel:
         out = torch.where(x99 - x01 > 1e-3, (flat - x01) / (x99 - x01), torch.zeros_like(flat))
         return out.to(torch.float32).reshape(F, Y, X)
 
+    def _forward_tiles(self, tiles: torch.Tensor, g: dict, batch_size: int) -> torch.Tensor:
+        """Network tiles [n,2,by,bx] -> outputs [n,3,by,bx], batch_size tiles per forward."""
+        ntiles = tiles.shape[0]
+        yt = torch.empty((ntiles, 3, g["by"], g["bx"]), dtype=torch.float32, device=self.device)
+        with self.eng.timed("unet_forward"), torch.no_grad():
+            for i in range(0, ntiles, batch_size):
+                if self.fused is not None and g["by"] % 8 == 0 and g["bx"] % 8 == 0:
+                    self._forward_batch(tiles[i : i + batch_size], yt[i : i + batch_size])  # written in place
+                else:
+                    xb = tiles[i : i + batch_size].to(self.net_dtype).contiguous(memory_format=torch.channels_last)
+                    yb, _ = self.net(xb)
+                    yt[i : i + batch_size] = yb.to(torch.float32)
+        return yt
+
     def run_network(self, img_u16: torch.Tensor, normalize: bool = True, bsize=None, tile_overlap=None, batch_size=None):
         """uint16 [F,Y,X] -> (dP float32 [F,2,Y,X], cellprob float32 [F,Y,X]) through the U-Net.
         bsize / tile_overlap / batch_size: this call's tile geometry and tiles per forward (default: the model's)."""
@@ -249,15 +267,7 @@ class CellposeModel:
             _lib.check(lib.aliby_make_tiles(h, _ptr(norm), F, Y, X, g["ypad1"], g["xpad1"], g["Ly"], g["Lx"], g["by"],
                                             g["bx"], g["ny"], g["nx"], _ptr(g["ys"]), _ptr(g["xs"]), 2, _ptr(tiles),
                                             _stream_ptr()))
-        yt = torch.empty((ntiles, 3, g["by"], g["bx"]), dtype=torch.float32, device=self.device)
-        with self.eng.timed("unet_forward"), torch.no_grad():
-            for i in range(0, ntiles, batch_size):
-                if self.fused is not None and g["by"] % 8 == 0 and g["bx"] % 8 == 0:
-                    self._forward_batch(tiles[i : i + batch_size], yt[i : i + batch_size])  # written in place
-                else:
-                    xb = tiles[i : i + batch_size].to(self.net_dtype).contiguous(memory_format=torch.channels_last)
-                    yb, _ = self.net(xb)
-                    yt[i : i + batch_size] = yb.to(torch.float32)
+        yt = self._forward_tiles(tiles, g, batch_size)
         dP = torch.empty((F, 2, Y, X), dtype=torch.float32, device=self.device)
         prob = torch.empty((F, Y, X), dtype=torch.float32, device=self.device)
         with self.eng.timed("average_tiles"):
@@ -265,6 +275,47 @@ class CellposeModel:
                                                g["bx"], g["ny"], g["nx"], _ptr(g["ys"]), _ptr(g["xs"]), _ptr(g["taper"]),
                                                _ptr(dP), _ptr(prob), _stream_ptr()))
         return dP, prob
+
+    # cellpose's run_3D: the 2-D network over the YX, ZY and ZX slices of the volume.  Per pass: (slice axis, image rows, image
+    # columns, the dP components its output channels 0 / 1 land in, add mask).  Run in this order, writing or adding, the passes
+    # leave cellpose's sums: dZ = ZY.0 + ZX.0, dY = YX.0 + ZX.1, dX = YX.1 + ZY.1, cellprob = (YX.2 + ZY.2) + ZX.2.
+    _PASSES_3D = (("YX", 0, 1, 2, (1, 2), 0b000), ("ZY", 1, 0, 2, (0, 2), 0b110), ("ZX", 2, 0, 1, (0, 1), 0b111))
+
+    def run_network_3d(self, vol: torch.Tensor, bsize=None, tile_overlap=None, batch_size=None):
+        """Normalised volumes float32 [F,Z,Y,X] -> (dP float32 [F,3,Z,Y,X] (dZ,dY,dX), cellprob float32 [F,Z,Y,X]): three passes
+        of the network over orthogonal slices, tiled and blended in place by strided kernels (no transposed copy of the volume).
+        Each pass sends the slices of all F volumes through the network together, batch_size tiles per forward."""
+        vol = vol.to(torch.float32).contiguous()
+        F, Z, Y, X = vol.shape
+        batch_size = self.batch_size if batch_size is None else max(1, int(batch_size))
+        lib, h = self.eng.lib, self.eng.ctx.handle
+        V = Z * Y * X
+        dP = torch.empty((F, 3, Z, Y, X), dtype=torch.float32, device=self.device)
+        prob = torch.empty((F, Z, Y, X), dtype=torch.float32, device=self.device)
+        dims, strides = (Z, Y, X), (Y * X, X, 1)
+        for _name, sa, ra, ca, (c0, c1), add in self._PASSES_3D:
+            S, rows, cols = dims[sa], dims[ra], dims[ca]
+            g = self._geometry(rows, cols, bsize, tile_overlap)
+            N = F * S
+            tiles = torch.empty((N * g["ny"] * g["nx"], 2, g["by"], g["bx"]), dtype=torch.float32, device=self.device)
+            with self.eng.timed("make_tiles"):
+                _lib.check(lib.aliby_make_tiles_strided(h, _ptr(vol), N, S, V, strides[sa], strides[ra], strides[ca], rows, cols,
+                                                        g["ypad1"], g["xpad1"], g["Ly"], g["Lx"], g["by"], g["bx"], g["ny"], g["nx"],
+                                                        _ptr(g["ys"]), _ptr(g["xs"]), 2, _ptr(tiles), _stream_ptr()))
+            yt = self._forward_tiles(tiles, g, batch_size)
+            del tiles
+            with self.eng.timed("average_tiles"):
+                _lib.check(lib.aliby_average_tiles_strided(h, _ptr(yt), N, S, 3 * V, V, strides[sa], strides[ra], strides[ca], V, c0,
+                                                           c1, add, rows, cols, g["ypad1"], g["xpad1"], g["Ly"], g["Lx"], g["by"],
+                                                           g["bx"], g["ny"], g["nx"], _ptr(g["ys"]), _ptr(g["xs"]), _ptr(g["taper"]),
+                                                           _ptr(dP), _ptr(prob), _stream_ptr()))
+        return dP, prob
+
+    def normalize_3d(self, vol: torch.Tensor, norm3D: bool) -> torch.Tensor:
+        """Volumes [F,Z,Y,X] -> float32: normalize99 per Z plane (norm3D False) or with one percentile pair per volume (True)."""
+        F, Z, Y, X = vol.shape
+        flat = vol.reshape(F, Z * Y, X) if norm3D else vol.reshape(F * Z, Y, X)
+        return self.normalize(flat).reshape(F, Z, Y, X)
 
     # ------------------------------------------------------------------------------------- eval
     # cellpose's other `eval` keywords (3.1 / 4.0 signatures) and the values at which they change nothing here: a caller who
@@ -296,7 +347,8 @@ class CellposeModel:
                        for n in self._EVAL_NEUTRAL[k]):
                 raise NotImplementedError(f"eval({k}={v!r}) is not built: only {self._EVAL_NEUTRAL[k]} (no effect) are accepted")
         if do_3D:
-            raise NotImplementedError("do_3D: hand the planes of the stack to eval as a batch and stitch them (segment/dispatch.py does)")
+            return self._eval_3d(x, normalize, z_axis, niter, cellprob_threshold, min_size, max_size_fraction, bsize, tile_overlap,
+                                 batch_size)
         if not isinstance(x, torch.Tensor):
             x = np.ascontiguousarray(x)
             x = torch.from_numpy(x if x.dtype == np.uint16 else x.astype(np.uint16 if x.dtype in (np.uint8, np.bool_) else np.float32))
@@ -305,15 +357,8 @@ class CellposeModel:
             x = x[None]
         if isinstance(normalize, dict):
             # cellpose's option dict: the reference passes dict(norm3D=False) on its 3-D branch (dispatch.py:196) = every plane
-            # normalised on its own, which is what a batch of planes gets here (so norm3D is moot for 2-D input).  Keys at the
-            # values that leave cellpose's default normalisation (1st / 99th percentile) unchanged pass; anything else is not built.
-            neutral = {"lowhigh": (None,), "percentile": (None, (1, 99), [1, 99], (1.0, 99.0), [1.0, 99.0]), "sharpen_radius": (0,),
-                       "smooth_radius": (0,), "tile_norm_blocksize": (0,), "invert": (False,)}
-            other_opts = {k: v for k, v in normalize.items() if k not in ("norm3D", "normalize", "tile_norm_smooth3D")
-                          and not (k in neutral and any(v is n or (n is not None and not isinstance(v, bool) and v == n) for n in neutral[k]))}
-            if other_opts:
-                raise NotImplementedError(f"normalize options {other_opts} are not built (percentile normalisation per plane is)")
-            normalize = bool(normalize.get("normalize", True))
+            # normalised on its own, which is what a batch of planes gets here (so norm3D is moot for 2-D input)
+            normalize, _ = self._normalize_options(normalize)
         dP = prob = None
         if self.flows_override is None or self.run_network_with_override:
             dP, prob = self.run_network(x, normalize=bool(normalize), bsize=bsize, tile_overlap=tile_overlap, batch_size=batch_size)
@@ -324,6 +369,56 @@ class CellposeModel:
             flow_threshold=flow_threshold, min_size=min_size, max_size_fraction=max_size_fraction,
         )
         dynamics._mark("eval:dynamics returned")
+        self.last_counts = counts
+        masks = labels[0] if labels.shape[0] == 1 else labels
+        return masks, [None, dP, prob], None
+
+    @staticmethod
+    def _normalize_options(normalize):
+        """cellpose's `normalize` argument -> (normalize?, norm3D).  Keys of the option dict at the values that leave cellpose's
+        default normalisation (1st / 99th percentile) unchanged pass; anything else is not built."""
+        if not isinstance(normalize, dict):
+            return bool(normalize), True
+        neutral = {"lowhigh": (None,), "percentile": (None, (1, 99), [1, 99], (1.0, 99.0), [1.0, 99.0]), "sharpen_radius": (0,),
+                   "smooth_radius": (0,), "tile_norm_blocksize": (0,), "invert": (False,)}
+        other_opts = {k: v for k, v in normalize.items() if k not in ("norm3D", "normalize", "tile_norm_smooth3D")
+                      and not (k in neutral and any(v is n or (n is not None and not isinstance(v, bool) and v == n) for n in neutral[k]))}
+        if other_opts:
+            raise NotImplementedError(f"normalize options {other_opts} are not built (percentile normalisation per plane is)")
+        return bool(normalize.get("normalize", True)), bool(normalize.get("norm3D", True))
+
+    def _eval_3d(self, x, normalize, z_axis, niter, cellprob_threshold, min_size, max_size_fraction, bsize, tile_overlap, batch_size):
+        """cellpose's do_3D mode: x is one volume [Z,Y,X] or a batch of F independent volumes [F,Z,Y,X] (an extension).
+        Normalisation once (per Z plane for norm3D=False, one percentile pair per volume for norm3D=True: cellpose's default), the
+        network over the YX / ZY / ZX slices (run_network_3d), then the 3-D dynamics (dynamics.masks_from_flows_3d; flow_threshold
+        is not used in 3-D, as in cellpose).  Returns (masks [Z,Y,X] for one volume else [F,Z,Y,X], [None, dP [F,3,Z,Y,X],
+        cellprob [F,Z,Y,X]], None).  flows_override(x [F,Z,Y,X]) -> (dP [F,3,Z,Y,X], cellprob [F,Z,Y,X]) replaces the network."""
+        if not isinstance(x, torch.Tensor):
+            x = np.ascontiguousarray(x)
+            x = torch.from_numpy(x if x.dtype == np.uint16 else x.astype(np.uint16 if x.dtype in (np.uint8, np.bool_) else np.float32))
+        x = x.to(self.device).contiguous()
+        if x.ndim not in (3, 4):
+            raise ValueError(f"do_3D: expected one volume [Z,Y,X] or a batch [F,Z,Y,X], got shape {tuple(x.shape)}")
+        if z_axis not in (None, x.ndim - 3):
+            raise NotImplementedError(f"do_3D with z_axis={z_axis}: the Z axis must lead each volume ([Z,Y,X] or [F,Z,Y,X])")
+        vol = x[None] if x.ndim == 3 else x
+        F, Z, Y, X = vol.shape
+        if Z < 2:
+            raise ValueError(f"do_3D needs Z >= 2 planes, got {Z}")
+        do_norm, norm3D = self._normalize_options(normalize)
+        dP = prob = None
+        if self.flows_override is None or self.run_network_with_override:
+            if do_norm:
+                vin = self.normalize_3d(vol, norm3D)
+            else:
+                vin = vol.to(torch.int32).to(torch.float32) if vol.dtype == torch.uint16 else vol.to(torch.float32)
+            dP, prob = self.run_network_3d(vin, bsize=bsize, tile_overlap=tile_overlap, batch_size=batch_size)
+        if self.flows_override is not None:
+            dP, prob = self.flows_override(vol)
+        labels, counts = dynamics.masks_from_flows_3d(
+            self.eng, dP, prob, niter=200 if niter is None else niter, cellprob_threshold=cellprob_threshold, min_size=min_size,
+            max_size_fraction=max_size_fraction,
+        )
         self.last_counts = counts
         masks = labels[0] if labels.shape[0] == 1 else labels
         return masks, [None, dP, prob], None

@@ -80,6 +80,15 @@ def dispatch_segmenter(kind: str, channel_to_segment: int, address: str = None, 
     # (dispatch.py:218-223: what the reference's cellpose branch does to a multi-tile batch).  The trap-tile time-lapse
     # workload (BASELINE config 4: tiles -> segment -> track -> extract) needs it; default False = reference behaviour.
     per_tile = bool(kwargs.get("per_tile", False))
+    # Extension: how `segment(pixels, do_3D=True)` treats a stack with Z > 1.  "stitch" (the default): every plane segmented in 2-D
+    # and the planes stitched along Z by IoU (_segment_volume).  "flows3d": cellpose's own 3-D mode, eval(do_3D=True) — the network
+    # over the YX / ZY / ZX slices and 3-D flow following (_segment_flows3d).  Either way the 3-D labels are kept on
+    # segment.last_volume and the step returns the reference's collapse (max over Z, relabel_sequential).
+    volume_mode = kwargs.get("volume_mode", "stitch")
+    if volume_mode not in ("stitch", "flows3d"):
+        raise ValueError(f"volume_mode={volume_mode!r}: expected 'stitch' or 'flows3d'")
+    if per_tile and volume_mode == "flows3d":
+        raise ValueError("per_tile=True takes 2-D tiles; volume_mode='flows3d' segments Z-stacks as volumes")
     setup_params = dict(kwargs.get("setup_params", {}))
     gpu = setup_params.pop("gpu", True)
     device = setup_params.pop("device", None)
@@ -150,7 +159,7 @@ def dispatch_segmenter(kind: str, channel_to_segment: int, address: str = None, 
         if pixels.ndim > 5:
             pixels = pixels[0]
         if do_3D and z_size > 1:
-            return _segment_volume(pixels, dict(kw))
+            return (_segment_flows3d if volume_mode == "flows3d" else _segment_volume)(pixels, dict(kw))
         stack, counts = _labels_of([_device_block(pixels)], dict(kw))
         return _finish(stack, counts)
 
@@ -173,6 +182,22 @@ def dispatch_segmenter(kind: str, channel_to_segment: int, address: str = None, 
         volume, counts = model.eng.stitch_planes(labels.view(F, Z, Y, X), threshold=0.01)
         segment.last_volume = (volume, counts)
         out = [_finish(volume[f], np.asarray([counts[f]])) for f in range(F)]
+        return out[0] if F == 1 else out
+
+    def _segment_flows3d(pixels, kw):
+        """The reference's do_3D branch through cellpose's 3-D mode: model.eval(stack, do_3D=True, normalize=dict(norm3D=False))
+        on every stack [F,Z,Y,X] of the block at once; the volume labels go to `segment.last_volume` = (uint16 device tensor
+        [F,Z,Y,X], objects per stack), the step result is their collapse (max over Z, relabel_sequential: dispatch.py:216-223)."""
+        block = _device_block(pixels)  # [F,C,Z,Y,X]
+        F, _, Z, Y, X = block.shape
+        vols = block[:, channel_to_segment].contiguous()  # [F,Z,Y,X]
+        kw.pop("normalize", None)
+        kw.pop("stitch_threshold", None)
+        masks = model.eval(vols, do_3D=True, normalize=dict(norm3D=False), z_axis=1, **kw)[0]
+        labels = masks if masks.ndim == 4 else masks[None]
+        counts = np.asarray(model.last_counts)
+        segment.last_volume = (labels, counts)
+        out = [_finish(labels[f], np.asarray([counts[f]])) for f in range(F)]
         return out[0] if F == 1 else out
 
     def segment_batch(blocks, pinned_alloc=None, **kw):
@@ -216,4 +241,5 @@ def dispatch_segmenter(kind: str, channel_to_segment: int, address: str = None, 
     segment.batch = segment_batch
     segment.channel_to_segment = channel_to_segment
     segment.per_tile = per_tile
+    segment.volume_mode = volume_mode
     return segment

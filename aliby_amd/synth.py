@@ -138,6 +138,31 @@ def analytic_flows(labels):
     return dP, prob
 
 
+def analytic_flows_3d(labels_zyx):
+    """Network-scale outputs for a volume's labels [Z,Y,X] (cellpose's do_3D): dP f32 [3,Z,Y,X] (dz,dy,dx) = 5 x unit vectors
+    pointing at each object's 3-D centre of mass, with analytic_flows' magnitude ramp (vanishing at the centre, 1 from 3 voxels
+    out), cellprob f32 [Z,Y,X] = +6 inside / -6 outside."""
+    labels_zyx = np.asarray(labels_zyx)
+    n = int(labels_zyx.max()) if labels_zyx.size else 0
+    Z, Y, X = labels_zyx.shape
+    dP = np.zeros((3, Z, Y, X), np.float32)
+    prob = np.full((Z, Y, X), -6.0, np.float32)
+    if n == 0:
+        return dP, prob
+    idx = np.arange(1, n + 1)
+    com = np.array(ndimage.center_of_mass(labels_zyx > 0, labels_zyx, idx), dtype=np.float64).reshape(n, 3)
+    com = np.nan_to_num(com)  # (ids without voxels)
+    inside = labels_zyx > 0
+    grid = np.mgrid[0:Z, 0:Y, 0:X]
+    d = [(np.concatenate([[0.0], com[:, k]])[labels_zyx] - grid[k]) * inside for k in range(3)]
+    nrm = np.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
+    mag = np.clip(nrm / 3.0, 0.0, 1.0)
+    nrm[nrm < 1e-6] = 1.0
+    for k in range(3):
+        dP[k] = (5.0 * d[k] / nrm * mag).astype(np.float32)
+    prob[inside] = 6.0
+    return dP, prob
+
 CONFIGS = {
     # id: (n_fov, C, Z, Y, X, n_target, segment_channel)
     1: dict(n_fov=1, C=2, Z=1, Y=512, X=512, n_target=60, seg_channel=1),

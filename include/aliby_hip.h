@@ -143,6 +143,20 @@ int aliby_average_tiles(aliby_ctx* ctx, const float* ytiles, int F, int Y, int X
                         int Ly, int Lx, int by, int bx, int ny, int nx, const int32_t* ystart_dev,
                         const int32_t* xstart_dev, const float* taper_dev, float* dP, float* cellprob,
                         void* stream);
+/* The same two steps over N slices of a batch of volumes, read and written in place (cellpose's do_3D passes): image n starts
+ * at (n / S) * vol_stride + (n % S) * slice_stride elements and its pixel (y, x) lies row_stride * y + col_stride * x further.
+ * aliby_average_tiles_strided writes output channel 0 / 1 into components comp0 / comp1 of dP (comp_stride elements apart,
+ * dP_vol_stride per volume) and channel 2 into cellprob (prob_vol_stride per volume), at the same slice / row / column
+ * offsets; bit k of add_mask adds channel k to the value already there (float32) instead of writing it. */
+int aliby_make_tiles_strided(aliby_ctx* ctx, const float* vol, int N, int S, long long vol_stride, long long slice_stride,
+                             long long row_stride, long long col_stride, int Y, int X, int ypad1, int xpad1, int Ly, int Lx,
+                             int by, int bx, int ny, int nx, const int32_t* ystart_dev, const int32_t* xstart_dev, int nchan,
+                             float* tiles, void* stream);
+int aliby_average_tiles_strided(aliby_ctx* ctx, const float* ytiles, int N, int S, long long dP_vol_stride,
+                                long long prob_vol_stride, long long slice_stride, long long row_stride, long long col_stride,
+                                long long comp_stride, int comp0, int comp1, int add_mask, int Y, int X, int ypad1, int xpad1,
+                                int Ly, int Lx, int by, int bx, int ny, int nx, const int32_t* ystart_dev,
+                                const int32_t* xstart_dev, const float* taper_dev, float* dP, float* cellprob, void* stream);
 
 /* Fused pointwise stage between two convolutions of the U-Net (bf16, NHWC): sum = A (+ B) (+ bias[c]), A/B
  * optionally read through a 2x nearest upsample; act = relu?(scale[c]*sum + shift[n,c] or shift[c]).
@@ -315,6 +329,17 @@ int aliby_masks_from_flows(aliby_ctx* ctx, const float* dP, const float* cellpro
                            int niter, float cellprob_threshold, float flow_threshold, int min_size,
                            float max_size_fraction, void* workspace, size_t workspace_bytes,
                            uint16_t* labels_out, int32_t* n_labels_host, float* p_final_out, void* stream);
+/* The same for volumes (cellpose's do_3D): dP [dev] [F,3,Z,Y,X] float32 (dZ,dY,dX at network scale), cellprob [dev]
+ * [F,Z,Y,X] -> labels_out [dev] uint16 [F,Z,Y,X], 1..n per volume, n_labels_host[F].  Trilinear flow following (grid_sample,
+ * align_corners=False, zero padding), 5x5x5 seeds, growth in 11x11x11 windows, masks above max_size_fraction of the volume and
+ * below min_size voxels dropped, 3-D holes (6-connected background) filled.  There is no flow-error QC in 3-D (cellpose: "not
+ * used for 3D").  workspace [dev] >= aliby_masks3d_workspace_bytes(F,Z,Y,X); p_final_out [dev, optional] [F,3,Z,Y,X] receives
+ * the end points of the foreground voxels.  ALIBY_ERR_OVERFLOW when a volume would need >= 65535 labels. */
+size_t aliby_masks3d_workspace_bytes(int F, int Z, int Y, int X);
+int aliby_masks_from_flows_3d(aliby_ctx* ctx, const float* dP, const float* cellprob, int F, int Z, int Y, int X, int niter,
+                              float cellprob_threshold, int min_size, float max_size_fraction, void* workspace,
+                              size_t workspace_bytes, uint16_t* labels_out, int32_t* n_labels_host, float* p_final_out,
+                              void* stream);
 
 /* ---- a13: cp_measure single-image features ------------------------------ */
 /* Call site wrap_cp_measure_features (loaders.py:135-150): fun(mask.astype(uint16), pixels).

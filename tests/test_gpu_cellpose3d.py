@@ -1,0 +1,273 @@
+"""
+cellpose's do_3D mode on the GPU: `CellposeModel.eval(x, do_3D=True)` (three orthogonal network passes, strided tiling /
+blending, 3-D dynamics in aliby_amd/csrc/dynamics3d.hip) and `dispatch_segmenter(volume_mode="flows3d")`.  The dynamics are
+checked bit for bit against the float32 restatement tests/cellpose3d_ref.py (itself pinned to grid_sample / max_pool3d /
+binary_fill_holes by tests/test_cpu_cellpose3d_ref.py); the network passes against the 2-D path on explicitly permuted copies.
+Parity against cellpose itself stays unpinned (not installable offline).
+"""
+import numpy as np
+import pytest
+
+from aliby_amd import synth
+from tests import cellpose3d_ref as ref
+
+pytestmark = pytest.mark.gpu
+
+
+def _gt(seed, shape, n_z, n_target):
+    f = synth.make_fov(5, seed, shape=shape, n_channels=2, n_z=n_z, n_target=n_target)
+    return f, synth.ellipsoid_planes(f["nuclei"], n_z, seed=seed)
+
+
+def _flows(gt, seed, noise=0.3):
+    """Analytic 3-D flows plus noise (so that the following does more than slide down a clean field)."""
+    dP, prob = synth.analytic_flows_3d(gt)
+    rng = np.random.default_rng(seed)
+    dP = (dP + rng.normal(0.0, noise, dP.shape)).astype(np.float32)
+    prob = (prob + rng.normal(0.0, 0.5, prob.shape)).astype(np.float32)
+    return dP, prob
+
+
+def _model(override=None, **kw):
+    from aliby_amd.segment.cellpose_hip import CellposeModel
+
+    return CellposeModel(flows_override=override, **kw)
+
+
+def _override_of(dP, prob):
+    """flows_override for a batch [F,Z,Y,X]: dP [F,3,Z,Y,X] / prob [F,Z,Y,X] (numpy, one volume's arrays broadcast if 4-D / 3-D)."""
+    import torch
+
+    def override(x):
+        F = x.shape[0]
+        d = dP if dP.ndim == 5 else np.broadcast_to(dP, (F, *dP.shape))
+        p = prob if prob.ndim == 4 else np.broadcast_to(prob, (F, *prob.shape))
+        assert d.shape[0] == F and tuple(d.shape[2:]) == tuple(x.shape[1:])
+        return torch.from_numpy(np.ascontiguousarray(d)).cuda(), torch.from_numpy(np.ascontiguousarray(p)).cuda()
+
+    return override
+
+
+# ------------------------------------------------------------------------------------------------ 1. dynamics vs restatement
+@pytest.mark.parametrize("seed,shape,n_z,n_target", [(0, (64, 64), 5, 6), (1, (48, 56), 32, 4), (2, (61, 83), 7, 6),
+                                                     (3, (128, 128), 16, 12)])
+def test_eval_3d_dynamics_equal_the_restatement(engine, seed, shape, n_z, n_target):
+    import torch
+
+    from aliby_amd.segment.dynamics import masks_from_flows_3d
+
+    _, gt = _gt(seed, shape, n_z, n_target)
+    dP, prob = _flows(gt, seed)
+    want, n, pf_want = ref.compute_masks_3d(dP, prob)
+    assert n > 0
+    model = _model(_override_of(dP, prob))
+    masks, flows, styles = model.eval(np.zeros(gt.shape, np.uint16), do_3D=True)
+    assert masks.shape == gt.shape and masks.dtype == torch.uint16 and styles is None
+    assert tuple(flows[1].shape) == (1, 3, *gt.shape) and tuple(flows[2].shape) == (1, *gt.shape)
+    assert list(model.last_counts) == [n]
+    assert np.array_equal(masks.cpu().numpy(), want)
+    # the end points of the flow following, and a batch of two volumes (the second one the first mirrored in Y)
+    dP2 = np.stack([dP, dP[:, :, ::-1] * np.array([1, -1, 1], np.float32)[:, None, None, None]])
+    prob2 = np.stack([prob, prob[:, ::-1]])
+    lab, cnt, pf = masks_from_flows_3d(engine, torch.from_numpy(np.ascontiguousarray(dP2)).cuda(),
+                                       torch.from_numpy(np.ascontiguousarray(prob2)).cuda(), return_endpoints=True)
+    assert np.array_equal(pf[0].cpu().numpy(), pf_want)
+    want2, n2, pf2 = ref.compute_masks_3d(np.ascontiguousarray(dP2[1]), np.ascontiguousarray(prob2[1]))
+    assert list(cnt) == [n, n2]
+    assert np.array_equal(lab[0].cpu().numpy(), want) and np.array_equal(lab[1].cpu().numpy(), want2)
+    assert np.array_equal(pf[1].cpu().numpy(), pf2)
+
+
+def test_dynamics_3d_do_not_depend_on_what_the_workspace_held(engine):
+    """The per-seed words, the owner map and the object table are initialised where they are used, not by memsets of the whole
+    workspace: whatever it held before, the labels are the same."""
+    import torch
+
+    from aliby_amd.segment import dynamics
+
+    _, gt = _gt(6, (64, 72), 9, 6)
+    dP, prob = (torch.from_numpy(a).cuda() for a in _flows(gt, 6))
+    want, n_want = dynamics.masks_from_flows_3d(engine, dP[None], prob[None])
+    ws = dynamics._workspaces3d[(str(dP.device),)]
+    for fill in (0x00, 0xFF, 0x7F):
+        ws.fill_(fill)
+        got, n = dynamics.masks_from_flows_3d(engine, dP[None], prob[None])
+        assert list(n) == list(n_want) and torch.equal(got, want), fill
+
+
+# ------------------------------------------------------------------------------------------------ 2. the network passes
+def _combined_2d(model, norm, batch_size=None):
+    """run_network(normalize=False) on permuted copies of the normalised volume [Z,Y,X], combined like cellpose's run_3D."""
+    yx_d, yx_p = model.run_network(norm.contiguous(), normalize=False, batch_size=batch_size)                    # [Z,2,Y,X]
+    zy_d, zy_p = model.run_network(norm.permute(1, 0, 2).contiguous(), normalize=False, batch_size=batch_size)  # [Y,2,Z,X]
+    zx_d, zx_p = model.run_network(norm.permute(2, 0, 1).contiguous(), normalize=False, batch_size=batch_size)  # [X,2,Z,Y]
+    yx = yx_d.permute(1, 0, 2, 3)  # [2,Z,Y,X]
+    zy = zy_d.permute(1, 2, 0, 3)
+    zx = zx_d.permute(1, 2, 3, 0)
+    import torch
+
+    dP = torch.stack([zy[0] + zx[0], yx[0] + zx[1], yx[1] + zy[1]])
+    prob = (yx_p + zy_p.permute(1, 0, 2)) + zx_p.permute(1, 2, 0)
+    return dP, prob
+
+
+@pytest.mark.parametrize("norm3D", [False, True])
+def test_network_passes_equal_permuted_2d_runs(norm3D):
+    import torch
+
+    f, _ = _gt(7, (64, 80), 6, 5)
+    vol = torch.from_numpy(f["pixels"][0]).cuda()  # uint16 [Z,Y,X]
+    model = _model(seed=3)
+    assert model.fused is not None
+    Z, Y, X = vol.shape
+    masks, flows, _ = model.eval(vol, do_3D=True, normalize=dict(norm3D=norm3D), batch_size=16)
+    dP, prob = flows[1], flows[2]
+    assert tuple(dP.shape) == (1, 3, Z, Y, X) and tuple(prob.shape) == (1, Z, Y, X) and tuple(masks.shape) == (Z, Y, X)
+    norm = model.normalize(vol.reshape(1, Z * Y, X)).reshape(Z, Y, X) if norm3D else model.normalize(vol)
+    want_d, want_p = _combined_2d(model, norm, batch_size=16)
+    assert torch.equal(dP[0], want_d) and torch.equal(prob[0], want_p)
+    # a batch of two volumes equals two single calls, bit for bit
+    vol2 = torch.from_numpy(f["pixels"][1]).cuda()
+    _, flows_b, _ = model.eval(torch.stack([vol, vol2]), do_3D=True, normalize=dict(norm3D=norm3D), batch_size=16)
+    m2, flows_2, _ = model.eval(vol2, do_3D=True, normalize=dict(norm3D=norm3D), batch_size=16)
+    assert torch.equal(flows_b[1][0], dP[0]) and torch.equal(flows_b[2][0], prob[0])
+    assert torch.equal(flows_b[1][1], flows_2[1][0]) and torch.equal(flows_b[2][1], flows_2[2][0])
+
+
+# ------------------------------------------------------------------------------------------------ 3. through segment
+def test_segment_flows3d_collapses_last_volume(engine):
+    import torch
+
+    from aliby_amd.segment.dispatch import dispatch_segmenter
+    from oracle import tiler_ref
+    from oracle import volume_restated as vr
+
+    f, gt = _gt(4, (96, 112), 8, 8)
+    dP, prob = _flows(gt, 4)
+    want, n, _ = ref.compute_masks_3d(dP, prob)
+    seen = []
+
+    def override(x):
+        seen.append(tuple(x.shape))
+        return _override_of(dP, prob)(x)
+
+    segment = dispatch_segmenter(kind="cellpose", channel_to_segment=0, volume_mode="flows3d",
+                                 setup_params=dict(flows_override=override))
+    labels2d = segment(f["pixels"][None], do_3D=True)
+    assert seen == [(1, *gt.shape)]
+    volume, counts = segment.last_volume
+    assert volume.dtype == torch.uint16 and tuple(volume.shape) == (1, *gt.shape)
+    assert list(counts) == [n] and np.array_equal(volume[0].cpu().numpy(), want)
+    assert labels2d.dtype == np.uint16 and np.array_equal(labels2d, tiler_ref.relabel_sequential(want.max(axis=0)))
+    # 3-D intensity features of the volume labels
+    px = torch.from_numpy(f["pixels"][None]).cuda()
+    for c in (0, 1):
+        got = engine.intensity3d(volume, px, c, counts).cpu().numpy()
+        exp = vr.intensity3d(want, f["pixels"][c])
+        assert got.shape == exp.shape == (n, 12)
+        assert np.allclose(got, exp, rtol=1e-10, atol=1e-9, equal_nan=True)
+    # the default mode is still the per-plane stitching, and an unknown mode is refused
+    assert dispatch_segmenter(kind="cellpose", channel_to_segment=0, setup_params=dict(flows_override=override)).volume_mode == "stitch"
+    with pytest.raises(ValueError):
+        dispatch_segmenter(kind="cellpose", channel_to_segment=0, volume_mode="volume")
+    with pytest.raises(ValueError):
+        dispatch_segmenter(kind="cellpose", channel_to_segment=0, volume_mode="flows3d", per_tile=True)
+
+
+def test_segment_flows3d_single_plane_takes_the_2d_path():
+    import torch
+
+    from aliby_amd.segment.dispatch import dispatch_segmenter
+    from oracle import cellpose_restated as cr
+
+    f = synth.make_fov(5, 9, shape=(96, 96), n_channels=1, n_z=1, n_target=6)
+    dP, prob = synth.analytic_flows(f["nuclei"])
+
+    def override(x):
+        assert x.ndim == 3 and x.shape[0] == 1  # the 2-D eval's [F,Y,X]
+        return torch.from_numpy(dP[None]).cuda(), torch.from_numpy(prob[None]).cuda()
+
+    segment = dispatch_segmenter(kind="cellpose", channel_to_segment=0, volume_mode="flows3d",
+                                 setup_params=dict(flows_override=override))
+    got = segment(f["pixels"][None], do_3D=True)
+    assert np.array_equal(got, segment(f["pixels"][None], do_3D=False))
+    assert np.array_equal(got, cr.finish_labels(cr.compute_masks(dP, prob)))
+
+
+# ------------------------------------------------------------------------------------------------ 4. edges
+def _ellipsoid(shape, centre, radii):
+    zz, yy, xx = np.mgrid[0 : shape[0], 0 : shape[1], 0 : shape[2]]
+    r2 = sum(((g - c) / r) ** 2 for g, c, r in zip((zz, yy, xx), centre, radii))
+    return r2 <= 1.0
+
+
+def _check(dP, prob, **kw):
+    """eval(do_3D=True) through flows_override against the restatement; returns the labels and the count."""
+    want, n, _ = ref.compute_masks_3d(dP, prob, **kw)
+    model = _model(_override_of(dP, prob))
+    masks, _, _ = model.eval(np.zeros(prob.shape, np.uint16), do_3D=True, **kw)
+    got = masks.cpu().numpy()
+    assert list(model.last_counts) == [n] and np.array_equal(got, want)
+    return got, n
+
+
+def test_empty_volume():
+    prob = np.full((6, 40, 48), -6.0, np.float32)
+    got, n = _check(np.zeros((3, *prob.shape), np.float32), prob)
+    assert n == 0 and not got.any()
+
+
+def test_small_masks_vanish_and_big_masks_are_removed():
+    shape = (10, 40, 40)
+    lab = np.zeros(shape, np.uint16)
+    lab[_ellipsoid(shape, (4, 10, 10), (1.2, 2.2, 2.2))] = 1   # ~20 voxels
+    lab[_ellipsoid(shape, (5, 28, 28), (3.5, 7, 7))] = 2       # ~700 voxels
+    dP, prob = synth.analytic_flows_3d(lab)
+    small = int((lab == 1).sum())
+    got, n = _check(dP, prob, min_size=small + 1)
+    assert n == 1 and not got[lab == 1].any() and got[lab == 2].all()
+    got, n = _check(dP, prob, min_size=small - 1)
+    assert n == 2
+    # a mask above max_size_fraction of the volume is removed
+    got, n = _check(dP, prob, max_size_fraction=0.5 * float((lab == 2).sum()) / lab.size)
+    assert n == 1 and not got[lab == 2].any()
+
+
+def test_cavity_is_filled():
+    shape = (16, 48, 48)
+    solid = _ellipsoid(shape, (8, 23.7, 23.6), (6, 16, 16))
+    # an enclosed 2x2x1 cavity off the centre: small enough that the points behind it are carried across it by the interpolated
+    # flow (a wide cavity stops them at its far wall, where they form a second mask)
+    cavity = np.zeros(shape, bool)
+    cavity[8:10, 24:26, 30] = True
+    lab = (solid & ~cavity).astype(np.uint16)
+    dP, prob = synth.analytic_flows_3d(lab)
+    got, n = _check(dP, prob)
+    assert n == 1 and (got[cavity] == 1).all() and (prob[cavity] < 0).all()
+
+
+def test_box_beyond_lds_takes_the_global_fill():
+    """A 41 x 61 x 61 box (+ ring: 168 k cells) does not fit the 128 KB LDS form: the grid-strided global-scratch fill runs."""
+    shape = (44, 72, 72)
+    solid = _ellipsoid(shape, (21.5, 35.5, 35.5), (20.4, 30.4, 30.4))
+    cavity = np.zeros(shape, bool)
+    cavity[21:23, 35:37, 45] = True
+    lab = (solid & ~cavity).astype(np.uint16)
+    zz, yy, xx = np.nonzero(lab)
+    assert (np.ptp(zz) + 3) * (np.ptp(yy) + 3) * (np.ptp(xx) + 3) > 128 * 1024
+    dP, prob = synth.analytic_flows_3d(lab)
+    got, n = _check(dP, prob)
+    assert n == 1 and (got[cavity] == 1).all()
+
+
+def test_refusals():
+    model = _model(_override_of(np.zeros((3, 4, 16, 16), np.float32), np.full((4, 16, 16), -6.0, np.float32)))
+    vol = np.zeros((4, 16, 16), np.uint16)
+    with pytest.raises(NotImplementedError):
+        model.eval(vol, do_3D=True, anisotropy=2.0)
+    with pytest.raises(NotImplementedError):
+        model.eval(vol, do_3D=True, flow3D_smooth=1)
+    with pytest.raises(ValueError):
+        model.eval(np.zeros((1, 16, 16), np.uint16)[None], do_3D=True)  # Z == 1
+    masks, _, _ = model.eval(vol, do_3D=True, flow_threshold=0.9)  # accepted, and not used in 3-D
+    assert not masks.cpu().numpy().any()
