@@ -163,70 +163,28 @@ struct TileGeom {
   int nchan;            // network input channels (channel 0 = image, the rest zero)
 };
 
-__global__ void k_make_tiles(const float* __restrict__ img, TileGeom g, const int* __restrict__ ystart,
-                             const int* __restrict__ xstart, float* __restrict__ tiles) {
-  const size_t per_tile = (size_t)g.nchan * g.by * g.bx;
-  const size_t total = (size_t)g.F * g.ny * g.nx * per_tile;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t t = i / per_tile, rem = i % per_tile;
-    const int ch = (int)(rem / ((size_t)g.by * g.bx));
-    const int r = (int)((rem / g.bx) % g.by), c = (int)(rem % g.bx);
-    const int f = (int)(t / (g.ny * g.nx)), k = (int)(t % (g.ny * g.nx));
-    float v = 0.0f;
-    if (ch == 0) {
-      const int y = ystart[k / g.nx] + r - g.ypad1, x = xstart[k % g.nx] + c - g.xpad1;
-      if (y >= 0 && y < g.Y && x >= 0 && x < g.X) v = img[((size_t)f * g.Y + y) * g.X + x];
-    }
-    tiles[i] = v;
-  }
-}
-
-// net output tiles [F*ny*nx, 3, by, bx] -> dP [F,2,Y,X], cellprob [F,Y,X]: taper-weighted average,
-// accumulated in tile order (float32), cropped back to the unpadded image
-__global__ void k_average_tiles(const float* __restrict__ ytiles, TileGeom g, const int* __restrict__ ystart,
-                                const int* __restrict__ xstart, const float* __restrict__ taper,
-                                float* __restrict__ dP, float* __restrict__ prob) {
-  const size_t P = (size_t)g.Y * g.X;
-  const size_t total = (size_t)g.F * P;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int f = (int)(i / P);
-    const int y = (int)((i % P) / g.X), x = (int)(i % g.X);
-    const int yp = y + g.ypad1, xp = x + g.xpad1;
-    float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, nav = 0.0f;
-    for (int j = 0; j < g.ny; ++j) {
-      const int r = yp - ystart[j];
-      if (r < 0 || r >= g.by) continue;
-      for (int q = 0; q < g.nx; ++q) {
-        const int c = xp - xstart[q];
-        if (c < 0 || c >= g.bx) continue;
-        const float m = taper[r * g.bx + c];
-        const size_t base = (((size_t)f * g.ny * g.nx + (size_t)j * g.nx + q) * 3) * g.by * g.bx + (size_t)r * g.bx + c;
-        a0 = a0 + ytiles[base] * m;
-        a1 = a1 + ytiles[base + (size_t)g.by * g.bx] * m;
-        a2 = a2 + ytiles[base + 2 * (size_t)g.by * g.bx] * m;
-        nav = nav + m;
-      }
-    }
-    dP[((size_t)f * 2 + 0) * P + (i % P)] = a0 / nav;
-    dP[((size_t)f * 2 + 1) * P + (i % P)] = a1 / nav;
-    prob[i] = a2 / nav;
-  }
-}
-
-// ---- strided tiling / blending (cellpose's do_3D: three orthogonal stacks of slices of one volume) -----------------------------
-// Image n of a pass starts at (n / S) * vol_stride + (n % S) * slice_stride and walks its rows / columns with its own strides, so one
-// kernel reads the YX, ZY and ZX slices of a batch of volumes [F,Z,Y,X] in place, without a transposed copy.  Per pixel the
-// arithmetic is k_make_tiles' / k_average_tiles' for a 2-D image of that shape.
+// Image n of a batch starts at (n / S) * vol_stride + (n % S) * slice_stride and walks its rows / columns with its own strides.
+// A batch of images [F,Y,X] is the identity map (S = 1, vol_stride = Y*X, slice_stride = 0, row = X, col = 1); cellpose's do_3D
+// reads the YX, ZY and ZX slices of a batch of volumes [F,Z,Y,X] in place (S = Z, Y or X), without a transposed copy.
 struct SliceMap {
   long long vol_stride, slice_stride, row_stride, col_stride;
   int S;  // slices per volume
 };
 
+// SLICED = false: S == 1, image n is volume n (no division by S: it cost the image batch 12-16 % of the tiling and blending time)
+template <bool SLICED>
+__device__ __forceinline__ long long volume_of(const SliceMap& m, int n) { return SLICED ? n / m.S : n; }
+template <bool SLICED>
+__device__ __forceinline__ long long slice_of(const SliceMap& m, int n) { return SLICED ? n % m.S : 0; }
+
+template <bool SLICED>
 __device__ __forceinline__ size_t slice_offset(const SliceMap& m, int n, int r, int c) {
-  return (size_t)((long long)(n / m.S) * m.vol_stride + (long long)(n % m.S) * m.slice_stride + (long long)r * m.row_stride +
+  return (size_t)(volume_of<SLICED>(m, n) * m.vol_stride + slice_of<SLICED>(m, n) * m.slice_stride + (long long)r * m.row_stride +
                   (long long)c * m.col_stride);
 }
 
+// tiles [N*ny*nx, nchan, by, bx] of the zero-padded images: channel 0 = image, the rest zero
+template <bool SLICED>
 __global__ void k_make_tiles_strided(const float* __restrict__ vol, TileGeom g, SliceMap m, const int* __restrict__ ystart,
                                      const int* __restrict__ xstart, float* __restrict__ tiles) {
   const size_t per_tile = (size_t)g.nchan * g.by * g.bx;
@@ -239,15 +197,17 @@ __global__ void k_make_tiles_strided(const float* __restrict__ vol, TileGeom g, 
     float v = 0.0f;
     if (ch == 0) {
       const int y = ystart[k / g.nx] + r - g.ypad1, x = xstart[k % g.nx] + c - g.xpad1;
-      if (y >= 0 && y < g.Y && x >= 0 && x < g.X) v = vol[slice_offset(m, n, y, x)];
+      if (y >= 0 && y < g.Y && x >= 0 && x < g.X) v = vol[slice_offset<SLICED>(m, n, y, x)];
     }
     tiles[i] = v;
   }
 }
 
-// net output tiles [N*ny*nx, 3, by, bx] -> channel 0 / 1 into components comp0 / comp1 of dP [F,3,...] (comp_stride apart, the
-// volume's spatial layout given by m with vol_stride = one volume of dP), channel 2 into cellprob (m with prob_vol_stride).
+// net output tiles [N*ny*nx, 3, by, bx] -> taper-weighted average, accumulated in tile order (float32), cropped back to the
+// unpadded image: channel 0 / 1 into components comp0 / comp1 of dP (comp_stride apart, the spatial layout given by m with
+// vol_stride = one frame of dP), channel 2 into cellprob (m with prob_vol_stride).
 // add_mask bit k: channel k is added to what is there (float32, after the blend) instead of written.
+template <bool SLICED>
 __global__ void k_average_tiles_strided(const float* __restrict__ ytiles, TileGeom g, SliceMap m, long long prob_vol_stride,
                                         long long comp_stride, int comp0, int comp1, int add_mask,
                                         const int* __restrict__ ystart, const int* __restrict__ xstart,
@@ -274,9 +234,9 @@ __global__ void k_average_tiles_strided(const float* __restrict__ ytiles, TileGe
       }
     }
     const float v0 = a0 / nav, v1 = a1 / nav, v2 = a2 / nav;
-    const size_t od = slice_offset(m, n, y, x);
-    const size_t spatial = (size_t)((long long)(n % m.S) * m.slice_stride + (long long)y * m.row_stride + (long long)x * m.col_stride);
-    const size_t op = (size_t)((long long)(n / m.S) * prob_vol_stride) + spatial;
+    const size_t od = slice_offset<SLICED>(m, n, y, x);
+    const size_t spatial = (size_t)(slice_of<SLICED>(m, n) * m.slice_stride + (long long)y * m.row_stride + (long long)x * m.col_stride);
+    const size_t op = (size_t)(volume_of<SLICED>(m, n) * prob_vol_stride) + spatial;
     float* d0 = dP + od + (size_t)((long long)comp0 * comp_stride);
     float* d1 = dP + od + (size_t)((long long)comp1 * comp_stride);
     *d0 = (add_mask & 1) ? *d0 + v0 : v0;
@@ -354,33 +314,22 @@ int aliby_normalize99_u16(aliby_ctx* ctx, const uint16_t* img, int F, int Y, int
   return ALIBY_OK;
 }
 
+// a batch of images [F,Y,X] (dP [F,2,Y,X], cellprob [F,Y,X]) is the strided form's identity slice map
 int aliby_make_tiles(aliby_ctx* ctx, const float* img, int F, int Y, int X, int ypad1, int xpad1, int Ly, int Lx,
                      int by, int bx, int ny, int nx, const int32_t* ystart_dev, const int32_t* xstart_dev,
                      int nchan, float* tiles, void* stream) {
-  ARG_CHECK(ctx != nullptr, "ctx is NULL");
-  if (F == 0) return ALIBY_OK;
-  ARG_CHECK(img && ystart_dev && xstart_dev && tiles, "NULL argument");
-  ARG_CHECK(by > 0 && bx > 0 && ny > 0 && nx > 0 && nchan > 0 && by <= Ly && bx <= Lx, "bad tile geometry");
-  TileGeom g{F, Y, X, ypad1, xpad1, Ly, Lx, by, bx, ny, nx, nchan};
-  const size_t total = (size_t)F * ny * nx * nchan * by * bx;
-  hipLaunchKernelGGL(k_make_tiles, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), img, g, ystart_dev, xstart_dev, tiles);
-  KERNEL_CHECK();
-  return ALIBY_OK;
+  const long long P = (long long)Y * X;
+  return aliby_make_tiles_strided(ctx, img, F, 1, P, 0, X, 1, Y, X, ypad1, xpad1, Ly, Lx, by, bx, ny, nx, ystart_dev, xstart_dev,
+                                  nchan, tiles, stream);
 }
 
 int aliby_average_tiles(aliby_ctx* ctx, const float* ytiles, int F, int Y, int X, int ypad1, int xpad1, int Ly,
                         int Lx, int by, int bx, int ny, int nx, const int32_t* ystart_dev,
                         const int32_t* xstart_dev, const float* taper_dev, float* dP, float* cellprob,
                         void* stream) {
-  ARG_CHECK(ctx != nullptr, "ctx is NULL");
-  if (F == 0) return ALIBY_OK;
-  ARG_CHECK(ytiles && ystart_dev && xstart_dev && taper_dev && dP && cellprob, "NULL argument");
-  ARG_CHECK(by > 0 && bx > 0 && ny > 0 && nx > 0, "bad tile geometry");
-  TileGeom g{F, Y, X, ypad1, xpad1, Ly, Lx, by, bx, ny, nx, 3};
-  hipLaunchKernelGGL(k_average_tiles, dim3(grid_for((size_t)F * Y * X)), dim3(256), 0, as_stream(stream), ytiles, g,
-                     ystart_dev, xstart_dev, taper_dev, dP, cellprob);
-  KERNEL_CHECK();
-  return ALIBY_OK;
+  const long long P = (long long)Y * X;
+  return aliby_average_tiles_strided(ctx, ytiles, F, 1, 2 * P, P, 0, X, 1, P, 0, 1, 0, Y, X, ypad1, xpad1, Ly, Lx, by, bx, ny, nx,
+                                     ystart_dev, xstart_dev, taper_dev, dP, cellprob, stream);
 }
 
 int aliby_make_tiles_strided(aliby_ctx* ctx, const float* vol, int N, int S, long long vol_stride, long long slice_stride,
@@ -396,8 +345,12 @@ int aliby_make_tiles_strided(aliby_ctx* ctx, const float* vol, int N, int S, lon
   TileGeom g{N, Y, X, ypad1, xpad1, Ly, Lx, by, bx, ny, nx, nchan};
   SliceMap m{vol_stride, slice_stride, row_stride, col_stride, S};
   const size_t total = (size_t)N * ny * nx * nchan * by * bx;
-  hipLaunchKernelGGL(k_make_tiles_strided, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), vol, g, m, ystart_dev, xstart_dev,
-                     tiles);
+  if (S == 1)
+    hipLaunchKernelGGL(k_make_tiles_strided<false>, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), vol, g, m, ystart_dev,
+                       xstart_dev, tiles);
+  else
+    hipLaunchKernelGGL(k_make_tiles_strided<true>, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), vol, g, m, ystart_dev,
+                       xstart_dev, tiles);
   KERNEL_CHECK();
   return ALIBY_OK;
 }
@@ -417,8 +370,12 @@ int aliby_average_tiles_strided(aliby_ctx* ctx, const float* ytiles, int N, int 
                 comp_stride >= 0, "negative stride");
   TileGeom g{N, Y, X, ypad1, xpad1, Ly, Lx, by, bx, ny, nx, 3};
   SliceMap m{dP_vol_stride, slice_stride, row_stride, col_stride, S};
-  hipLaunchKernelGGL(k_average_tiles_strided, dim3(grid_for((size_t)N * Y * X)), dim3(256), 0, as_stream(stream), ytiles, g, m,
-                     prob_vol_stride, comp_stride, comp0, comp1, add_mask, ystart_dev, xstart_dev, taper_dev, dP, cellprob);
+  if (S == 1)
+    hipLaunchKernelGGL(k_average_tiles_strided<false>, dim3(grid_for((size_t)N * Y * X)), dim3(256), 0, as_stream(stream), ytiles, g,
+                       m, prob_vol_stride, comp_stride, comp0, comp1, add_mask, ystart_dev, xstart_dev, taper_dev, dP, cellprob);
+  else
+    hipLaunchKernelGGL(k_average_tiles_strided<true>, dim3(grid_for((size_t)N * Y * X)), dim3(256), 0, as_stream(stream), ytiles, g,
+                       m, prob_vol_stride, comp_stride, comp0, comp1, add_mask, ystart_dev, xstart_dev, taper_dev, dP, cellprob);
   KERNEL_CHECK();
   return ALIBY_OK;
 }

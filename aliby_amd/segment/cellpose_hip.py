@@ -14,7 +14,7 @@ offline, so tests and bench.py feed analytic flows deriv
 ground truth into the same dynamics.
 
 `eval(x, do_3D=True)` is cellpose's 3-D mode for volumes [Z,Y,X] / [F,Z,Y,X]: the network over the YX, ZY and ZX slices
-(strided tiling / blending, HIP), flows summed per axis, then the 3-D dynamics (csrc/dynamics3d.hip).  Its flows_override
+(strided tiling / blending, HIP), flows summed per axis, then the 3-D dynamics (csrc/dynamics.hip).  Its flows_override
 takes [F,Z,Y,X] and returns (dP [F,3,Z,Y,X], cellprob [F,Z,Y,X]).
 """
 

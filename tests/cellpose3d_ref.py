@@ -1,6 +1,6 @@
 """
 Float32 restatement of cellpose's 3-D dynamics (compute_masks on a [3,Z,Y,X] flow field, do_3D=True), the yardstick of
-aliby_amd/csrc/dynamics3d.hip.  Every float32 operation is written out in the order the kernels use, so labels compare bit for
+aliby_amd/csrc/dynamics.hip.  Every float32 operation is written out in the order the kernels use, so labels compare bit for
 bit; where cellpose leaves an order to an unstable sort (overlapping seeds) the restatement fixes it as the 2-D one does
 (oracle/cellpose_restated.py): seed priority = (points in the bin, raster position), a later seed overwrites an earlier one.
 

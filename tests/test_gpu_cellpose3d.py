@@ -1,6 +1,6 @@
 """
 cellpose's do_3D mode on the GPU: `CellposeModel.eval(x, do_3D=True)` (three orthogonal network passes, strided tiling /
-blending, 3-D dynamics in aliby_amd/csrc/dynamics3d.hip) and `dispatch_segmenter(volume_mode="flows3d")`.  The dynamics are
+blending, 3-D dynamics in aliby_amd/csrc/dynamics.hip) and `dispatch_segmenter(volume_mode="flows3d")`.  The dynamics are
 checked bit for bit against the float32 restatement tests/cellpose3d_ref.py (itself pinned to grid_sample / max_pool3d /
 binary_fill_holes by tests/test_cpu_cellpose3d_ref.py); the network passes against the 2-D path on explicitly permuted copies.
 Parity against cellpose itself stays unpinned (not installable offline).
@@ -78,9 +78,9 @@ def test_eval_3d_dynamics_equal_the_restatement(engine, seed, shape, n_z, n_targ
     assert np.array_equal(pf[1].cpu().numpy(), pf2)
 
 
-def test_dynamics_3d_do_not_depend_on_what_the_workspace_held(engine):
+def test_dynamics_3d_do_not_depend_on_what_the_shared_workspace_held(engine):
     """The per-seed words, the owner map and the object table are initialised where they are used, not by memsets of the whole
-    workspace: whatever it held before, the labels are the same."""
+    workspace (one per device, shared with the image dynamics): whatever it held before, the labels are the same."""
     import torch
 
     from aliby_amd.segment import dynamics
@@ -88,11 +88,30 @@ def test_dynamics_3d_do_not_depend_on_what_the_workspace_held(engine):
     _, gt = _gt(6, (64, 72), 9, 6)
     dP, prob = (torch.from_numpy(a).cuda() for a in _flows(gt, 6))
     want, n_want = dynamics.masks_from_flows_3d(engine, dP[None], prob[None])
-    ws = dynamics._workspaces3d[(str(dP.device),)]
+    ws = dynamics._workspaces[(str(dP.device),)]
     for fill in (0x00, 0xFF, 0x7F):
         ws.fill_(fill)
         got, n = dynamics.masks_from_flows_3d(engine, dP[None], prob[None])
         assert list(n) == list(n_want) and torch.equal(got, want), fill
+
+
+def test_dynamics_3d_do_not_depend_on_the_order_of_the_foreground_list(engine, monkeypatch):
+    """The volume twin of tests/test_gpu_segment.py::test_dynamics_do_not_depend_on_the_order_of_the_foreground_list: with
+    ALIBY_DEBUG_FG_REVERSE=1 the 4096-voxel chunks of the compacted foreground list land in descending order (masks span many
+    chunk boundaries here), and labels, counts and end points are still the restatement's."""
+    import torch
+
+    from aliby_amd.segment.dynamics import masks_from_flows_3d
+
+    _, gt = _gt(3, (128, 128), 16, 12)
+    dP, prob = _flows(gt, 3)
+    want, n, pf_want = ref.compute_masks_3d(dP, prob)
+    assert n > 0
+    monkeypatch.setenv("ALIBY_DEBUG_FG_REVERSE", "1")
+    lab, cnt, pf = masks_from_flows_3d(engine, torch.from_numpy(dP[None]).cuda(), torch.from_numpy(prob[None]).cuda(),
+                                       return_endpoints=True)
+    assert list(cnt) == [n] and np.array_equal(lab[0].cpu().numpy(), want)
+    assert np.array_equal(pf[0].cpu().numpy(), pf_want)
 
 
 # ------------------------------------------------------------------------------------------------ 2. the network passes
