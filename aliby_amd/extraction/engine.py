@@ -331,6 +331,26 @@ class FeatureEngine:
                                                            _stream_ptr()))
         return out
 
+    def sizeshape3d(self, volume: torch.Tensor, counts, spacing=(1.0, 1.0, 1.0)) -> torch.Tensor:
+        """Volume labels uint16 [F,Z,Y,X] (1..counts[f] per stack) -> float64 [sum counts, 19] (features.sizeshape3d_names();
+        aliby_features_sizeshape3d).  Rows in (stack, label) order; spacing = physical voxel size (dz, dy, dx).  A label of
+        1..counts[f] without voxels gets Volume 0 and NaN elsewhere, as in intensity3d."""
+        assert volume.dtype == torch.uint16 and volume.dim() == 4 and volume.is_cuda
+        F, Z, Y, X = volume.shape
+        assert len(counts) == F
+        sp = np.ascontiguousarray(np.asarray(spacing, np.float64).reshape(3))
+        if not (np.isfinite(sp).all() and (sp > 0).all()):
+            raise ValueError(f"spacing must be three positive finite numbers (dz, dy, dx), got {spacing!r}")
+        offsets = np.zeros(F + 1, np.int32)
+        np.cumsum(np.asarray(counts, np.int32), out=offsets[1:])
+        out = self.new_output(int(offsets[-1]), 19)
+        if int(offsets[-1]) == 0:
+            return out  # stacks without any object: an empty block
+        with self.timed("sizeshape3d"):
+            _lib.check(self.lib.aliby_features_sizeshape3d(self.ctx.handle, _ptr(volume.contiguous()), F, Z, Y, X, _ptr(offsets), _ptr(sp), _ptr(out),
+                                                           out.stride(0), 0, _stream_ptr()))
+        return out
+
     def relabel_sequential(self, labels: torch.Tensor) -> np.ndarray:
         F, Y, X = labels.shape
         n = np.zeros(F, np.int32)

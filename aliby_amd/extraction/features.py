@@ -175,3 +175,12 @@ def intensity3d_names() -> list[str]:
     return ["Volume", "Intensity_IntegratedIntensity", "Intensity_MeanIntensity", "Intensity_StdIntensity", "Intensity_MinIntensity",
             "Intensity_MaxIntensity", "Location_CenterMassIntensity_X", "Location_CenterMassIntensity_Y", "Location_CenterMassIntensity_Z",
             "Location_Center_X", "Location_Center_Y", "Location_Center_Z"]
+
+
+def sizeshape3d_names() -> list[str]:
+    """Size and shape of volume labels (csrc/feat_sizeshape3d.hip), named after CellProfiler's 3-D MeasureObjectSizeShape (the
+    names cp_measure's `sizeshape` uses for 3-D input; parity with it is unpinned, like intensity3d).  SurfaceArea and Solidity
+    are deliberately absent."""
+    return ["Volume", "BoundingBoxMinimum_X", "BoundingBoxMinimum_Y", "BoundingBoxMinimum_Z", "BoundingBoxMaximum_X", "BoundingBoxMaximum_Y",
+            "BoundingBoxMaximum_Z", "BoundingBoxVolume", "Center_X", "Center_Y", "Center_Z", "Extent", "EquivalentDiameter", "EulerNumber",
+            "MajorAxisLength", "MinorAxisLength", "InertiaTensorEigenvalues_0", "InertiaTensorEigenvalues_1", "InertiaTensorEigenvalues_2"]

@@ -534,6 +534,16 @@ int aliby_labels_apply_lut(aliby_ctx* ctx, const uint16_t* labels_in, int T, int
  * Center_X/Y/Z.  Exact integer sums: run-to-run deterministic. */
 int aliby_features_intensity3d(aliby_ctx* ctx, const uint16_t* labels, const uint16_t* pixels, int F, int C, int Z, int Y,
                                int X, int channel, const int32_t* offsets_host, double* out, int ld, int col0, void* stream);
+/* Per-object size and shape over the same labelled stacks (uint16 [F,Z,Y,X], object (f, label) = row offsets_host[f] + label - 1).
+ * 19 columns at out[row * ld + col0 ..]: Volume, BoundingBoxMinimum_X/Y/Z, BoundingBoxMaximum_X/Y/Z (exclusive),
+ * BoundingBoxVolume, Center_X/Y/Z (voxel indices: bit-identical to intensity3d's), Extent, EquivalentDiameter, EulerNumber
+ * (of the union of the object's closed voxel cubes, i.e. 26-connected foreground), MajorAxisLength, MinorAxisLength
+ * (sqrt(20 c), c the extreme eigenvalues of the population covariance of the coordinates scaled by spacing),
+ * InertiaTensorEigenvalues_0/1/2 (of tr(C) Id - C, descending).  spacing = host double[3] (dz, dy, dx), positive; it scales
+ * Volume, BoundingBoxVolume, EquivalentDiameter, the axis lengths and the inertia eigenvalues.  A label of 1..n_f without
+ * voxels gets Volume 0 and NaN elsewhere.  Exact integer sums: run-to-run deterministic and independent of the batch. */
+int aliby_features_sizeshape3d(aliby_ctx* ctx, const uint16_t* labels, int F, int Z, int Y, int X, const int32_t* offsets_host,
+                               const double* spacing, double* out, int ld, int col0, void* stream);
 
 /* ---- a17: the step API's files, encoded natively (host code, no GPU work) ------------------ */
 /* profiles/<name>.parquet — pyarrow.parquet.write_table(profiles, path, compression="zstd")

@@ -1,0 +1,85 @@
+"""
+Cost of the two volume feature families on a BASELINE config-5 stack (uint16 labels [32, 512, 512], the synthetic ground-truth
+ellipsoids relabelled 1..n; pixels of channel 0): `FeatureEngine.intensity3d` (4 bytes per voxel: labels + pixels) and
+`FeatureEngine.sizeshape3d` (2 bytes per voxel, 2.57 with the low-side halo of its 8 x 8 x 64 tiles), one stack and a batch of 8.
+Times are the engine's own `timed(...)` events around each call (memsets, offsets upload, accumulation and finalise kernels), the
+two families alternating, warm-up calls discarded; prints one JSON line.  The 16.8 MB of labels of one stack stay resident in
+the 256 MB Infinity Cache between repeats, so the "fraction of HBM peak" of F = 1 is a rate against the HBM figure, not proof of
+HBM traffic; the batch of 8 (134 MB labels + 134 MB pixels) does not fit for intensity3d.
+Run it under `rocprofv3 --kernel-trace --stats -- python scripts/profile_features3d.py` for the per-kernel times.
+"""
+
+from __future__ import annotations
+
+import json
+import statistics
+import sys
+from pathlib import Path
+
+import numpy as np
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+
+from aliby_amd import synth  # noqa: E402
+from aliby_amd.extraction.engine import FeatureEngine  # noqa: E402
+
+HBM_PEAK = 8.0e12  # bytes / s, MI355X specification
+TILE = (8, 8, 64)
+
+
+def staged_bytes(F, Z, Y, X):
+    """What sizeshape3d's workgroups read: every tile of the corner grid with its one-voxel low-side halo, clipped to the volume."""
+    per_axis = []
+    for n, t in zip((Z, Y, X), TILE):
+        reads = 0
+        for k in range(n // t + 1):
+            lo, hi = max(k * t - 1, 0), min(k * t + t, n)
+            reads += max(hi - lo, 0)
+        per_axis.append(reads)
+    return 2 * F * per_axis[0] * per_axis[1] * per_axis[2]
+
+
+def main(warmup=3, reps=20):
+    torch.cuda.set_device(0)
+    f = synth.make_fov(5, 0)
+    gt = synth.ellipsoid_planes(f["nuclei"], f["pixels"].shape[1], seed=0)
+    present = np.unique(gt[gt > 0])
+    lut = np.zeros(int(gt.max()) + 1, np.uint16)
+    lut[present] = np.arange(1, len(present) + 1)
+    labels = torch.from_numpy(lut[gt]).cuda()              # [32, 512, 512]
+    pixels = torch.from_numpy(f["pixels"][:1]).cuda()      # [1, 32, 512, 512]
+    eng = FeatureEngine(0)
+    res = {"shape": list(labels.shape), "objects": int(len(present)), "foreground_fraction": round(float((gt > 0).mean()), 4),
+           "hbm_peak_bytes_per_s": HBM_PEAK, "warmup": warmup, "reps": reps}
+    for F in (1, 8):
+        vol = labels[None].expand(F, -1, -1, -1).contiguous()
+        px = pixels[None].expand(F, -1, -1, -1, -1).contiguous()
+        counts = [int(len(present))] * F
+        eng.profile = {}
+        for _ in range(warmup):
+            eng.intensity3d(vol, px, 0, counts)
+            eng.sizeshape3d(vol, counts)
+        torch.cuda.synchronize()
+        eng.profile = {}
+        for _ in range(reps):
+            eng.intensity3d(vol, px, 0, counts)
+            eng.sizeshape3d(vol, counts)
+        torch.cuda.synchronize()
+        ms = {k: [a.elapsed_time(b) for a, b in v] for k, v in eng.profile.items()}
+        eng.profile = None
+        voxels = vol.numel()
+        moved = {"intensity3d": 4 * voxels, "sizeshape3d": 2 * voxels}
+        out = {}
+        for name in ("intensity3d", "sizeshape3d"):
+            med, best = statistics.median(ms[name]), min(ms[name])
+            out[name] = dict(ms_median=round(med, 4), ms_min=round(best, 4), ms_max=round(max(ms[name]), 4), bytes_algorithmic=moved[name],
+                             fraction_of_hbm_peak=round(moved[name] / (med * 1e-3) / HBM_PEAK, 4))
+        out["sizeshape3d"]["bytes_staged_with_halo"] = staged_bytes(F, *labels.shape)
+        out["sizeshape3d_over_intensity3d"] = round(out["sizeshape3d"]["ms_median"] / out["intensity3d"]["ms_median"], 3)
+        res[f"F{F}"] = out
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
