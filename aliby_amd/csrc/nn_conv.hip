@@ -272,13 +272,9 @@ struct ConvCfg {
   static constexpr int LDS_BYTES = NPL * PLANE * 16;
   static constexpr int PIX_PER_IT = 256 / NPL;
   static constexpr int ITERS = (RAW + PIX_PER_IT - 1) / PIX_PER_IT;  // staging loads per thread and tile
-#ifndef C3_B32T
-#define C3_B32T 1  // diagnostics: batches of the 32-channel TALL window
-#endif
-#ifndef C3_B64T
-#define C3_B64T 4  // batches of the 64 -> 64 TALL window (20 loads per thread; measured 2 / 3 / 4 batches: 394 / 320 / 294 us per 288-tile
-                   // launch — ten or seven loads at once spill the resident weights)
-#endif
+  static constexpr int C3_B32T = 1;  // batches of the 32-channel TALL window
+  static constexpr int C3_B64T = 4;  // batches of the 64 -> 64 TALL window (20 loads per thread; measured 2 / 3 / 4 batches: 394 / 320 / 294 us per
+                                     // 288-tile launch — ten or seven loads at once spill the resident weights)
   static constexpr int NBATCH = (PACK && COUT >= 128) ? 3 : (CIN >= 64 ? ((TALL && COUT == 64) ? C3_B64T : 2) : (TALL ? C3_B32T : 1));
   static constexpr int BATCH = (ITERS + NBATCH - 1) / NBATCH;  // staging loads in flight per thread
   static constexpr int DEPTH = (CIN >= 64 && COUT >= 64) ? 4 : 6;  // pixel fragments in flight LDS -> VGPR ahead of their MFMAs
@@ -300,9 +296,6 @@ struct ConvCfg {
 // NHWC -> NCHW float32, from the accumulators: a lane holds 16 of a pixel's 32 channels, its partner (lane ^ 32) the other
 // 16.  Products are summed octet by octet, then octet pairs, then the two halves: the order of k_out_head, so both paths give
 // the same bits.  OUT may be NULL then (nothing else reads the last unit's output: 0.9 GB per forward not written, not re-read).
-#ifndef C3_HACK
-#define C3_HACK 0  // diagnostics (scripts/phase_builds.sh): compile-time phase switches of this kernel, timing only
-#endif
 template <int CIN, int COUT, bool UP, bool POOL, int PK, bool TALL, bool PACK = false, bool HEAD = false>
 __global__ __launch_bounds__(256, 2) void k_conv3x3(ConvArgs a) {
   static_assert(!PACK || (!UP && PK == 0), "packed launches: plain input, no fused projection");
@@ -323,9 +316,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(ConvArgs a) {
   {
     const bf16x8_t* wp = reinterpret_cast<const bf16x8_t*>(a.wpk) + (size_t)cb * 9 * KC * 64 + lane;
 #pragma unroll
-    for (int i = 0; i < 9 * KC; ++i) {
-      if constexpr (C3_HACK & 256) { wfrag[i] = bf16x8_t{}; wfrag[i][0] = (__bf16)(float)(i + lane); } else wfrag[i] = wp[i * 64];
-    }
+    for (int i = 0; i < 9 * KC; ++i) wfrag[i] = wp[i * 64];
   }
   bf16x8_t pfrag[PK > 0 ? PK : 1];
   if constexpr (PK > 0) {
@@ -397,9 +388,9 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(ConvArgs a) {
     // (pass 0 before the prologue, pass p+1 while pass p is on the matrix cores: one pass worth of registers)
     uint4 rr[R][2];
     auto load_res = [&](int pass) { conv_load_res<R>(a, nimg, irow, y0 + (rg * PASSES + pass) * R, gx, c0, rr); };
-    if (a.res && !(C3_HACK & 2)) load_res(0);
+    if (a.res) load_res(0);
     CONV_STAMP(1);
-    if constexpr (!(C3_HACK & 128)) __syncthreads();  // every wave is done reading the previous tile's planes
+    __syncthreads();  // every wave is done reading the previous tile's planes
     CONV_STAMP(2);
     // ---- stage the raw window: BATCH 16-byte loads per thread in flight at once (unconditional, from clamped
     // addresses: no divergent branch around a load), then the prologue (BatchNorm affine + style shift + ReLU,
@@ -430,14 +421,12 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(ConvArgs a) {
           const int img = (snd && ok) ? g0 + 1 : g0;
           inside |= (unsigned)ok << u;
           later |= (unsigned)snd << u;
-          if constexpr (C3_HACK & 1) v[u] = make_uint4(cy, c, img, 3);
-          else v[u] = inN[(unsigned)(((img * a.H + cy) * IW + min(max(c, 0), a.W - 1)) * a.cs + pl)];
+          v[u] = inN[(unsigned)(((img * a.H + cy) * IW + min(max(c, 0), a.W - 1)) * a.cs + pl)];
         } else {
           const int gxi = x0 - 1 + lx;
           inside |= (unsigned)((unsigned)gy < (unsigned)a.H && (unsigned)gxi < (unsigned)a.W) << u;
           const int cx = min(max(gxi, 0), a.W - 1);
-          if constexpr (C3_HACK & 1) v[u] = make_uint4(cy, cx, 2, 3);
-          else v[u] = inN[(unsigned)(((UP ? cy >> 1 : cy) * IW + (UP ? cx >> 1 : cx)) * a.cs + pl)];
+          v[u] = inN[(unsigned)(((UP ? cy >> 1 : cy) * IW + (UP ? cx >> 1 : cx)) * a.cs + pl)];
         }
       }
 #pragma unroll
@@ -450,11 +439,10 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(ConvArgs a) {
           for (int k = 0; k < 4; ++k) shs[k] = ((later >> u) & 1u) ? sh1[k] : sh[k];
           o = conv_act8(v[u], sc, shs, 0u - ((inside >> u) & 1u));
         } else {
-          if constexpr (C3_HACK & 16) o = v[u]; else o = conv_act8(v[u], sc, sh, 0u - ((inside >> u) & 1u));
+          o = conv_act8(v[u], sc, sh, 0u - ((inside >> u) & 1u));
         }
         if (it0 + u == ITERS - 1 && p0 + (it0 + u) * PIX_PER_IT >= RAW) continue;  // only the last round can run past the window
-        if constexpr (C3_HACK & 32) { if (o.x == 0x12345u) lds[pl * PLANE + p0 + (it0 + u) * PIX_PER_IT] = o; }
-        else lds[pl * PLANE + p0 + (it0 + u) * PIX_PER_IT] = o;
+        lds[pl * PLANE + p0 + (it0 + u) * PIX_PER_IT] = o;
       }
     }
     if constexpr (PK > 0) {  // the projection's raw input tile: TH x TW pixels, 2*PK channel octets, no halo
@@ -472,7 +460,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(ConvArgs a) {
       }
     }
     CONV_STAMP(3);
-    if constexpr (!(C3_HACK & 128)) __syncthreads();
+    __syncthreads();
     CONV_STAMP(4);
 
 #pragma unroll
@@ -482,13 +470,12 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(ConvArgs a) {
       {
         float4 b4[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) b4[q] = (C3_HACK & 64) ? make_float4(0.f, 0.f, 0.f, 0.f) : sbias[(c0 >> 2) + q];
-        conv_seed<R>(acc, b4, rr, a.res != nullptr && !(C3_HACK & 2));
+        for (int q = 0; q < 4; ++q) b4[q] = float4(sbias[(c0 >> 2) + q]);  // (through a temporary: the plain assignment schedules these reads differently)
+        conv_seed<R>(acc, b4, rr, a.res != nullptr);
       }
       __builtin_amdgcn_sched_barrier(0);
-      if (pass + 1 < PASSES && a.res && !(C3_HACK & 2)) load_res(pass + 1);
+      if (pass + 1 < PASSES && a.res) load_res(pass + 1);
       __builtin_amdgcn_sched_barrier(0);
-      if constexpr (!(C3_HACK & 8))
       conv_mfma<R, KC, (POOL ? cfg::DEPTH_POOL : cfg::DEPTH), PLANE, LW>(
           reinterpret_cast<const bf16x8_t*>(lds) + hh * PLANE + rbase * LW + px + second, wfrag, acc);
       if constexpr (PK > 0) {
@@ -513,7 +500,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(ConvArgs a) {
           }
         }
       }
-      if ((!HEAD || a.out) && (!(C3_HACK & 4) || acc[0][3] == 12345.f)) conv_store<R>(a, nimg, irow, y0 + rbase, gx, c0, acc);
+      if (!HEAD || a.out) conv_store<R>(a, nimg, irow, y0 + rbase, gx, c0, acc);
       // ---- the next level's input, max_pool2d(OUT, 2, 2), straight from the accumulators: row pairs are in this
       // wave's registers, column pairs are neighbouring lanes (max commutes with the bf16 rounding)
       if constexpr (POOL) {
@@ -677,7 +664,7 @@ __global__ __launch_bounds__(256, (DmaCfg<CIN, COUT, UP, PACK>::WAVES_PER_SIMD))
     }
     uint4 rr[R][2];
     auto load_res = [&](int pass) { conv_load_res<R>(a, nimg, irow, y0 + (rg * PASSES + pass) * R, gx, c0, rr); };
-    if (a.res && !(C3_HACK & 2)) load_res(0);
+    if (a.res) load_res(0);
     CONV_STAMP(1);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's share of the window has landed in R
     __syncthreads();                                   // ... and everyone's; the previous tile's reads of A are over
@@ -766,9 +753,6 @@ struct PairCfg {
   static constexpr int DEPTH = 6;
 };
 
-#ifndef CP_HACK
-#define CP_HACK 0  // diagnostics (scripts/phase_builds.sh): compile-time phase switches of the pair kernel, timing only
-#endif
 template <bool POOL, bool HEAD>
 __global__ __launch_bounds__(512, 1) void k_conv_pair32(ConvArgs a) {
   static_assert(!(POOL && HEAD), "either the pooled output (down block) or the output head (last unit)");
@@ -821,7 +805,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_pair32(ConvArgs a) {
         const int gy = y0 - 2 + ly, gxi = x0 - 2 + lx;
         inside |= (unsigned)((unsigned)gy < (unsigned)a.H && (unsigned)gxi < (unsigned)a.W) << u;
         const int cy = min(max(gy, 0), a.H - 1), cx = min(max(gxi, 0), a.W - 1);
-        if constexpr (CP_HACK & 1) v[u] = make_uint4(u, 1, 2, 3); else v[u] = inN[(unsigned)((cy * a.W + cx) * a.cs + pl)];
+        v[u] = inN[(unsigned)((cy * a.W + cx) * a.cs + pl)];
       }
     };
     if (my_tiles > 0) request(t_begin);
@@ -845,7 +829,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_pair32(ConvArgs a) {
       for (int u = 0; u < ITERS; ++u) {
         const uint4 o = conv_act8(v[u], sc, sh, 0u - ((inside >> u) & 1u));
         if (u == ITERS - 1 && pix0 + u * PIX_PER_IT >= RAW_IN) continue;
-        if constexpr (!(CP_HACK & 64)) ldsIn[pl * PLANE_IN + pix0 + u * PIX_PER_IT] = o;
+        ldsIn[pl * PLANE_IN + pix0 + u * PIX_PER_IT] = o;
       }
       __syncthreads();  // S1: the window is complete
       if (it + 1 < my_tiles) request(tile + nslots);
@@ -867,7 +851,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_pair32(ConvArgs a) {
             for (int q = 0; q < 4; ++q) { acc[r][4 * q] = b4[q].x; acc[r][4 * q + 1] = b4[q].y; acc[r][4 * q + 2] = b4[q].z; acc[r][4 * q + 3] = b4[q].w; }
         }
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (!(CP_HACK & 8)) conv_mfma<R, KC, cfg::DEPTH, PLANE_IN, IW_>(reinterpret_cast<const bf16x8_t*>(ldsIn) + hh * PLANE_IN + mbase * IW_ + px, wA, acc);
+        conv_mfma<R, KC, cfg::DEPTH, PLANE_IN, IW_>(reinterpret_cast<const bf16x8_t*>(ldsIn) + hh * PLANE_IN + mbase * IW_ + px, wA, acc);
         __builtin_amdgcn_sched_barrier(0);
         // bf16 as the two-launch path stores it, then B's prologue; zero where the intermediate pixel lies outside the image
         const int mgx = x0 - 1 + px;
@@ -884,7 +868,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_pair32(ConvArgs a) {
             h2[0] = f32x2_t{ha.x, ha.y}; h2[1] = f32x2_t{ha.z, ha.w}; h2[2] = f32x2_t{hb.x, hb.y}; h2[3] = f32x2_t{hb.z, hb.w};
             const uint4 raw = make_uint4(cv_pack2(acc[r][8 * half + 0], acc[r][8 * half + 1]), cv_pack2(acc[r][8 * half + 2], acc[r][8 * half + 3]),
                                          cv_pack2(acc[r][8 * half + 4], acc[r][8 * half + 5]), cv_pack2(acc[r][8 * half + 6], acc[r][8 * half + 7]));
-            if constexpr (!(CP_HACK & 32)) ldsMid[(2 * hh + half) * PLANE_MID + (mbase + r) * MW + px] = conv_act8(raw, s2, h2, keep);
+            ldsMid[(2 * hh + half) * PLANE_MID + (mbase + r) * MW + px] = conv_act8(raw, s2, h2, keep);
           }
         }
       }
@@ -931,11 +915,11 @@ __global__ __launch_bounds__(512, 1) void k_conv_pair32(ConvArgs a) {
         const int rbase = (wave * PASSES + pass) * R;
         if (rbase < TH) {  // (the last wave's second pass has no rows)
           uint4 rr[R][2];
-          if (a.res && !(CP_HACK & 2)) conv_load_res<R>(a, n, 0, y0 + rbase, min(gx, a.W - 1), c0, rr);
+          if (a.res) conv_load_res<R>(a, n, 0, y0 + rbase, min(gx, a.W - 1), c0, rr);
           f32x16_t acc[R];
-          conv_seed<R>(acc, b4, rr, a.res != nullptr && !(CP_HACK & 2));
+          conv_seed<R>(acc, b4, rr, a.res != nullptr);
           __builtin_amdgcn_sched_barrier(0);
-          if constexpr (!(CP_HACK & 16)) conv_mfma<R, KC, cfg::DEPTH, PLANE_MID, MW>(reinterpret_cast<const bf16x8_t*>(ldsMid) + hh * PLANE_MID + rbase * MW + px, wB, acc);
+          conv_mfma<R, KC, cfg::DEPTH, PLANE_MID, MW>(reinterpret_cast<const bf16x8_t*>(ldsMid) + hh * PLANE_MID + rbase * MW + px, wB, acc);
           if constexpr (HEAD) {  // the output head from the accumulators (head_apply: the same bits as k_out_head)
 #pragma unroll
             for (int r = 0; r < R; ++r) {
@@ -948,7 +932,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_pair32(ConvArgs a) {
               }
             }
           }
-          if ((!HEAD || a.out) && (!(CP_HACK & 4) || acc[0][3] == 12345.f)) conv_store<R>(a, n, 0, y0 + rbase, gx, c0, acc);
+          if (!HEAD || a.out) conv_store<R>(a, n, 0, y0 + rbase, gx, c0, acc);
           if constexpr (POOL) {
             const int PH = a.H >> 1, PW = a.W >> 1;
             const int gy = y0 + rbase;
@@ -963,7 +947,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_pair32(ConvArgs a) {
                 const float v1 = fmaxf(acc[0][half * 8 + 2 * q + 1], acc[1][half * 8 + 2 * q + 1]);
                 pk[q] = cv_pack2(fmaxf(v0, __shfl_xor(v0, 1)), fmaxf(v1, __shfl_xor(v1, 1)));
               }
-              if (writer && (!(CP_HACK & 4) || acc[0][3] == 12345.f)) pp[half] = make_uint4(pk[0], pk[1], pk[2], pk[3]);
+              if (writer) pp[half] = make_uint4(pk[0], pk[1], pk[2], pk[3]);
             }
           }
         }

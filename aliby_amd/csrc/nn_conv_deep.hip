@@ -24,12 +24,6 @@
 //     through a 3-deep ring, seven MFMAs of cover each;
 //   * two workgroups per CU (<= 256 VGPRs, 44 KiB of LDS each) overlap each other's staging and MFMA phases.
 #include "common.h"
-#ifndef DC_REQ_AT
-#define DC_REQ_AT 27  // weight fragment (of 36 per slice) before which the next slice's window is requested
-#endif
-#ifndef DC_HACK
-#define DC_HACK 0  // diagnostics (scripts/deep_phases.sh): compile-time phase switches, timing only, results wrong
-#endif
 #include <stdlib.h>
 #include <utility>
 
@@ -102,14 +96,118 @@ constexpr int DC_PLANE = DC_WIN_MAX | 1;       // odd slot pitch: the 8 octets o
 constexpr int DC_ITERS = (DC_WIN_MAX + 31) / 32;  // staging rounds: 32 positions x 8 octets per round of 256 threads
 // planes + per-thread input offsets + prologue constants + per-thread output / residual offsets
 constexpr int DC_LDS_BYTES = 8 * DC_PLANE * 16 + DC_ITERS * 256 * 4 + 3 * 256 * 4 + 2 * DC_NB * 256 * 4;
-#ifndef DC_WDEPTH_
-#define DC_WDEPTH_ 3
-#endif
-#ifndef DC_PDEPTH_
-#define DC_PDEPTH_ 4
-#endif
-constexpr int DC_WDEPTH = DC_WDEPTH_;  // weight fragments in flight
-constexpr int DC_PDEPTH = DC_PDEPTH_;  // pixel fragments in flight
+constexpr int DC_WDEPTH = 3;  // weight fragments in flight
+constexpr int DC_PDEPTH = 4;  // pixel fragments in flight
+constexpr int DC_REQ_AT = 27;  // weight fragment (of 36 per slice) before which the next slice's window is requested
+
+// ---- the stages that the three kernels of this file share (they differ in their K loops)
+// 32 positions further in the tall image: column c, row y of image n
+__device__ __forceinline__ void dc_step32(int& c, int& y, int& n, int LW, int HP) {
+  c += 32;
+  while (c >= LW) {  // (at most two wraps: LW >= 30 at the levels these kernels serve)
+    c -= LW;
+    if (++y == HP) { y = 0; ++n; }
+  }
+}
+// window position P (flat index, >= -1) -> column, row, image (y < 0: rows above the first image)
+__device__ __forceinline__ void dc_win_pos(int P, int LW, int HP, int& c, int& y, int& n) {
+  const int r = P >= 0 ? P / LW : -1;
+  c = P - r * LW;
+  n = r >= 1 ? (r - 1) / HP : 0;
+  y = r >= 1 ? (r - 1) - n * HP : r - 1;
+}
+// output position q -> column, row, image (its row is >= 1 always: q >= q_begin = LW)
+__device__ __forceinline__ void dc_out_pos(int q, int LW, int HP, int& c, int& y, int& n) {
+  const int r = q / LW;
+  c = q - r * LW;
+  n = (r - 1) / HP;
+  y = (r - 1) - n * HP;
+}
+// input offset (16-byte units) of channel octet `oct` at window position (c, y, n), clamped to a valid address.  Bit `bit` of
+// `inside`: the position is a pixel (and `valid`); of `later`: it belongs to an image after the window's first one, n0
+template <bool UP>
+__device__ __forceinline__ int dc_win_off(const DeepArgs& a, int c, int y, int n, int n0, int cs, int oct, bool valid, int bit,
+                                          unsigned& inside, unsigned& later) {
+  const int IH = UP ? a.H >> 1 : a.H, IW = UP ? a.W >> 1 : a.W;
+  const bool ok = valid && y >= 0 && y < a.H && c >= 1 && c <= a.W && n < a.N;
+  inside |= (unsigned)ok << bit;
+  later |= (unsigned)(n > n0) << bit;
+  const int nn = min(n, a.N - 1), yy = min(max(y, 0), a.H - 1), xx = min(max(c - 1, 0), a.W - 1);
+  return ((nn * IH + (UP ? yy >> 1 : yy)) * IW + (UP ? xx >> 1 : xx)) * cs + oct;
+}
+// prologue constants of K slice s for one channel octet: scale, and the style shifts of images n0 and n1
+__device__ __forceinline__ void dc_prologue_consts(const DeepArgs& a, int s, int oct, int n0, int n1, f32x2_t (&sc)[4], f32x2_t (&sh)[4],
+                                                   f32x2_t (&sh1)[4]) {
+  const int ch = s * 64 + oct * 8;
+  const float* sp0 = a.shift + (size_t)n0 * a.shift_stride + ch;
+  const float* sp1 = a.shift + (size_t)n1 * a.shift_stride + ch;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    sc[k] = f32x2_t{a.scale[ch + 2 * k], a.scale[ch + 2 * k + 1]};
+    sh[k] = f32x2_t{sp0[2 * k], sp0[2 * k + 1]};
+    sh1[k] = f32x2_t{sp1[2 * k], sp1[2 * k + 1]};
+  }
+}
+// residual offset (16-byte units) of output channel c0 at (n, y, x); clamped: positions that are not stored (zero row / columns,
+// past the last image) read some valid address
+__device__ __forceinline__ unsigned dc_res_off(const DeepArgs& a, int n, int y, int x, int ocs, int c0) {
+  const int RH = a.H >> a.res_up, RW = a.W >> a.res_up;
+  const int nn = min(n, a.N - 1), yy = min(y, a.H - 1), xx = min(max(x, 0), a.W - 1);
+  return (unsigned)(((nn * RH + (yy >> a.res_up)) * RW + (xx >> a.res_up)) * ocs + (c0 >> 3));
+}
+// 32x32x16 layout (a lane holds channels c0 .. c0 + 15 of positions q0 + px + 32 b).  The accumulators start at bias + residual
+// (as in nn_conv.hip): the residual's loads are in flight together with the first window's, behind the first staging phase,
+// instead of twice exposed in the epilogue, which is then convert + store
+__device__ __forceinline__ void dc_seed32(const DeepArgs& a, int q0, int px, int c0, int ocs, int LW, int HP, f32x16_t (&acc)[DC_NB]) {
+  float b16[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) b16[k] = a.bias ? a.bias[c0 + k] : 0.f;
+  if (a.res) {
+    uint4 rr[DC_NB][2];
+    int c, y, n;
+    dc_out_pos(q0 + px, LW, HP, c, y, n);
+#pragma unroll
+    for (int b = 0; b < DC_NB; ++b) {
+      const unsigned roff = dc_res_off(a, n, y, c - 1, ocs, c0);
+      rr[b][0] = a.res[roff];
+      rr[b][1] = a.res[roff + 1];
+      dc_step32(c, y, n, LW, HP);
+    }
+#pragma unroll
+    for (int b = 0; b < DC_NB; ++b) {
+      const unsigned rw[8] = {rr[b][0].x, rr[b][0].y, rr[b][0].z, rr[b][0].w, rr[b][1].x, rr[b][1].y, rr[b][1].z, rr[b][1].w};
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        acc[b][2 * j] = b16[2 * j] + dc_bf2f(rw[j] & 0xffffu);
+        acc[b][2 * j + 1] = b16[2 * j + 1] + dc_bf2f(rw[j] >> 16);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int b = 0; b < DC_NB; ++b)
+#pragma unroll
+      for (int k = 0; k < 16; ++k) acc[b][k] = b16[k];
+  }
+}
+// ... and the epilogue: fp32 -> bf16, 32 contiguous bytes per lane and position.  Positions by stepping (no divisions)
+__device__ __forceinline__ void dc_store32(const DeepArgs& a, int q0, int px, int c0, int ocs, int LW, int HP,
+                                           const f32x16_t (&acc)[DC_NB]) {
+  int c, y, n;
+  dc_out_pos(q0 + px, LW, HP, c, y, n);
+#pragma unroll
+  for (int b = 0; b < DC_NB; ++b) {
+    const int x = c - 1;
+    const bool ok = q0 + b * 32 + px < a.q_end && y < a.H && x >= 0 && x < a.W && n < a.N;
+    if (ok) {
+      uint4* op = a.out + (unsigned)(((n * a.H + y) * a.W + x) * ocs + (c0 >> 3));
+      op[0] = make_uint4(dc_pack2(acc[b][0], acc[b][1]), dc_pack2(acc[b][2], acc[b][3]), dc_pack2(acc[b][4], acc[b][5]),
+                         dc_pack2(acc[b][6], acc[b][7]));
+      op[1] = make_uint4(dc_pack2(acc[b][8], acc[b][9]), dc_pack2(acc[b][10], acc[b][11]), dc_pack2(acc[b][12], acc[b][13]),
+                         dc_pack2(acc[b][14], acc[b][15]));
+    }
+    dc_step32(c, y, n, LW, HP);
+  }
+}
 
 template <int CIN, bool UP>
 __global__ __launch_bounds__(256, 2) void k_conv3x3_deep(DeepArgs a) {
@@ -118,7 +216,6 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep(DeepArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, cb = tid >> 6;
   const int px = lane & 31, hh = lane >> 5;
   const int pl = tid & 7, pos0 = tid >> 3;  // staging role: a fixed channel octet of position pos0 + 32 * round
-  const int IH = UP ? a.H >> 1 : a.H, IW = UP ? a.W >> 1 : a.W;
   const int LW = a.LW, HP = a.HP;
   const int WIN = DC_RUN + 2 * LW + 2;
   const int cs = CIN / 8;
@@ -141,21 +238,12 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep(DeepArgs a) {
     unsigned inside = 0, later = 0;
     const int n0 = max(0, ((p_first / LW) - 1) / HP);  // image of the window's first row (clamped)
     {
-      const int P0 = p_first + pos0;  // >= -1
-      int r = P0 >= 0 ? P0 / LW : -1, c = P0 - r * LW;
-      int n = r >= 1 ? (r - 1) / HP : 0, y = r >= 1 ? (r - 1) - n * HP : r - 1;  // (y < 0: rows above the first image)
+      int c, y, n;
+      dc_win_pos(p_first + pos0, LW, HP, c, y, n);
 #pragma unroll
       for (int it = 0; it < DC_ITERS; ++it) {
-        const bool ok = y >= 0 && y < a.H && c >= 1 && c <= a.W && n < a.N;
-        inside |= (unsigned)ok << it;
-        later |= (unsigned)(n > n0) << it;
-        const int nn = min(n, a.N - 1), yy = min(max(y, 0), a.H - 1), xx = min(max(c - 1, 0), a.W - 1);
-        goff[it * 256] = ((nn * IH + (UP ? yy >> 1 : yy)) * IW + (UP ? xx >> 1 : xx)) * cs + pl;
-        c += 32;
-        while (c >= LW) {  // (at most two wraps: LW >= 30 at the levels this kernel serves)
-          c -= LW;
-          if (++y == HP) { y = 0; ++n; }
-        }
+        goff[it * 256] = dc_win_off<UP>(a, c, y, n, n0, cs, pl, true, it, inside, later);
+        dc_step32(c, y, n, LW, HP);
       }
     }
     const int n1 = min(n0 + 1, a.N - 1);
@@ -165,56 +253,14 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep(DeepArgs a) {
     auto request = [&](int s) {
       const uint4* inS = a.in + s * 8;
 #pragma unroll
-      for (int it = 0; it < DC_ITERS; ++it) { if constexpr (!(DC_HACK & 32)) v[it] = inS[(unsigned)goff[it * 256]]; else v[it] = make_uint4(it, 1, 2, 3); }
+      for (int it = 0; it < DC_ITERS; ++it) v[it] = inS[(unsigned)goff[it * 256]];
     };
     request(0);
 
-    // ---- accumulators start at bias + residual (as in nn_conv.hip): the residual's loads are in flight together with the first
-    // window's, behind the first staging phase, instead of twice exposed in the epilogue, which is then convert + store
     const int c0 = half * 128 + cb * 32 + hh * 16;
     const int ocs = a.COUT / 8;
     f32x16_t acc[DC_NB];
-    {
-      float b16[16];
-#pragma unroll
-      for (int k = 0; k < 16; ++k) b16[k] = a.bias ? a.bias[c0 + k] : 0.f;
-      if (a.res && !(DC_HACK & 64)) {
-        const int RH = a.H >> a.res_up, RW = a.W >> a.res_up;
-        uint4 rr[DC_NB][2];
-        {
-          const int q = q0 + px;
-          int r = q / LW, c = q - r * LW;
-          int n = (r - 1) / HP, y = (r - 1) - n * HP;  // r >= 1 always: q >= q_begin = LW
-#pragma unroll
-          for (int b = 0; b < DC_NB; ++b) {
-            // clamped: positions that are not stored (zero row / columns, past the last image) read some valid address
-            const int nn = min(n, a.N - 1), yy = min(y, a.H - 1), xx = min(max(c - 1, 0), a.W - 1);
-            const unsigned roff = (unsigned)(((nn * RH + (yy >> a.res_up)) * RW + (xx >> a.res_up)) * ocs + (c0 >> 3));
-            rr[b][0] = a.res[roff];
-            rr[b][1] = a.res[roff + 1];
-            c += 32;
-            while (c >= LW) {
-              c -= LW;
-              if (++y == HP) { y = 0; ++n; }
-            }
-          }
-        }
-#pragma unroll
-        for (int b = 0; b < DC_NB; ++b) {
-          const unsigned rw[8] = {rr[b][0].x, rr[b][0].y, rr[b][0].z, rr[b][0].w, rr[b][1].x, rr[b][1].y, rr[b][1].z, rr[b][1].w};
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            acc[b][2 * j] = b16[2 * j] + dc_bf2f(rw[j] & 0xffffu);
-            acc[b][2 * j + 1] = b16[2 * j + 1] + dc_bf2f(rw[j] >> 16);
-          }
-        }
-      } else {
-#pragma unroll
-        for (int b = 0; b < DC_NB; ++b)
-#pragma unroll
-          for (int k = 0; k < 16; ++k) acc[b][k] = b16[k];
-      }
-    }
+    dc_seed32(a, q0, px, c0, ocs, LW, HP, acc);
     const bf16x8_t* wbase = reinterpret_cast<const bf16x8_t*>(a.wpk) + (size_t)(half * 4 + cb) * 9 * KCT * 64 + lane;
     DC_STAMP(1);
 
@@ -224,22 +270,11 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep(DeepArgs a) {
       const bf16x8_t* wp = wbase + (size_t)(4 * s) * 64;  // fragment (tap, kc) of this slice at wp[(tap * KCT + kc) * 64]
       constexpr int NW = 36;  // weight fragments per slice, in (kc, tap) order
       bf16x8_t wring[DC_WDEPTH];
-      auto wfrag = [&](int i) { if constexpr (DC_HACK & 2) return wp[0]; else return wp[((i % 9) * KCT + (i / 9)) * 64]; };
+      auto wfrag = [&](int i) { return wp[((i % 9) * KCT + (i / 9)) * 64]; };
 #pragma unroll
       for (int i = 0; i < DC_WDEPTH - 1; ++i) wring[i] = wfrag(i);
-      // the slice's prologue constants for this thread's octet
-      f32x2_t sc[4], sh[4], sh1[4];
-      {
-        const int ch = s * 64 + pl * 8;
-        const float* sp0 = a.shift + (size_t)n0 * a.shift_stride + ch;
-        const float* sp1 = a.shift + (size_t)n1 * a.shift_stride + ch;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          sc[k] = f32x2_t{a.scale[ch + 2 * k], a.scale[ch + 2 * k + 1]};
-          sh[k] = f32x2_t{sp0[2 * k], sp0[2 * k + 1]};
-          sh1[k] = f32x2_t{sp1[2 * k], sp1[2 * k + 1]};
-        }
-      }
+      f32x2_t sc[4], sh[4], sh1[4];  // the slice's prologue constants for this thread's octet
+      dc_prologue_consts(a, s, pl, n0, n1, sc, sh, sh1);
       __syncthreads();  // every wave is done reading the previous slice's planes
       DC_STAMP(2 + 4 * s);
       // ---- stage: prologue (BatchNorm affine + style shift + ReLU, zero outside the image) into the octet planes
@@ -248,7 +283,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep(DeepArgs a) {
         f32x2_t shs[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) shs[k] = ((later >> it) & 1u) ? sh1[k] : sh[k];
-        const uint4 o = (DC_HACK & 8) ? v[it] : dc_act8(v[it], sc, shs, 0u - ((inside >> it) & 1u));
+        const uint4 o = dc_act8(v[it], sc, shs, 0u - ((inside >> it) & 1u));
         const int wp_ = pos0 + 32 * it;
         if (wp_ < WIN) lds[pl * DC_PLANE + wp_] = o;
       }
@@ -263,7 +298,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep(DeepArgs a) {
       bf16x8_t pring[DC_PDEPTH];
       auto pfrag = [&](int f) {
         const int i = f / DC_NB, b = f % DC_NB, kc = i / 9, tap = i % 9;
-        if constexpr (DC_HACK & 4) return L[f & 3]; else return L[2 * kc * DC_PLANE + b * 32 + row_off[tap / 3] + tap % 3];
+        return L[2 * kc * DC_PLANE + b * 32 + row_off[tap / 3] + tap % 3];
       };
 #pragma unroll
       for (int f = 0; f < DC_PDEPTH - 1; ++f) pring[f] = pfrag(f);
@@ -276,21 +311,8 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep(DeepArgs a) {
         if constexpr (i + DC_WDEPTH - 1 < NW) wring[(i + DC_WDEPTH - 1) % DC_WDEPTH] = wfrag(i + DC_WDEPTH - 1);
         sfor<DC_NB>([&](auto bc) {
           constexpr int b = decltype(bc)::value, f = i * DC_NB + b;
-#ifdef DC_HACK_HALF_LDS
-          if constexpr (f % 2 == 0 && f + 2 < NF) pring[(f + 2) % DC_PDEPTH] = pfrag(f + 2);
-          acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wring[i % DC_WDEPTH], pring[(f & ~1) % DC_PDEPTH], acc[b], 0, 0, 0);
-#else
           if constexpr (f + DC_PDEPTH - 1 < NF) pring[(f + DC_PDEPTH - 1) % DC_PDEPTH] = pfrag(f + DC_PDEPTH - 1);
-          if constexpr (DC_HACK & 128) {  // timing only: the same FLOPs and operand reads as two v_mfma_f32_16x16x32_bf16 (the clock the chip holds depends on the shape)
-            typedef float f32x4_t __attribute__((ext_vector_type(4)));
-            f32x4_t q0 = {acc[b][0], acc[b][1], acc[b][2], acc[b][3]}, q1 = {acc[b][4], acc[b][5], acc[b][6], acc[b][7]};
-            q0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wring[i % DC_WDEPTH], pring[f % DC_PDEPTH], q0, 0, 0, 0);
-            q1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wring[i % DC_WDEPTH], pring[f % DC_PDEPTH], q1, 0, 0, 0);
-            acc[b][0] = q0[0]; acc[b][1] = q0[1]; acc[b][2] = q0[2]; acc[b][3] = q0[3];
-            acc[b][4] = q1[0]; acc[b][5] = q1[1]; acc[b][6] = q1[2]; acc[b][7] = q1[3];
-          } else if constexpr (!(DC_HACK & 1)) acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wring[i % DC_WDEPTH], pring[f % DC_PDEPTH], acc[b], 0, 0, 0);
-          else { acc[b][0] += (float)(__builtin_bit_cast(uint4, wring[i % DC_WDEPTH]).x + __builtin_bit_cast(uint4, pring[f % DC_PDEPTH]).x); }
-#endif
+          acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wring[i % DC_WDEPTH], pring[f % DC_PDEPTH], acc[b], 0, 0, 0);
         });
         __builtin_amdgcn_sched_barrier(0);
       });
@@ -299,44 +321,24 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep(DeepArgs a) {
 
     // ---- epilogue: fp32 -> bf16, 32 contiguous bytes per lane and position.  Positions by stepping (no divisions)
     __builtin_amdgcn_sched_barrier(0);  // nothing of the epilogue is hoisted into the MFMA loop (it would spill there)
-    {
-      const int q = q0 + px;
-      int r = q / LW, c = q - r * LW;
-      int n = (r - 1) / HP, y = (r - 1) - n * HP;  // r >= 1 always: q >= q_begin = LW
-#pragma unroll
-      for (int b = 0; b < DC_NB; ++b) {
-        const int x = c - 1;
-        const bool ok = q0 + b * 32 + px < a.q_end && y < a.H && x >= 0 && x < a.W && n < a.N;
-        if (ok && (!(DC_HACK & 16) || acc[b][3] == 12345.f)) {
-          uint4* op = a.out + (unsigned)(((n * a.H + y) * a.W + x) * ocs + (c0 >> 3));
-          op[0] = make_uint4(dc_pack2(acc[b][0], acc[b][1]), dc_pack2(acc[b][2], acc[b][3]), dc_pack2(acc[b][4], acc[b][5]),
-                             dc_pack2(acc[b][6], acc[b][7]));
-          op[1] = make_uint4(dc_pack2(acc[b][8], acc[b][9]), dc_pack2(acc[b][10], acc[b][11]), dc_pack2(acc[b][12], acc[b][13]),
-                             dc_pack2(acc[b][14], acc[b][15]));
-        }
-        c += 32;
-        while (c >= LW) {
-          c -= LW;
-          if (++y == HP) { y = 0; ++n; }
-        }
-      }
-    }
+    dc_store32(a, q0, px, c0, ocs, LW, HP, acc);
     DC_STAMP(2 + 4 * S);
   }
 }
 
-template <int CIN, bool UP>
-int launch_deep(DeepArgs& a, hipStream_t stream) {
+// One launch for the three forms: persistent workgroups, 8 XCDs x at most CAP slots (the kernel's workgroups per CU x 32 CUs per
+// XCD; `cap_env` names an environment variable that overrides it)
+template <auto Kernel, int LDS_BYTES, int CAP, int THREADS>
+int launch(DeepArgs& a, hipStream_t stream, const char* cap_env = nullptr) {
   static bool attr_done = false;
   if (!attr_done) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_deep<CIN, UP>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                DC_LDS_BYTES));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
     attr_done = true;
   }
+  static const int cap = [&] { const char* e = cap_env ? getenv(cap_env) : nullptr; return e ? atoi(e) : CAP; }();
   const int per_xcd = (a.ntiles + 7) / 8;
-  static const int cap = [] { const char* e = getenv("ALIBY_DEEP_SLOTS"); return e ? atoi(e) : 64; }();  // 2 workgroups per CU, 32 CUs per XCD
   const int nslots = per_xcd < cap ? per_xcd : cap;
-  hipLaunchKernelGGL((k_conv3x3_deep<CIN, UP>), dim3(8 * nslots), dim3(256), DC_LDS_BYTES, stream, a);
+  hipLaunchKernelGGL(Kernel, dim3(8 * nslots), dim3(THREADS), LDS_BYTES, stream, a);
   KERNEL_CHECK();
   return ALIBY_OK;
 }
@@ -373,7 +375,6 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep16(DeepArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, cb = tid >> 6;
   const int c16 = lane & 15, kg = lane >> 4;  // MFMA role: column (position) / k-group = output row group
   const int pl = tid & 7, pos0 = tid >> 3;    // staging role: a fixed channel octet of position pos0 + 32 * round
-  const int IH = UP ? a.H >> 1 : a.H, IW = UP ? a.W >> 1 : a.W;
   const int LW = a.LW, HP = a.HP;
   const int WIN = DC_RUN + 2 * LW + 2;
   const int cs = CIN / 8;
@@ -390,21 +391,12 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep16(DeepArgs a) {
     unsigned inside = 0, later = 0;
     const int n0 = max(0, ((p_first / LW) - 1) / HP);
     {
-      const int P0 = p_first + pos0;
-      int r = P0 >= 0 ? P0 / LW : -1, c = P0 - r * LW;
-      int n = r >= 1 ? (r - 1) / HP : 0, y = r >= 1 ? (r - 1) - n * HP : r - 1;
+      int c, y, n;
+      dc_win_pos(p_first + pos0, LW, HP, c, y, n);
 #pragma unroll
       for (int it = 0; it < DC_ITERS; ++it) {
-        const bool ok = y >= 0 && y < a.H && c >= 1 && c <= a.W && n < a.N;
-        inside |= (unsigned)ok << it;
-        later |= (unsigned)(n > n0) << it;
-        const int nn = min(n, a.N - 1), yy = min(max(y, 0), a.H - 1), xx = min(max(c - 1, 0), a.W - 1);
-        goff[it * 256] = ((nn * IH + (UP ? yy >> 1 : yy)) * IW + (UP ? xx >> 1 : xx)) * cs + pl;
-        c += 32;
-        while (c >= LW) {
-          c -= LW;
-          if (++y == HP) { y = 0; ++n; }
-        }
+        goff[it * 256] = dc_win_off<UP>(a, c, y, n, n0, cs, pl, true, it, inside, later);
+        dc_step32(c, y, n, LW, HP);
       }
     }
     const int n1 = min(n0 + 1, a.N - 1);
@@ -423,18 +415,15 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep16(DeepArgs a) {
     int qbase = q0 + c16;  // (re-read through an empty asm before the epilogue: its 14 positions are then computed again there
     // instead of being kept in 40 registers across the MFMA loops, which is what common-subexpression elimination does otherwise)
     auto where = [&](int b, int h, int& n, int& y, int& x) {  // image, row, column of this lane's position (b, h)
-      const int q = qbase + b * 32 + h * 16;
-      const int r = q / LW;  // >= 1: q >= q_begin = LW
-      x = q - r * LW - 1;
-      n = (r - 1) / HP;
-      y = (r - 1) - n * HP;
+      int c;
+      dc_out_pos(qbase + b * 32 + h * 16, LW, HP, c, y, n);
+      x = c - 1;
     };
     {
       float b8[8];
 #pragma unroll
       for (int k = 0; k < 8; ++k) b8[k] = a.bias ? a.bias[c0 + k] : 0.f;
       if (a.res) {
-        const int RH = a.H >> a.res_up, RW = a.W >> a.res_up;
         uint4 rr[DC_NB][2];
 #pragma unroll
         for (int b = 0; b < DC_NB; ++b)
@@ -442,8 +431,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep16(DeepArgs a) {
           for (int h = 0; h < 2; ++h) {
             int n, y, x;
             where(b, h, n, y, x);
-            const int nn = min(n, a.N - 1), yy = min(y, a.H - 1), xx = min(max(x, 0), a.W - 1);  // (clamped: not every position is stored)
-            rr[b][h] = a.res[(unsigned)(((nn * RH + (yy >> a.res_up)) * RW + (xx >> a.res_up)) * ocs + (c0 >> 3))];
+            rr[b][h] = a.res[dc_res_off(a, n, y, x, ocs, c0)];
           }
 #pragma unroll
         for (int b = 0; b < DC_NB; ++b)
@@ -478,18 +466,8 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep16(DeepArgs a) {
       auto wfrag = [&](int i, int aa) { return wp[(((i % 9) * K32T + (i / 9)) * 2 + aa) * 64]; };
 #pragma unroll
       for (int i = 0; i < WD - 1; ++i) { wring[i][0] = wfrag(i, 0); wring[i][1] = wfrag(i, 1); }
-      f32x2_t sc[4], sh[4], sh1[4];
-      {
-        const int ch = s * 64 + pl * 8;
-        const float* sp0 = a.shift + (size_t)n0 * a.shift_stride + ch;
-        const float* sp1 = a.shift + (size_t)n1 * a.shift_stride + ch;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          sc[k] = f32x2_t{a.scale[ch + 2 * k], a.scale[ch + 2 * k + 1]};
-          sh[k] = f32x2_t{sp0[2 * k], sp0[2 * k + 1]};
-          sh1[k] = f32x2_t{sp1[2 * k], sp1[2 * k + 1]};
-        }
-      }
+      f32x2_t sc[4], sh[4], sh1[4];  // the slice's prologue constants for this thread's octet
+      dc_prologue_consts(a, s, pl, n0, n1, sc, sh, sh1);
       __syncthreads();  // every wave is done reading the previous slice's planes
 #pragma unroll
       for (int it = 0; it < DC_ITERS; ++it) {
@@ -553,21 +531,6 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep16(DeepArgs a) {
   }
 }
 
-template <int CIN, bool UP>
-int launch_deep16(DeepArgs& a, hipStream_t stream) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_deep16<CIN, UP>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                DC16_LDS_BYTES));
-    attr_done = true;
-  }
-  const int per_xcd = (a.ntiles + 7) / 8;
-  const int nslots = per_xcd < 64 ? per_xcd : 64;  // 2 workgroups per CU, 32 CUs per XCD
-  hipLaunchKernelGGL((k_conv3x3_deep16<CIN, UP>), dim3(8 * nslots), dim3(256), DC16_LDS_BYTES, stream, a);
-  KERNEL_CHECK();
-  return ALIBY_OK;
-}
-
 // weights for k_conv3x3_deep16: out[(((cb * 9 + tap) * (CIN / 32) + k32) * 2 + a) * 64 + lane][j] =
 // W[32 cb + 8 (r >> 2) + 4 a + (r & 3)][64 (k32 >> 1) + 8 oct + j][tap], r = lane & 15, kg = lane >> 4,
 // oct = 2 (k32 & 1) + (kg >> 1) + 4 (kg & 1)
@@ -590,7 +553,7 @@ __global__ void k_pack_deep16(const float* __restrict__ w, int cout, int cin, un
 }
 
 // ------------------------------------------------------------------------------------------------
-// Loader-specialised form of the same unit (round 3).  Phase elimination on k_conv3x3_deep (scripts/deep_phases.sh, timing only):
+// Loader-specialised form of the same unit (round 3).  Phase elimination on k_conv3x3_deep (timing-only builds):
 // without the window loads 256 -> 256 runs 24 % faster, without residual loads 9 %, without stores 9 %, without all three
 // 31 % (1458 TFLOP/s) — although the loads are issued a k-step ahead, and moving the request anywhere in the slice changes
 // nothing.  The reason is the in-order vmcnt counter: a wave's weight-fragment waits (L2 hits, a few hundred cycles) cannot pass
@@ -601,12 +564,7 @@ __global__ void k_pack_deep16(const float* __restrict__ w, int cout, int cin, un
 //     hand-off), run it through the prologue into the OTHER of two plane images, request the slice after that, and meet the MFMA
 //     waves at ONE workgroup barrier per slice.
 // One workgroup (4 MFMA + DL_NLW loader waves, ~132 KB of LDS) per CU.  Same MFMA order as k_conv3x3_deep: same bits.
-#ifndef DL_HACK
-#define DL_HACK 0  // diagnostics like DC_HACK: 1 loaders idle, 2 no MFMA loop, 4 no residual, 8 no stores, 16 no prologue math, 32 no DMA
-#endif
-#ifndef DL_NLW
-#define DL_NLW 4                                          // loader waves
-#endif
+constexpr int DL_NLW = 4;                                 // loader waves
 constexpr int DL_LT = DL_NLW * 64;                        // loader threads
 constexpr int DL_UNITS = DC_WIN_MAX * 8;                  // 16-byte units of a slice's window (position-major, 8 octets each)
 constexpr int DL_ROUNDS = (DL_UNITS + DL_LT - 1) / DL_LT; // DMA instructions per loader wave and slice
@@ -619,7 +577,6 @@ __global__ __launch_bounds__(256 + DL_LT, 1) void k_conv3x3_deep_ls(DeepArgs a) 
   uint4* const planes0 = lds;
   uint4* const rawbuf = lds + 2 * 8 * DC_PLANE;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int IH = UP ? a.H >> 1 : a.H, IW = UP ? a.W >> 1 : a.W;
   const int LW = a.LW, HP = a.HP;
   const int WIN = DC_RUN + 2 * LW + 2;
   const int cs = CIN / 8;
@@ -648,34 +605,21 @@ __global__ __launch_bounds__(256 + DL_LT, 1) void k_conv3x3_deep_ls(DeepArgs a) 
 #pragma unroll
       for (int k = 0; k < DL_ROUNDS; ++k) {
         const int wp_ = (lt >> 3) + (DL_LT / 8) * k;    // window position of unit lt + DL_LT k
-        const int P0 = p_first + wp_;         // >= -1
-        const int r = P0 >= 0 ? P0 / LW : -1, c = P0 - r * LW;
-        const int n = r >= 1 ? (r - 1) / HP : 0, y = r >= 1 ? (r - 1) - n * HP : r - 1;
-        const bool ok = wp_ < WIN && y >= 0 && y < a.H && c >= 1 && c <= a.W && n < a.N;
-        inside |= (unsigned)ok << k;
-        later |= (unsigned)(n > n0) << k;
-        const int nn = min(n, a.N - 1), yy = min(max(y, 0), a.H - 1), xx = min(max(c - 1, 0), a.W - 1);
-        goff[k] = ((nn * IH + (UP ? yy >> 1 : yy)) * IW + (UP ? xx >> 1 : xx)) * cs + oct;
+        int c, y, n;
+        dc_win_pos(p_first + wp_, LW, HP, c, y, n);
+        goff[k] = dc_win_off<UP>(a, c, y, n, n0, cs, oct, wp_ < WIN, k, inside, later);
       }
     };
     auto issue_dma = [&](int s) {  // this wave's units of slice s -> rawbuf (lane-linear: unit u lands at rawbuf[u])
       const uint4* inS = a.in + s * 8;
 #pragma unroll
       for (int k = 0; k < DL_ROUNDS; ++k)
-        if constexpr (!(DL_HACK & 32)) __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(inS + (unsigned)goff[k]),
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(inS + (unsigned)goff[k]),
                                          (__attribute__((address_space(3))) void*)(rawbuf + k * DL_LT + wave_u * 64), 16, 0, 0);
     };
     auto activate = [&](int s, uint4* planes) {  // rawbuf -> prologue -> channel-octet planes
       f32x2_t sc[4], sh[4], sh1[4];
-      const int ch = s * 64 + oct * 8;
-      const float* sp0 = a.shift + (size_t)n0 * a.shift_stride + ch;
-      const float* sp1 = a.shift + (size_t)n1 * a.shift_stride + ch;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        sc[k] = f32x2_t{a.scale[ch + 2 * k], a.scale[ch + 2 * k + 1]};
-        sh[k] = f32x2_t{sp0[2 * k], sp0[2 * k + 1]};
-        sh1[k] = f32x2_t{sp1[2 * k], sp1[2 * k + 1]};
-      }
+      dc_prologue_consts(a, s, oct, n0, n1, sc, sh, sh1);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA pieces (and the constants above) have landed
 #pragma unroll
       for (int k = 0; k < DL_ROUNDS; ++k) {
@@ -684,8 +628,7 @@ __global__ __launch_bounds__(256 + DL_LT, 1) void k_conv3x3_deep_ls(DeepArgs a) 
         f32x2_t shs[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) shs[q] = ((later >> k) & 1u) ? sh1[q] : sh[q];
-        if constexpr (DL_HACK & 16) planes[oct * DC_PLANE + wp_] = rawbuf[k * DL_LT + lt];
-        else planes[oct * DC_PLANE + wp_] = dc_act8(rawbuf[k * DL_LT + lt], sc, shs, 0u - ((inside >> k) & 1u));
+        planes[oct * DC_PLANE + wp_] = dc_act8(rawbuf[k * DL_LT + lt], sc, shs, 0u - ((inside >> k) & 1u));
       }
     };
     // slice g of the workgroup = (tile g / S, slice g % S); prepared one barrier ahead of its MFMAs
@@ -700,7 +643,7 @@ __global__ __launch_bounds__(256 + DL_LT, 1) void k_conv3x3_deep_ls(DeepArgs a) 
     }
     for (int g = 0; g < G; ++g) {
       __syncthreads();  // B_g: planes[g & 1] hold slice g; the MFMA waves are done with planes[(g + 1) & 1]
-      if (g + 1 < G && !(DL_HACK & 1)) {
+      if (g + 1 < G) {
         const int s1 = (g + 1) % S;
         activate(s1, planes0 + ((g + 1) & 1) * 8 * DC_PLANE);  // (its offsets / masks are the ones its DMA was issued with)
         if (g + 2 < G) {
@@ -724,52 +667,13 @@ __global__ __launch_bounds__(256 + DL_LT, 1) void k_conv3x3_deep_ls(DeepArgs a) 
     const int q0 = a.q_begin + run * DC_RUN;
     const int c0 = half * 128 + cb * 32 + hh * 16;
     f32x16_t acc[DC_NB];
-    {
-      float b16[16];
-#pragma unroll
-      for (int k = 0; k < 16; ++k) b16[k] = a.bias ? a.bias[c0 + k] : 0.f;
-      if (a.res && !(DL_HACK & 4)) {
-        const int RH = a.H >> a.res_up, RW = a.W >> a.res_up;
-        uint4 rr[DC_NB][2];
-        {
-          const int q = q0 + px;
-          int r = q / LW, c = q - r * LW;
-          int n = (r - 1) / HP, y = (r - 1) - n * HP;
-#pragma unroll
-          for (int b = 0; b < DC_NB; ++b) {
-            const int nn = min(n, a.N - 1), yy = min(y, a.H - 1), xx = min(max(c - 1, 0), a.W - 1);
-            const unsigned roff = (unsigned)(((nn * RH + (yy >> a.res_up)) * RW + (xx >> a.res_up)) * ocs + (c0 >> 3));
-            rr[b][0] = a.res[roff];
-            rr[b][1] = a.res[roff + 1];
-            c += 32;
-            while (c >= LW) {
-              c -= LW;
-              if (++y == HP) { y = 0; ++n; }
-            }
-          }
-        }
-#pragma unroll
-        for (int b = 0; b < DC_NB; ++b) {
-          const unsigned rw[8] = {rr[b][0].x, rr[b][0].y, rr[b][0].z, rr[b][0].w, rr[b][1].x, rr[b][1].y, rr[b][1].z, rr[b][1].w};
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            acc[b][2 * j] = b16[2 * j] + dc_bf2f(rw[j] & 0xffffu);
-            acc[b][2 * j + 1] = b16[2 * j + 1] + dc_bf2f(rw[j] >> 16);
-          }
-        }
-      } else {
-#pragma unroll
-        for (int b = 0; b < DC_NB; ++b)
-#pragma unroll
-          for (int k = 0; k < 16; ++k) acc[b][k] = b16[k];
-      }
-    }
+    dc_seed32(a, q0, px, c0, ocs, LW, HP, acc);
     const bf16x8_t* wbase = reinterpret_cast<const bf16x8_t*>(a.wpk) + (size_t)(half * 4 + cb) * 9 * KCT * 64 + lane;
     for (int s = 0; s < S; ++s, ++g) {
       const bf16x8_t* wp = wbase + (size_t)(4 * s) * 64;
       constexpr int NW = 36;
       bf16x8_t wring[DC_WDEPTH];
-      auto wfrag = [&](int i) { if constexpr (DL_HACK & 64) return wp[0]; else return wp[((i % 9) * KCT + (i / 9)) * 64]; };
+      auto wfrag = [&](int i) { return wp[((i % 9) * KCT + (i / 9)) * 64]; };
 #pragma unroll
       for (int i = 0; i < DC_WDEPTH - 1; ++i) wring[i] = wfrag(i);
       __syncthreads();  // B_g
@@ -778,11 +682,11 @@ __global__ __launch_bounds__(256 + DL_LT, 1) void k_conv3x3_deep_ls(DeepArgs a) 
       bf16x8_t pring[DC_PDEPTH];
       auto pfrag = [&](int f) {
         const int i = f / DC_NB, b = f % DC_NB, kc = i / 9, tap = i % 9;
-        if constexpr (DL_HACK & 128) return L[f & 3]; else return L[2 * kc * DC_PLANE + b * 32 + row_off[tap / 3] + tap % 3];
+        return L[2 * kc * DC_PLANE + b * 32 + row_off[tap / 3] + tap % 3];
       };
 #pragma unroll
       for (int f = 0; f < DC_PDEPTH - 1; ++f) pring[f] = pfrag(f);
-      if constexpr (!(DL_HACK & 2)) sfor<NW>([&](auto ic) {
+      sfor<NW>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
         if constexpr (i + DC_WDEPTH - 1 < NW) wring[(i + DC_WDEPTH - 1) % DC_WDEPTH] = wfrag(i + DC_WDEPTH - 1);
         sfor<DC_NB>([&](auto bc) {
@@ -794,44 +698,8 @@ __global__ __launch_bounds__(256 + DL_LT, 1) void k_conv3x3_deep_ls(DeepArgs a) 
       });
     }
     __builtin_amdgcn_sched_barrier(0);
-    {
-      const int q = q0 + px;
-      int r = q / LW, c = q - r * LW;
-      int n = (r - 1) / HP, y = (r - 1) - n * HP;
-#pragma unroll
-      for (int b = 0; b < DC_NB; ++b) {
-        const int x = c - 1;
-        const bool ok = q0 + b * 32 + px < a.q_end && y < a.H && x >= 0 && x < a.W && n < a.N;
-        if (ok && (!(DL_HACK & 8) || acc[b][3] == 12345.f)) {
-          uint4* op = a.out + (unsigned)(((n * a.H + y) * a.W + x) * ocs + (c0 >> 3));
-          op[0] = make_uint4(dc_pack2(acc[b][0], acc[b][1]), dc_pack2(acc[b][2], acc[b][3]), dc_pack2(acc[b][4], acc[b][5]),
-                             dc_pack2(acc[b][6], acc[b][7]));
-          op[1] = make_uint4(dc_pack2(acc[b][8], acc[b][9]), dc_pack2(acc[b][10], acc[b][11]), dc_pack2(acc[b][12], acc[b][13]),
-                             dc_pack2(acc[b][14], acc[b][15]));
-        }
-        c += 32;
-        while (c >= LW) {
-          c -= LW;
-          if (++y == HP) { y = 0; ++n; }
-        }
-      }
-    }
+    dc_store32(a, q0, px, c0, ocs, LW, HP, acc);
   }
-}
-
-template <int CIN, bool UP>
-int launch_deep_ls(DeepArgs& a, hipStream_t stream) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_deep_ls<CIN, UP>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                DL_LDS_BYTES));
-    attr_done = true;
-  }
-  const int per_xcd = (a.ntiles + 7) / 8;
-  const int nslots = per_xcd < 32 ? per_xcd : 32;  // one workgroup per CU, 32 CUs per XCD
-  hipLaunchKernelGGL((k_conv3x3_deep_ls<CIN, UP>), dim3(8 * nslots), dim3(256 + DL_LT), DL_LDS_BYTES, stream, a);
-  KERNEL_CHECK();
-  return ALIBY_OK;
 }
 
 // max_pool2d(x, 2, 2) on bf16 NHWC: one 16-byte channel octet per thread (the comparison runs on the bf16 values as
@@ -915,20 +783,19 @@ static int deep_entry(aliby_ctx* ctx, const void* in, const void* wpk, void* out
   static const int stagger = [] { const char* e = getenv("ALIBY_DEEP_STAGGER"); return e ? atoi(e) : 0; }();
   a.stagger = stagger;
   a.trace = g_deep_trace;
-  if (m16) {
-    if (CIN == 64) return in_up ? launch_deep16<64, true>(a, stream) : launch_deep16<64, false>(a, stream);
-    if (CIN == 128) return in_up ? launch_deep16<128, true>(a, stream) : launch_deep16<128, false>(a, stream);
-    return in_up ? launch_deep16<256, true>(a, stream) : launch_deep16<256, false>(a, stream);
-  }
-  const char* ls = getenv("ALIBY_DEEP_LS");  // loader-specialised form: measured slower, kept for A/B; read per call
-  if (ls && atoi(ls)) {
-    if (CIN == 64) return in_up ? launch_deep_ls<64, true>(a, stream) : launch_deep_ls<64, false>(a, stream);
-    if (CIN == 128) return in_up ? launch_deep_ls<128, true>(a, stream) : launch_deep_ls<128, false>(a, stream);
-    return in_up ? launch_deep_ls<256, true>(a, stream) : launch_deep_ls<256, false>(a, stream);
-  }
-  if (CIN == 64) return in_up ? launch_deep<64, true>(a, stream) : launch_deep<64, false>(a, stream);
-  if (CIN == 128) return in_up ? launch_deep<128, true>(a, stream) : launch_deep<128, false>(a, stream);
-  return in_up ? launch_deep<256, true>(a, stream) : launch_deep<256, false>(a, stream);
+  const char* ls_env = getenv("ALIBY_DEEP_LS");  // loader-specialised form: measured slower, kept for A/B; read per call
+  const bool ls = ls_env && atoi(ls_env);
+  auto go = [&](auto cin, auto up) {
+    constexpr int C = decltype(cin)::value;
+    constexpr bool U = decltype(up)::value;
+    if (m16) return launch<k_conv3x3_deep16<C, U>, DC16_LDS_BYTES, 64, 256>(a, stream);
+    if (ls) return launch<k_conv3x3_deep_ls<C, U>, DL_LDS_BYTES, 32, 256 + DL_LT>(a, stream);  // one workgroup per CU
+    return launch<k_conv3x3_deep<C, U>, DC_LDS_BYTES, 64, 256>(a, stream, "ALIBY_DEEP_SLOTS");
+  };
+  auto by_up = [&](auto cin) { return in_up ? go(cin, std::true_type{}) : go(cin, std::false_type{}); };
+  if (CIN == 64) return by_up(std::integral_constant<int, 64>{});
+  if (CIN == 128) return by_up(std::integral_constant<int, 128>{});
+  return by_up(std::integral_constant<int, 256>{});
 }
 
 extern "C" int aliby_nn_conv3x3_deep_bf16(aliby_ctx* ctx, const void* in, const void* wpk, void* out, const float* scale,
