@@ -351,6 +351,55 @@ class FeatureEngine:
                                                            out.stride(0), 0, _stream_ptr()))
         return out
 
+    @property
+    def coloc3d_lds_voxels(self) -> int:
+        """Largest object, in voxels, that `coloc3d` measures from LDS; larger ones go through global scratch (same results)."""
+        return int(self.lib.aliby_coloc3d_lds_voxels())
+
+    def coloc3d(self, volume: torch.Tensor, pixels: torch.Tensor, pairs, counts, metrics=("pearson", "manders_fold", "rwc", "costes"),
+                thr: float = 15.0, scale_max: float = 255.0) -> torch.Tensor:
+        """Volume labels uint16 [F,Z,Y,X] (1..counts[f] per stack), pixels uint16 or float32 [F,C,Z,Y,X], pairs = [(c0, c1), ...]
+        -> float64 [sum counts, 2 * len(metrics) * len(pairs)] (features.coloc3d_names(pairs, metrics); aliby_features_coloc3d):
+        the 2-D colocalisation metrics over each object's voxels.  Rows in (stack, label) order, columns pair-major in the order
+        of `pairs` and `metrics`.  A label of 1..counts[f] without voxels gets a row of NaN.  Bitwise independent of run and batch."""
+        if not (isinstance(volume, torch.Tensor) and isinstance(pixels, torch.Tensor)):
+            raise TypeError("coloc3d takes torch tensors on the device")
+        if volume.dtype != torch.uint16:
+            raise TypeError(f"volume labels must be uint16, got {volume.dtype}")
+        if pixels.dtype not in (torch.uint16, torch.float32):
+            raise TypeError(f"pixels must be uint16 or float32, got {pixels.dtype}")
+        if volume.dim() != 4 or pixels.dim() != 5 or tuple(pixels.shape[:1]) != tuple(volume.shape[:1]) or tuple(pixels.shape[2:]) != tuple(volume.shape[1:]):
+            raise ValueError(f"volume must be [F,Z,Y,X] and pixels [F,C,Z,Y,X], got {tuple(volume.shape)} and {tuple(pixels.shape)}")
+        if not (volume.is_cuda and pixels.is_cuda):
+            raise ValueError("coloc3d takes tensors on the device")
+        F, Z, Y, X = volume.shape
+        Cn = int(pixels.shape[1])
+        names = feat.coloc3d_names(pairs, metrics)  # (refuses unknown or repeated metrics and malformed pairs)
+        pr = np.ascontiguousarray(np.asarray([(int(a), int(b)) for a, b in pairs], np.int32).reshape(-1, 2))
+        if len(pr) == 0 or len(pr) > 64:
+            raise ValueError(f"coloc3d takes between 1 and 64 channel pairs per call, got {len(pr)}")
+        if ((pr < 0) | (pr >= Cn)).any():
+            raise ValueError(f"channel out of range for {Cn} channels: {pairs!r}")
+        cnt = np.asarray(counts, np.int64).reshape(-1)
+        if cnt.shape != (F,) or (cnt < 0).any() or (cnt > 65535).any():
+            raise ValueError(f"counts must hold one label count (0..65535) per stack ({F}), got {counts!r}")
+        thr, scale_max = float(thr), float(scale_max)
+        if not (np.isfinite(thr) and np.isfinite(scale_max) and scale_max > 0):
+            raise ValueError(f"thr must be finite and scale_max positive and finite, got {thr!r}, {scale_max!r}")
+        offsets = np.zeros(F + 1, np.int32)
+        np.cumsum(cnt, out=offsets[1:])
+        stride = 2 * len(metrics)
+        out = self.new_output(int(offsets[-1]), len(names))
+        if int(offsets[-1]) == 0:
+            return out  # stacks without any object: an empty block
+        col = {m: 2 * k for k, m in enumerate(metrics)}
+        with self.timed("coloc3d"):
+            _lib.check(self.lib.aliby_features_coloc3d(
+                self.ctx.handle, _ptr(volume.contiguous()), _ptr(pixels.contiguous()), _lib.U16 if pixels.dtype == torch.uint16 else _lib.F32,
+                F, Cn, Z, Y, X, _ptr(pr), len(pr), _ptr(offsets), _ptr(out), out.stride(0), 0, stride, col.get("pearson", -1),
+                col.get("manders_fold", -1), col.get("rwc", -1), col.get("costes", -1), thr, scale_max, _stream_ptr()))
+        return out
+
     def relabel_sequential(self, labels: torch.Tensor) -> np.ndarray:
         F, Y, X = labels.shape
         n = np.zeros(F, np.int32)

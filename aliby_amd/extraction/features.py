@@ -184,3 +184,23 @@ def sizeshape3d_names() -> list[str]:
     return ["Volume", "BoundingBoxMinimum_X", "BoundingBoxMinimum_Y", "BoundingBoxMinimum_Z", "BoundingBoxMaximum_X", "BoundingBoxMaximum_Y",
             "BoundingBoxMaximum_Z", "BoundingBoxVolume", "Center_X", "Center_Y", "Center_Z", "Extent", "EquivalentDiameter", "EulerNumber",
             "MajorAxisLength", "MinorAxisLength", "InertiaTensorEigenvalues_0", "InertiaTensorEigenvalues_1", "InertiaTensorEigenvalues_2"]
+
+
+def coloc3d_names(pairs, metrics=("pearson", "manders_fold", "rwc", "costes")) -> list[str]:
+    """Columns of `FeatureEngine.coloc3d` (csrc/feat_coloc3d.hip): for every channel pair, in the order given, the two columns of
+    every metric, in the order given: "(c0, c1)/<metric>/<name>", e.g. "(0, 1)/pearson/Correlation_Pearson".  That is the 2-D
+    multi tree's key "(c0, c1)/<reduction>/<z reduction>/<metric>/<name>" without the two reductions a volume has no use for.
+    The names are cp_measure's 2-D ones; parity with cp_measure on volumes is unpinned, like the other 3-D families."""
+    metrics = list(metrics)
+    unknown = [m for m in metrics if m not in COLOC]
+    if unknown or not metrics or len(set(metrics)) != len(metrics):
+        raise ValueError(f"metrics must be distinct names out of {sorted(COLOC)}, got {metrics!r}")
+    out = []
+    for pair in pairs:
+        if len(pair) != 2:
+            raise ValueError(f"a channel pair is (c0, c1), got {pair!r}")
+        c0, c1 = int(pair[0]), int(pair[1])
+        if c0 == c1 or c0 < 0 or c1 < 0:
+            raise ValueError(f"a channel pair needs two different non-negative channels, got {pair!r}")
+        out += [f"({c0}, {c1})/{m}/{name}" for m in metrics for name in COLOC[m]]
+    return out

@@ -544,6 +544,19 @@ int aliby_features_intensity3d(aliby_ctx* ctx, const uint16_t* labels, const uin
  * voxels gets Volume 0 and NaN elsewhere.  Exact integer sums: run-to-run deterministic and independent of the batch. */
 int aliby_features_sizeshape3d(aliby_ctx* ctx, const uint16_t* labels, int F, int Z, int Y, int X, const int32_t* offsets_host,
                                const double* spacing, double* out, int ld, int col0, void* stream);
+/* Colocalisation of channel pairs inside the objects of the same labelled stacks: labels uint16 [F,Z,Y,X], pixels [F,C,Z,Y,X] of
+ * dtype ALIBY_U16 or ALIBY_F32, pairs_host = n_pairs x (ch0, ch1) with ch0 != ch1 (at most 64).  Over the voxels of object
+ * (f, label) = row offsets_host[f] + label - 1 in raster order (z, y, x), the metrics of aliby_features_coloc with the same
+ * definitions: pair p writes at out[row * ld + col0 + p * pair_stride + col_<metric>], two columns per metric (Pearson, Slope /
+ * Manders_1, _2 / RWC_1, _2 / Costes_1, _2), col_<metric> = -1 skips it.  RWC's dense ranks and Costes' threshold are per
+ * object.  A label of 1..n_f without voxels gets NaN in every requested column.  Objects of up to aliby_coloc3d_lds_voxels()
+ * voxels are measured from LDS, larger ones from global scratch, by the same code: results are bitwise independent of the run,
+ * of the other objects of the call and of the batch. */
+int aliby_coloc3d_lds_voxels(void);
+int aliby_features_coloc3d(aliby_ctx* ctx, const uint16_t* labels, const void* pixels, int dtype, int F, int C, int Z, int Y, int X,
+                           const int32_t* pairs_host, int n_pairs, const int32_t* offsets_host, double* out, int ld, int col0,
+                           int pair_stride, int col_pearson, int col_manders, int col_rwc, int col_costes, double thr_percent,
+                           double costes_scale_max, void* stream);
 
 /* ---- a17: the step API's files, encoded natively (host code, no GPU work) ------------------ */
 /* profiles/<name>.parquet — pyarrow.parquet.write_table(profiles, path, compression="zstd")
