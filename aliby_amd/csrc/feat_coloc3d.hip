@@ -5,7 +5,7 @@
 // (definitions: the header of feat_coloc.hip; the arithmetic itself is coloc_stats.h, shared with the 2-D per-pair kernel).
 //
 // Two passes.
-//   1. k_c3_table: voxel count and bounding box per (stack, label), one read of the labels.  A lane walks 16 voxels of a row and
+//   1. k_c3_table (volume_table.h): voxel count and bounding box per (stack, label), one read of the labels.  A lane walks 16 voxels of a row and
 //      flushes once per run of equal labels; integer atomics only, so the table is exact whatever the order.
 //   2. k_coloc3d: one workgroup of 256 lanes per (object, pair).  The object's voxels of both channels are gathered from its
 //      bounding box in raster order (z, y, x) by order-preserving compaction into two float lists, then each list is copied,
@@ -17,6 +17,7 @@
 // independent of all three (the 2-D kernels size their workgroup by the launch's largest object and are not).
 #include "common.h"
 #include "coloc_stats.h"
+#include "volume_table.h"  // k_c3_table, shared with feat_texture3d.hip
 
 typedef unsigned short u16;
 
@@ -28,39 +29,6 @@ typedef unsigned short u16;
 #define C3_GLOBAL_BYTES (1ull << 30)  // ceiling of the global-scratch form's lists, all workgroups together
 
 namespace {
-
-// labels [F, Z, Y, X]; offsets[f] = first row of stack f; row = offsets[f] + label - 1; bmin / bmax [row][z, y, x]
-__global__ __launch_bounds__(256) void k_c3_table(const u16* __restrict__ labels, int F, int Z, int Y, int X, const int* __restrict__ offsets,
-                                                  unsigned* __restrict__ count, unsigned* __restrict__ bmin, unsigned* __restrict__ bmax) {
-  const size_t vol = (size_t)Z * Y * X;
-  const int segs = (X + 15) / 16;
-  const size_t total = (size_t)F * Z * Y * segs;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int sg = (int)(i % segs);
-    size_t rest = i / segs;
-    const unsigned y = (unsigned)(rest % Y);
-    rest /= Y;
-    const unsigned z = (unsigned)(rest % Z);
-    const int f = (int)(rest / Z);
-    const u16* lb = labels + (size_t)f * vol + ((size_t)z * Y + y) * X;
-    const int x0 = sg * 16, x1 = min(X, x0 + 16);
-    const int base = offsets[f], nrows = offsets[f + 1] - base;
-    unsigned cur = 0;
-    int xs = x0;
-    for (int x = x0; x <= x1; ++x) {
-      const unsigned L = x < x1 ? lb[x] : 0xffffffffu;  // (the sentinel closes the last run)
-      if (L == cur) continue;
-      if (cur && (int)cur <= nrows) {
-        const size_t row = (size_t)(base + cur - 1);
-        atomicAdd(&count[row], (unsigned)(x - xs));
-        atomicMin(&bmin[row * 3 + 0], z); atomicMin(&bmin[row * 3 + 1], y); atomicMin(&bmin[row * 3 + 2], (unsigned)xs);
-        atomicMax(&bmax[row * 3 + 0], z); atomicMax(&bmax[row * 3 + 1], y); atomicMax(&bmax[row * 3 + 2], (unsigned)(x - 1));
-      }
-      cur = L;
-      xs = x;
-    }
-  }
-}
 
 struct C3Args {
   const u16* labels;
@@ -249,17 +217,10 @@ extern "C" int aliby_features_coloc3d(aliby_ctx* ctx, const uint16_t* labels, co
   int rc = aliby_ensure_scratch(ctx, head_bytes);
   if (rc) return rc;
   unsigned* count = (unsigned*)ctx->scratch;
-  HIP_TRY(hipMemsetAsync(count, 0, sizeof(unsigned) * (size_t)n, s));
-  HIP_TRY(hipMemsetAsync(count + n, 0xFF, sizeof(unsigned) * (size_t)n * 3, s));
-  HIP_TRY(hipMemsetAsync(count + (size_t)n * 4, 0, sizeof(unsigned) * (size_t)n * 3, s));
   int* d_off = (int*)(count + tab_words);
   HIP_TRY(hipMemcpyAsync(d_off, offsets_host, sizeof(int) * (size_t)(F + 1), hipMemcpyHostToDevice, s));
-  {
-    const size_t total = (size_t)F * Z * Y * ((X + 15) / 16);
-    const unsigned grid = (unsigned)((total + 255) / 256 < 32768 ? (total + 255) / 256 : 32768);
-    hipLaunchKernelGGL(k_c3_table, dim3(grid), dim3(256), 0, s, labels, F, Z, Y, X, d_off, count, count + n, count + (size_t)n * 4);
-    KERNEL_CHECK();
-  }
+  rc = volume_table_launch(labels, F, Z, Y, X, d_off, n, count, s);
+  if (rc) return rc;
   unsigned* table_host = (unsigned*)malloc(sizeof(unsigned) * tab_words + sizeof(int) * (size_t)n);
   if (!table_host) { aliby_set_error("coloc3d: out of host memory"); return ALIBY_ERR_INVALID; }
   int* items_host = (int*)(table_host + tab_words);

@@ -17,11 +17,9 @@
 // (p_x, p_{x+y}, p_{x-y}) are integer LDS histograms, so every statistic is exact-integer counts
 // divided once by the total: no atomics on floats, run-to-run deterministic.
 #include "common.h"
-#include <atomic>
+#include "haralick_stats.h"  // grey_of, the log2 table, cells -> marginals -> the 13 statistics (shared with feat_texture3d.hip)
 
 typedef unsigned short u16;
-
-#define TX_NSTAT 13
 
 struct TextureArgs {
   const u16* labels;
@@ -38,34 +36,6 @@ struct TextureArgs {
   double* out;
   int ld, col0;
 };
-
-__device__ __forceinline__ int grey_of(unsigned short v, int gl, int shift) {
-  int q = v >> shift;
-  if (gl != 256) q = (int)((double)q / 255.0 * (double)(gl - 1));
-  return q;
-}
-__device__ __forceinline__ int grey_of(float v, int gl, int) {
-  double x = rint((double)v * 255.0);
-  x = fmin(fmax(x, 0.0), 255.0);
-  int q = (int)x;
-  if (gl != 256) q = (int)((double)q / 255.0 * (double)(gl - 1));
-  return q;
-}
-
-// Every probability of the co-occurrence statistics is an integer count over the total T, so p log2(p) is
-// (c / T) (log2 c - log2 T): log2 of the integers below 2^16 comes from a table in device memory (512 KB, L2-resident,
-// filled once per device with the same log2() it replaces); the fp64 log2 sequence was most of the kernel's instructions.
-#define TX_LOGTAB 65536
-__device__ double g_log2_int[TX_LOGTAB];
-__global__ void k_init_log2_table() {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < TX_LOGTAB) g_log2_int[i] = i > 0 ? log2((double)i) : 0.0;
-}
-__device__ __forceinline__ double log2_int(int n) { return n < TX_LOGTAB ? g_log2_int[n] : log2((double)n); }
-// (c / T) log2(c / T), logT = log2(T)
-__device__ __forceinline__ double plog2p_count(int c, double Tt, double logT) {
-  return c > 0 ? ((double)c / Tt) * (log2_int(c) - logT) : 0.0;
-}
 
 template <typename T, bool GLOBAL>
 __global__ __launch_bounds__(256) void k_texture(TextureArgs a) {
@@ -212,26 +182,10 @@ __global__ __launch_bounds__(256) void k_texture(TextureArgs a) {
 
       // ---- non-zero cells -> integer marginals + cell sums ------------------------------------------
       double acc[3] = {0, 0, 0};  // sum p^2 (as counts^2), sum i*j*count, sum p*log2(p)
-      auto cell1 = [&](int c, int lo, int hi) {  // c pixel pairs with the unordered grey-level pair (lo, hi)
-        if (lo == hi) {
-          atomicAdd(&hx[lo], 2 * c);
-          acc[0] += 4.0 * (double)c * (double)c;
-          acc[2] += plog2p_count(2 * c, Tt, logT);
-        } else {
-          atomicAdd(&hx[lo], c);
-          atomicAdd(&hx[hi], c);
-          acc[0] += 2.0 * (double)c * (double)c;
-          acc[2] += 2.0 * plog2p_count(c, Tt, logT);
-        }
-        atomicAdd(&hplus[lo + hi], 2 * c);
-        atomicAdd(&hminus[hi - lo], 2 * c);
-        acc[1] += 2.0 * (double)c * (double)lo * (double)hi;
-      };
+      auto cell1 = [&](int c, int lo, int hi) { haralick_cell(c, lo, hi, Tt, logT, hx, hplus, hminus, acc); };
       auto dense_cell = [&](int idx, int& c, int& lo, int& hi) {  // triangular index -> (count, levels)
         c = (int)((cells[idx >> 1] >> (16 * (idx & 1))) & 0xffffu);
-        int rh = (int)((sqrtf(8.0f * (float)idx + 1.0f) - 1.0f) * 0.5f);
-        while (rh * (rh + 1) / 2 > idx) --rh;
-        while ((rh + 1) * (rh + 2) / 2 <= idx) ++rh;
+        const int rh = haralick_tri_row(idx);
         lo = lev[idx - rh * (rh + 1) / 2];
         hi = lev[rh];
       };
@@ -250,38 +204,8 @@ __global__ __launch_bounds__(256) void k_texture(TextureArgs a) {
           cell1(lo_ - i, (int)(key >> 8), (int)(key & 255u));
         }
       }
-      block_sum_vec_all<3>(acc, vec);
-      __syncthreads();
-      const double f_asm = acc[0] / (Tt * Tt);
-      const double sum_ij = acc[1] / Tt;
-      const double f_entropy = -acc[2];
-
-      // ---- marginal statistics --------------------------------------------------------------------
-      double m[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      // m0 = ux, m1 = sum k^2 px, m2 = HX(sum p log p), m3 = contrast, m4 = IDM, m5 = sum p_minus,
-      // m6 = sum p_minus^2 (for the vector variance), m7 = difference entropy (sum p log p)
-      for (int k = minlev + tid; k <= maxlev; k += blockDim.x) {  // p_x is zero outside the present levels
-        const double pxk = (double)hx[k] / Tt;
-        m[0] += (double)k * pxk;
-        m[1] += (double)k * (double)k * pxk;
-        m[2] += plog2p_count(hx[k], Tt, logT);
-      }
-      for (int k = tid; k <= maxlev - minlev; k += blockDim.x) {  // |i - j| never exceeds the level range
-        const double pm = (double)hminus[k] / Tt;
-        m[3] += (double)k * (double)k * pm;
-        m[4] += pm / (1.0 + (double)k * (double)k);
-        if (k < maxv) { m[5] += pm; m[6] += pm * pm; }
-        m[7] += plog2p_count(hminus[k], Tt, logT);
-      }
-      block_sum_vec_all<8>(m, vec);
-      double s[3] = {0, 0, 0};  // sum average, sum k^2 p_plus, sum entropy (sum p log p)
-      for (int k = 2 * minlev + tid; k <= 2 * maxlev; k += blockDim.x) {
-        const double pp = (double)hplus[k] / Tt;
-        s[0] += (double)k * pp;
-        s[1] += (double)k * (double)k * pp;
-        s[2] += plog2p_count(hplus[k], Tt, logT);
-      }
-      block_sum_vec_all<3>(s, vec);
+      HaralickSums hs;
+      haralick_marginal_sums(hs, acc, hx, hplus, hminus, minlev, maxlev, maxv, Tt, logT, vec);
 
       // HXY1 = -sum_ij p_ij log2(px_i py_j): second pass over the cells now that p_x is complete
       double hxy = 0;
@@ -289,7 +213,7 @@ __global__ __launch_bounds__(256) void k_texture(TextureArgs a) {
         for (int idx = tid; idx < ncell; idx += blockDim.x) {
           int c, lo, hi;
           dense_cell(idx, c, lo, hi);
-          if (c) hxy += (2.0 * (double)c / Tt) * (log2_int(hx[lo]) + log2_int(hx[hi]) - 2.0 * logT);
+          if (c) hxy += haralick_hxy1_term(c, lo, hi, hx, Tt, logT);
         }
       } else {
         for (int i = tid; i < NP; i += blockDim.x) {
@@ -299,35 +223,10 @@ __global__ __launch_bounds__(256) void k_texture(TextureArgs a) {
           while (lo_ < hi_) { const int mid = (lo_ + hi_) >> 1; if (keys[mid] == key) lo_ = mid + 1; else hi_ = mid; }
           const int c = lo_ - i;
           const int lo = (int)(key >> 8), hi = (int)(key & 255u);
-          hxy += (2.0 * (double)c / Tt) * (log2_int(hx[lo]) + log2_int(hx[hi]) - 2.0 * logT);
+          hxy += haralick_hxy1_term(c, lo, hi, hx, Tt, logT);
         }
       }
-      double hv[1] = {hxy};
-      block_sum_vec_all<1>(hv, vec);
-
-      if (tid == 0) {
-        const double ux = m[0], vx = m[1] - ux * ux, sx = sqrt(vx);
-        const double HX = -m[2];
-        const double HXY1 = -hv[0];
-        const double HXY2 = 2.0 * HX;  // -sum (px_i py_j) log2(px_i py_j) with p symmetric
-        fo[0] = f_asm;
-        fo[1] = m[3];
-        fo[2] = (sx == 0.0) ? 1.0 : (1.0 / sx / sx) * (sum_ij - ux * ux);
-        fo[3] = vx;
-        fo[4] = m[4];
-        fo[5] = s[0];
-        fo[6] = s[1] - s[0] * s[0];
-        fo[7] = -s[2];
-        fo[8] = f_entropy;
-        {
-          // numpy var of the length-maxv vector p_{x-y}: mean(|x - mean|^2)
-          const double mean = m[5] / (double)maxv;
-          fo[9] = m[6] / (double)maxv - mean * mean;
-        }
-        fo[10] = -m[7];
-        fo[11] = (HX == 0.0) ? (f_entropy - HXY1) : (f_entropy - HXY1) / HX;
-        fo[12] = sqrt(fmax(0.0, 1.0 - exp(-2.0 * (HXY2 - f_entropy))));
-      }
+      haralick_finish(fo, hs, hxy, maxv, vec);
       __syncthreads();
     }
   }
@@ -359,16 +258,7 @@ extern "C" int aliby_features_texture(aliby_ctx* ctx, const uint16_t* labels, co
   a.cap_cells = max_area < 65536 ? 2 * ck : 0;
   const size_t need = (size_t)a.cap_pix + (size_t)ck * 4;
   hipStream_t s = as_stream(stream);
-  {
-    static std::atomic<unsigned long long> ready{0};  // one bit per device
-    const unsigned long long bit = 1ull << (ctx->device & 63);
-    if (!(ready.load(std::memory_order_acquire) & bit)) {
-      hipLaunchKernelGGL(k_init_log2_table, dim3(TX_LOGTAB / 256), dim3(256), 0, s);
-      KERNEL_CHECK();
-      HIP_TRY(hipStreamSynchronize(s));  // other streams may run this kernel next
-      ready.fetch_or(bit, std::memory_order_release);
-    }
-  }
+  { const int rc = haralick_log2_table_ready(ctx, s); if (rc) return rc; }
   if (need <= 96 * 1024) {
     a.gscratch = nullptr;
     dim3 grid(n_obj), block(aliby_pick_block((long long)max_h * max_w));

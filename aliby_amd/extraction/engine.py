@@ -400,6 +400,50 @@ class FeatureEngine:
                 col.get("manders_fold", -1), col.get("rwc", -1), col.get("costes", -1), thr, scale_max, _stream_ptr()))
         return out
 
+    @property
+    def texture3d_lds_voxels(self) -> int:
+        """Largest bounding box, in voxels, that `texture3d` measures from LDS; larger boxes go through global scratch (same results)."""
+        return int(self.lib.aliby_texture3d_lds_voxels())
+
+    def texture3d(self, volume: torch.Tensor, pixels: torch.Tensor, channel: int, counts, scale: int = 3, gray_levels: int = 256) -> torch.Tensor:
+        """Volume labels uint16 [F,Z,Y,X] (1..counts[f] per stack), pixels uint16 or float32 [F,C,Z,Y,X] -> float64 [sum counts, 169]
+        (features.texture3d_names(scale, gray_levels); aliby_features_texture3d): the 13 Haralick statistics of the 2-D `texture`
+        in 13 directions over each object's bounding box, direction-major.  Rows in (stack, label) order.  A direction without a
+        voxel pair gets 13 NaN, a label of 1..counts[f] without voxels a row of NaN.  Bitwise independent of run and batch."""
+        if not (isinstance(volume, torch.Tensor) and isinstance(pixels, torch.Tensor)):
+            raise TypeError("texture3d takes torch tensors on the device")
+        if volume.dtype != torch.uint16:
+            raise TypeError(f"volume labels must be uint16, got {volume.dtype}")
+        if pixels.dtype not in (torch.uint16, torch.float32):
+            raise TypeError(f"pixels must be uint16 or float32, got {pixels.dtype}")
+        if volume.dim() != 4 or pixels.dim() != 5 or tuple(pixels.shape[:1]) != tuple(volume.shape[:1]) or tuple(pixels.shape[2:]) != tuple(volume.shape[1:]):
+            raise ValueError(f"volume must be [F,Z,Y,X] and pixels [F,C,Z,Y,X], got {tuple(volume.shape)} and {tuple(pixels.shape)}")
+        if not (volume.is_cuda and pixels.is_cuda):
+            raise ValueError("texture3d takes tensors on the device")
+        F, Z, Y, X = volume.shape
+        Cn = int(pixels.shape[1])
+        for name, v in (("channel", channel), ("scale", scale), ("gray_levels", gray_levels)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"{name} must be an integer, got {v!r}")
+        channel, scale, gray_levels = int(channel), int(scale), int(gray_levels)
+        if not 0 <= channel < Cn:
+            raise ValueError(f"channel {channel} out of range for {Cn} channels")
+        if scale < 1 or not 2 <= gray_levels <= 256:
+            raise ValueError(f"texture3d needs scale >= 1 and 2 <= gray_levels <= 256, got {scale}, {gray_levels}")
+        cnt = np.asarray(counts, np.int64).reshape(-1)
+        if cnt.shape != (F,) or (cnt < 0).any() or (cnt > 65535).any():
+            raise ValueError(f"counts must hold one label count (0..65535) per stack ({F}), got {counts!r}")
+        offsets = np.zeros(F + 1, np.int32)
+        np.cumsum(cnt, out=offsets[1:])
+        out = self.new_output(int(offsets[-1]), len(feat.texture3d_names(scale, gray_levels)))
+        if int(offsets[-1]) == 0:
+            return out  # stacks without any object: an empty block
+        with self.timed("texture3d"):
+            _lib.check(self.lib.aliby_features_texture3d(
+                self.ctx.handle, _ptr(volume.contiguous()), _ptr(pixels.contiguous()), _lib.U16 if pixels.dtype == torch.uint16 else _lib.F32,
+                F, Cn, Z, Y, X, channel, _ptr(offsets), scale, gray_levels, _ptr(out), out.stride(0), 0, _stream_ptr()))
+        return out
+
     def relabel_sequential(self, labels: torch.Tensor) -> np.ndarray:
         F, Y, X = labels.shape
         n = np.zeros(F, np.int32)

@@ -204,3 +204,10 @@ def coloc3d_names(pairs, metrics=("pearson", "manders_fold", "rwc", "costes")) -
             raise ValueError(f"a channel pair needs two different non-negative channels, got {pair!r}")
         out += [f"({c0}, {c1})/{m}/{name}" for m in metrics for name in COLOC[m]]
     return out
+
+
+def texture3d_names(scale: int = 3, gray_levels: int = 256) -> list[str]:
+    """Columns of `FeatureEngine.texture3d` (csrc/feat_texture3d.hip): the 13 Haralick statistics x 13 directions, direction-major,
+    named as the 2-D `texture_names` names its 4 (mahotas' (13, 13) result on a 3-D array).  Which direction a block index stands
+    for is the kernel's table (the header of feat_texture3d.hip); that order and parity with cp_measure are unpinned."""
+    return [f"{h}_{scale}_{d:02d}_{gray_levels}" for d in range(13) for h in HARALICK]

@@ -557,6 +557,20 @@ int aliby_features_coloc3d(aliby_ctx* ctx, const uint16_t* labels, const void* p
                            const int32_t* pairs_host, int n_pairs, const int32_t* offsets_host, double* out, int ld, int col0,
                            int pair_stride, int col_pearson, int col_manders, int col_rwc, int col_costes, double thr_percent,
                            double costes_scale_max, void* stream);
+/* Haralick texture of one channel inside the objects of the same labelled stacks: labels uint16 [F,Z,Y,X], pixels [F,C,Z,Y,X] of
+ * dtype ALIBY_U16 or ALIBY_F32.  Per object (f, label) = row offsets_host[f] + label - 1: grey levels as aliby_features_texture
+ * takes them (uint16 >> 8, or rint(255 f) clipped; rescaled to gray_levels), the bounding box in (z, y, x) with every voxel of
+ * another label set to 0, and for each of 13 directions the symmetric co-occurrence matrix of the voxel pairs (p, p + scale d)
+ * inside the box, pairs touching grey level 0 dropped; the 13 Haralick statistics of aliby_features_texture per direction, 169
+ * columns at out[row * ld + col0 ..], direction-major.  Directions d on the axes (z, y, x), in column order: (1,0,0) (1,1,0)
+ * (0,1,0) (1,-1,0) (0,0,1) (1,0,1) (0,1,1) (1,1,1) (1,-1,1) (1,0,-1) (0,1,-1) (1,1,-1) (1,-1,-1) (mahotas' order as recalled:
+ * unpinned).  A direction without a pair gets 13 NaN, a label of 1..n_f without voxels a row of NaN.  Objects whose bounding box
+ * holds up to aliby_texture3d_lds_voxels() voxels are measured from LDS, larger ones from global scratch, by the same code:
+ * results are bitwise independent of the run, of the other objects of the call and of the batch. */
+int aliby_texture3d_lds_voxels(void);
+int aliby_features_texture3d(aliby_ctx* ctx, const uint16_t* labels, const void* pixels, int dtype, int F, int C, int Z, int Y, int X,
+                             int channel, const int32_t* offsets_host, int scale, int gray_levels, double* out, int ld, int col0,
+                             void* stream);
 
 /* ---- a17: the step API's files, encoded natively (host code, no GPU work) ------------------ */
 /* profiles/<name>.parquet — pyarrow.parquet.write_table(profiles, path, compression="zstd")

@@ -3,7 +3,8 @@ Cost of the volume feature families on a BASELINE config-5 stack (uint16 labels 
 ellipsoids relabelled 1..n; pixels of channel 0): `FeatureEngine.intensity3d` (4 bytes per voxel: labels + pixels) and
 `FeatureEngine.sizeshape3d` (2 bytes per voxel, 2.57 with the low-side halo of its 8 x 8 x 64 tiles), one stack and a batch of 8,
 and `FeatureEngine.coloc3d` on both channels (one pair, all four metrics: the labels once for the object table, then per object
-the labels of its bounding box and its voxels of both channels; `coloc3d_bytes`).
+the labels of its bounding box and its voxels of both channels; `coloc3d_bytes`), and `FeatureEngine.texture3d` on channel 0
+(scale 3, 256 grey levels: the labels once for the object table, then labels and pixels of every bounding box; `texture3d_bytes`).
 Times are the engine's own `timed(...)` events around each call (memsets, offsets upload, accumulation and finalise kernels), the
 families alternating, warm-up calls discarded; prints one JSON line.  The 16.8 MB of labels of one stack stay resident in
 the 256 MB Infinity Cache between repeats, so the "fraction of HBM peak" of F = 1 is a rate against the HBM figure, not proof of
@@ -53,6 +54,16 @@ def coloc3d_bytes(labels, n, F, n_pairs=1, px_bytes=2):
     return F * (2 * lab.size + n_pairs * (2 * boxes + 2 * px_bytes * int(counts.sum()))), int(counts.max())
 
 
+def texture3d_bytes(labels, n, F, px_bytes=2):
+    """Bytes texture3d asks for: the label volume once (object table), then labels and pixels of every bounding box.
+    -> (bytes, voxels of every box)."""
+    from scipy import ndimage as ndi
+
+    lab = labels.cpu().numpy()
+    boxes = np.asarray([int(np.prod([s.stop - s.start for s in sl])) for sl in ndi.find_objects(lab.astype(np.int32), n) if sl is not None])
+    return F * (2 * lab.size + (2 + px_bytes) * int(boxes.sum())), boxes
+
+
 def main(warmup=3, reps=20):
     torch.cuda.set_device(0)
     f = synth.make_fov(5, 0)
@@ -76,26 +87,31 @@ def main(warmup=3, reps=20):
             eng.intensity3d(vol, px, 0, counts)
             eng.sizeshape3d(vol, counts)
             eng.coloc3d(vol, px2, [(0, 1)], counts)
+            eng.texture3d(vol, px, 0, counts)
         torch.cuda.synchronize()
         eng.profile = {}
         for _ in range(reps):
             eng.intensity3d(vol, px, 0, counts)
             eng.sizeshape3d(vol, counts)
             eng.coloc3d(vol, px2, [(0, 1)], counts)
+            eng.texture3d(vol, px, 0, counts)
         torch.cuda.synchronize()
         ms = {k: [a.elapsed_time(b) for a, b in v] for k, v in eng.profile.items()}
         eng.profile = None
         voxels = vol.numel()
         c3_bytes, c3_largest = coloc3d_bytes(labels, len(present), F)
-        moved = {"intensity3d": 4 * voxels, "sizeshape3d": 2 * voxels, "coloc3d": c3_bytes}
+        t3_bytes, t3_boxes = texture3d_bytes(labels, len(present), F)
+        moved = {"intensity3d": 4 * voxels, "sizeshape3d": 2 * voxels, "coloc3d": c3_bytes, "texture3d": t3_bytes}
         out = {}
-        for name in ("intensity3d", "sizeshape3d", "coloc3d"):
+        for name in ("intensity3d", "sizeshape3d", "coloc3d", "texture3d"):
             med, best = statistics.median(ms[name]), min(ms[name])
             out[name] = dict(ms_median=round(med, 4), ms_min=round(best, 4), ms_max=round(max(ms[name]), 4), bytes_algorithmic=moved[name],
                              fraction_of_hbm_peak=round(moved[name] / (med * 1e-3) / HBM_PEAK, 4))
         out["sizeshape3d"]["bytes_staged_with_halo"] = staged_bytes(F, *labels.shape)
         out["coloc3d"].update(largest_object_voxels=c3_largest, lds_budget_voxels=eng.coloc3d_lds_voxels,
                               objects_in_global_scratch_form=int((np.bincount(lut[gt].ravel())[1:] > eng.coloc3d_lds_voxels).sum()) * F)
+        out["texture3d"].update(largest_box_voxels=int(t3_boxes.max()), lds_budget_box_voxels=eng.texture3d_lds_voxels,
+                                objects_in_global_scratch_form=int((t3_boxes > eng.texture3d_lds_voxels).sum()) * F)
         out["sizeshape3d_over_intensity3d"] = round(out["sizeshape3d"]["ms_median"] / out["intensity3d"]["ms_median"], 3)
         res[f"F{F}"] = out
     print(json.dumps(res))
