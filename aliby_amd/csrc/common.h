@@ -58,6 +58,15 @@ static inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
 // waves would spend their time in barriers.  `work` = pixels the workgroup loops over (bbox or area).
 static inline int aliby_pick_block(long long work) { return work <= 2048 ? 64 : (work <= 8192 ? 128 : 256); }
 
+// Row offsets [F + 1] of a volume family (aliby_features_*3d): first entry 0, non-decreasing, at most 65535 rows per stack (labels
+// are uint16).  A kernel writes row offsets[f] + L - 1 for every label L <= offsets[f + 1] - offsets[f], into scratch sized by
+// offsets[F]: other offsets would put rows past its end.
+static inline bool volume_offsets_ok(const int32_t* offsets, int F) {
+  bool ok = offsets[0] == 0;
+  for (int f = 0; f < F; ++f) ok = ok && offsets[f + 1] >= offsets[f] && offsets[f + 1] - offsets[f] <= 65535;
+  return ok;
+}
+
 // ---------------------------------------------------------------------------
 // device helpers
 // ---------------------------------------------------------------------------

@@ -4,9 +4,9 @@
 // cp_measure is unpinned.  Eight columns per (object, pair), the 2-D family's: Pearson, Slope, Manders_1/2, RWC_1/2, Costes_1/2
 // (definitions: the header of feat_coloc.hip; the arithmetic itself is coloc_stats.h, shared with the 2-D per-pair kernel).
 //
-// Two passes.
-//   1. k_c3_table (volume_table.h): voxel count and bounding box per (stack, label), one read of the labels.  A lane walks 16 voxels of a row and
-//      flushes once per run of equal labels; integer atomics only, so the table is exact whatever the order.
+// Two passes; the first, the split of the rows between the two forms of the second and the kernel's prologue are volume_table.h,
+// shared with feat_texture3d.hip.
+//   1. k_volume_table: voxel count and bounding box per (stack, label), one read of the labels.
 //   2. k_coloc3d: one workgroup of 256 lanes per (object, pair).  The object's voxels of both channels are gathered from its
 //      bounding box in raster order (z, y, x) by order-preserving compaction into two float lists, then each list is copied,
 //      sorted (bitonic) and reduced to its distinct values in place: the dense rank of a value is its index among them (binary
@@ -17,7 +17,7 @@
 // independent of all three (the 2-D kernels size their workgroup by the launch's largest object and are not).
 #include "common.h"
 #include "coloc_stats.h"
-#include "volume_table.h"  // k_c3_table, shared with feat_texture3d.hip
+#include "volume_table.h"
 
 typedef unsigned short u16;
 
@@ -25,22 +25,14 @@ typedef unsigned short u16;
 #define C3_LDS_VOXELS 8192  // power of two (the sort pads to one): 4 lists x 4 bytes x 8192 = 128 KiB of the CU's 160
 #define C3_PER_LANE 4       // voxels of the bounding box per lane and compaction round
 #define C3_MAX_PAIRS 64
-#define C3_GLOBAL_BLOCKS 256
-#define C3_GLOBAL_BYTES (1ull << 30)  // ceiling of the global-scratch form's lists, all workgroups together
 
 namespace {
 
 struct C3Args {
-  const u16* labels;
+  VolumeArgs v;
   const void* pixels;  // [F,C,Z,Y,X]
-  int F, C, Z, Y, X;
-  const int* offsets;       // [F+1]
-  const unsigned* count;    // [n]
-  const unsigned* bmin;     // [n][z, y, x]
-  const unsigned* bmax;     // inclusive
+  int C;
   const int* pairs;         // [n_pairs][2]
-  const int* items;         // GLOBAL: rows of the objects above the LDS budget
-  int n_items;              // GLOBAL: how many; else the number of rows
   int cap;                  // GLOBAL: power of two >= the largest voxel count; else C3_LDS_VOXELS
   unsigned char* gscratch;  // GLOBAL: gridDim.x * gridDim.y lists of cap * 16 bytes
   double* out;
@@ -98,11 +90,11 @@ __global__ __launch_bounds__(C3_BLOCK) void k_coloc3d(C3Args a) {
   float* d2 = d1 + cap;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int ch0 = a.pairs[2 * blockIdx.y], ch1 = a.pairs[2 * blockIdx.y + 1];
-  const size_t vol = (size_t)a.Z * a.Y * a.X;
+  const size_t vol = (size_t)a.v.Z * a.v.Y * a.v.X;
 
-  for (int it = blockIdx.x; it < a.n_items; it += gridDim.x) {
-    const int row = GLOBAL ? a.items[it] : it;
-    const unsigned cnt = a.count[row];
+  for (int it = blockIdx.x; it < a.v.n_items; it += gridDim.x) {
+    const int row = volume_row<GLOBAL>(a.v.items, it);
+    const unsigned cnt = a.v.count[row];
     if (GLOBAL ? cnt > (unsigned)cap : cnt > (unsigned)C3_LDS_VOXELS) continue;  // (the other form's object; uniform)
     double* out = a.out + (size_t)row * a.ld + a.col0 + (size_t)blockIdx.y * a.pair_stride;
     if (cnt == 0) {  // a label without voxels
@@ -114,15 +106,13 @@ __global__ __launch_bounds__(C3_BLOCK) void k_coloc3d(C3Args a) {
       }
       continue;
     }
-    int f = 0, fhi = a.F;  // the stack of this row: offsets[f] <= row < offsets[f + 1]
-    while (fhi - f > 1) { const int mid = (f + fhi) >> 1; if (a.offsets[mid] <= row) f = mid; else fhi = mid; }
-    const u16 L = (u16)(row - a.offsets[f] + 1);
-    const u16* lab = a.labels + (size_t)f * vol;
+    const int f = volume_stack_of(a.v.offsets, a.v.F, row);
+    const u16 L = (u16)(row - a.v.offsets[f] + 1);
+    const u16* lab = a.v.labels + (size_t)f * vol;
     const T* p0 = reinterpret_cast<const T*>(a.pixels) + ((size_t)f * a.C + ch0) * vol;
     const T* p1 = reinterpret_cast<const T*>(a.pixels) + ((size_t)f * a.C + ch1) * vol;
-    const unsigned z0 = a.bmin[(size_t)row * 3], y0 = a.bmin[(size_t)row * 3 + 1], x0 = a.bmin[(size_t)row * 3 + 2];
-    const unsigned h = a.bmax[(size_t)row * 3 + 1] - y0 + 1, w = a.bmax[(size_t)row * 3 + 2] - x0 + 1;
-    const unsigned nbox = (a.bmax[(size_t)row * 3] - z0 + 1) * h * w;  // (a stack holds at most 2^30 voxels)
+    const VolumeBox box = volume_box(a.v.bmin, a.v.bmax, row);
+    const unsigned nbox = box.nbox;
 
     // ---- gather (raster order): C3_PER_LANE consecutive voxels of the box per lane and round -----------------------------
     __syncthreads();  // the previous object's lists are done with
@@ -135,8 +125,7 @@ __global__ __launch_bounds__(C3_BLOCK) void k_coloc3d(C3Args a) {
         const unsigned i = i0 + (unsigned)tid * C3_PER_LANE + k;
         idx[k] = 0;
         if (i < nbox) {
-          const unsigned x = i % w, r = i / w;
-          idx[k] = ((size_t)(z0 + r / h) * a.Y + (y0 + r % h)) * a.X + (x0 + x);
+          idx[k] = box.index(i, a.v.Y, a.v.X);
           if (lab[idx[k]] == L) in |= 1u << k;
         }
       }
@@ -177,11 +166,6 @@ __global__ __launch_bounds__(C3_BLOCK) void k_coloc3d(C3Args a) {
   }
 }
 
-template <typename T, bool GLOBAL>
-void launch_coloc3d(const C3Args& a, dim3 grid, size_t lds, hipStream_t s) {
-  hipLaunchKernelGGL((k_coloc3d<T, GLOBAL>), grid, dim3(C3_BLOCK), lds, s, a);
-}
-
 }  // namespace
 
 extern "C" int aliby_coloc3d_lds_voxels(void) { return C3_LDS_VOXELS; }
@@ -202,88 +186,36 @@ extern "C" int aliby_features_coloc3d(aliby_ctx* ctx, const uint16_t* labels, co
   }
   const int cols[4] = {col_pearson, col_manders, col_rwc, col_costes};
   for (int k = 0; k < 4; ++k) ARG_CHECK(cols[k] < 0 || cols[k] + 2 <= pair_stride, "coloc3d: a metric's columns exceed the pair's block");
-  ARG_CHECK(offsets_host[0] == 0 && col0 >= 0 && pair_stride >= 0 && (long long)col0 + (long long)n_pairs * pair_stride <= ld,
-            "coloc3d: bad offsets / output stride");
-  for (int f = 0; f < F; ++f) ARG_CHECK(offsets_host[f + 1] >= offsets_host[f] && offsets_host[f + 1] - offsets_host[f] <= 65535, "coloc3d: bad offsets");
+  ARG_CHECK(volume_offsets_ok(offsets_host, F), "coloc3d: bad offsets");
+  ARG_CHECK(col0 >= 0 && pair_stride >= 0 && (long long)col0 + (long long)n_pairs * pair_stride <= ld, "coloc3d: bad output stride");
   ARG_CHECK(costes_scale_max > 0.0 && costes_scale_max < 1e300 && thr_percent == thr_percent, "coloc3d: bad thr / scale_max");
   const int n = offsets_host[F];
   if (n <= 0) return ALIBY_OK;
   hipStream_t s = as_stream(stream);
 
-  // scratch: [count n][bmin 3n][bmax 3n][offsets F+1][pairs 2 n_pairs][items n], then (16-byte aligned) the lists of the
-  // global-scratch form.  The table is read back: the host needs the largest count and the rows above the LDS budget.
-  const size_t tab_words = (size_t)n * 7, head_words = tab_words + (size_t)(F + 1) + 2 * (size_t)n_pairs + (size_t)n;
-  const size_t head_bytes = (head_words * 4 + 255) & ~(size_t)255;
-  int rc = aliby_ensure_scratch(ctx, head_bytes);
+  // a row is measured by its voxel count; a workgroup of the global-scratch form holds four lists of the next power of two (the
+  // sort pads to one) of the largest count, and there is one per (grid column, pair); the pairs travel as the plan's extra words
+  VolumePlan plan;
+  const int rc = volume_plan(
+      ctx, labels, F, Z, Y, X, offsets_host, pairs_host, 2 * (size_t)n_pairs, C3_LDS_VOXELS,
+      [](unsigned count, const unsigned*, const unsigned*) { return (size_t)count; },
+      [](size_t max_count) { size_t cap = C3_LDS_VOXELS; while (cap < max_count) cap <<= 1; return cap * 16; }, (size_t)n_pairs, s, &plan, "coloc3d");
   if (rc) return rc;
-  unsigned* count = (unsigned*)ctx->scratch;
-  int* d_off = (int*)(count + tab_words);
-  HIP_TRY(hipMemcpyAsync(d_off, offsets_host, sizeof(int) * (size_t)(F + 1), hipMemcpyHostToDevice, s));
-  rc = volume_table_launch(labels, F, Z, Y, X, d_off, n, count, s);
-  if (rc) return rc;
-  unsigned* table_host = (unsigned*)malloc(sizeof(unsigned) * tab_words + sizeof(int) * (size_t)n);
-  if (!table_host) { aliby_set_error("coloc3d: out of host memory"); return ALIBY_ERR_INVALID; }
-  int* items_host = (int*)(table_host + tab_words);
-  hipError_t e = hipMemcpyAsync(table_host, count, sizeof(unsigned) * tab_words, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess && aliby_wait_stream(s) != ALIBY_OK) e = hipErrorUnknown;
-  if (e != hipSuccess) { free(table_host); aliby_set_error("coloc3d: reading the object table back failed: %s", hipGetErrorString(e)); return ALIBY_ERR_HIP; }
-  unsigned max_count = 0;
-  int n_big = 0;
-  for (int i = 0; i < n; ++i) {
-    max_count = table_host[i] > max_count ? table_host[i] : max_count;
-    if (table_host[i] > C3_LDS_VOXELS) items_host[n_big++] = i;
-  }
-  size_t need = 0;  // bytes of one global-scratch list set
-  int g = 0;
-  if (n_big) {
-    size_t cap = C3_LDS_VOXELS;
-    while (cap < max_count) cap <<= 1;
-    need = cap * 16;
-    size_t blocks = C3_GLOBAL_BYTES / need / (size_t)n_pairs;
-    if (blocks < 1) blocks = 1;
-    g = (int)(blocks < C3_GLOBAL_BLOCKS ? blocks : C3_GLOBAL_BLOCKS);
-    if (g > n_big) g = n_big;
-    void* before = ctx->scratch;
-    rc = aliby_ensure_scratch(ctx, head_bytes + need * (size_t)g * (size_t)n_pairs);
-    if (rc) { free(table_host); return rc; }
-    if (ctx->scratch != before) {  // the block moved: put the table and the offsets back
-      count = (unsigned*)ctx->scratch;
-      d_off = (int*)(count + tab_words);
-      e = hipMemcpyAsync(count, table_host, sizeof(unsigned) * tab_words, hipMemcpyHostToDevice, s);
-      if (e == hipSuccess) e = hipMemcpyAsync(d_off, offsets_host, sizeof(int) * (size_t)(F + 1), hipMemcpyHostToDevice, s);
-    }
-  }
-  int* d_pairs = d_off + (F + 1);
-  int* d_items = d_pairs + 2 * n_pairs;
-  if (e == hipSuccess) e = hipMemcpyAsync(d_pairs, pairs_host, sizeof(int) * 2 * (size_t)n_pairs, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && n_big) e = hipMemcpyAsync(d_items, items_host, sizeof(int) * (size_t)n_big, hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) { free(table_host); aliby_set_error("coloc3d: upload failed: %s", hipGetErrorString(e)); return ALIBY_ERR_HIP; }
 
   C3Args a;
-  a.labels = labels; a.pixels = pixels; a.F = F; a.C = C; a.Z = Z; a.Y = Y; a.X = X; a.offsets = d_off; a.count = count;
-  a.bmin = count + n; a.bmax = count + (size_t)n * 4; a.pairs = d_pairs; a.items = d_items; a.out = out; a.ld = ld; a.col0 = col0;
+  a.v = plan.args; a.pixels = pixels; a.C = C; a.pairs = plan.d_extra; a.out = out; a.ld = ld; a.col0 = col0;
   a.pair_stride = pair_stride; a.col_pearson = col_pearson; a.col_manders = col_manders; a.col_rwc = col_rwc; a.col_costes = col_costes;
   a.thr = thr_percent; a.scale_max = costes_scale_max;
-  if (n_big < n) {  // rows within the LDS budget, absent labels included
-    a.n_items = n; a.cap = C3_LDS_VOXELS; a.gscratch = nullptr;
-    const size_t lds = (size_t)C3_LDS_VOXELS * 16;
-    const void* fn = dtype == ALIBY_U16 ? (const void*)k_coloc3d<u16, false> : (const void*)k_coloc3d<float, false>;
-    e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) {
-      if (dtype == ALIBY_U16) launch_coloc3d<u16, false>(a, dim3(n, n_pairs), lds, s);
-      else launch_coloc3d<float, false>(a, dim3(n, n_pairs), lds, s);
-      e = hipGetLastError();
-    }
+  hipError_t e = hipSuccess;
+  if (plan.n_big < n) {  // rows within the LDS budget, absent labels included; not launched when every row is of the other form
+    a.cap = C3_LDS_VOXELS; a.gscratch = nullptr;
+    e = volume_launch(dtype, k_coloc3d<u16, false>, k_coloc3d<float, false>, a, dim3(n, n_pairs), C3_BLOCK, (size_t)C3_LDS_VOXELS * 16, s);
   }
-  if (e == hipSuccess && n_big) {
-    a.n_items = n_big; a.cap = (int)(need / 16); a.gscratch = (unsigned char*)ctx->scratch + head_bytes;
-    if (dtype == ALIBY_U16) launch_coloc3d<u16, true>(a, dim3(g, n_pairs), 0, s);
-    else launch_coloc3d<float, true>(a, dim3(g, n_pairs), 0, s);
-    e = hipGetLastError();
+  if (e == hipSuccess && plan.n_big) {
+    a.v.n_items = plan.n_big; a.cap = (int)(plan.need / 16); a.gscratch = plan.gscratch;
+    e = volume_launch(dtype, k_coloc3d<u16, true>, k_coloc3d<float, true>, a, dim3(plan.grid_big, n_pairs), C3_BLOCK, 0, s);
   }
-  free(table_host);
   if (e != hipSuccess) { aliby_set_error("coloc3d: kernel launch failed: %s", hipGetErrorString(e)); return ALIBY_ERR_HIP; }
   // the table, offsets and pairs live in ctx scratch: they must be consumed before the host reuses it
-  { const int rcw = aliby_wait_stream(s); if (rcw) return rcw; }
-  return ALIBY_OK;
+  return aliby_wait_stream(s);
 }

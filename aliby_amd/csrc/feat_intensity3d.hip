@@ -110,7 +110,8 @@ extern "C" int aliby_features_intensity3d(aliby_ctx* ctx, const uint16_t* labels
                                           int channel, const int32_t* offsets_host, double* out, int ld, int col0, void* stream) {
   ARG_CHECK(ctx && labels && pixels && offsets_host && out, "intensity3d: null argument");
   ARG_CHECK(F > 0 && C > 0 && Z > 0 && Y > 0 && X > 0 && channel >= 0 && channel < C, "intensity3d: bad shape");
-  ARG_CHECK(offsets_host[0] == 0 && col0 >= 0 && ld >= col0 + 12, "intensity3d: bad offsets / output stride");
+  ARG_CHECK(volume_offsets_ok(offsets_host, F), "intensity3d: bad offsets");  // (else labelled voxels would write past the accumulators)
+  ARG_CHECK(col0 >= 0 && ld >= col0 + 12, "intensity3d: bad output stride");
   // (x, y, z < 65536 and at most 2^32 voxels per object keep every sum below 2^63)
   ARG_CHECK(X <= 65536 && Y <= 65536 && Z <= 65536 && (size_t)Z * Y * X <= (1ull << 32), "intensity3d: stack too large for exact 64-bit sums");
   const int n = offsets_host[F];

@@ -220,7 +220,8 @@ extern "C" int aliby_features_sizeshape3d(aliby_ctx* ctx, const uint16_t* labels
                                           const double* spacing, double* out, int ld, int col0, void* stream) {
   ARG_CHECK(ctx && labels && offsets_host && spacing && out, "sizeshape3d: null argument");
   ARG_CHECK(F > 0 && Z > 0 && Y > 0 && X > 0, "sizeshape3d: bad shape");
-  ARG_CHECK(offsets_host[0] == 0 && col0 >= 0 && ld >= col0 + S3_COLS, "sizeshape3d: bad offsets / output stride");
+  ARG_CHECK(volume_offsets_ok(offsets_host, F), "sizeshape3d: bad offsets");  // (else labelled voxels would write past the accumulators)
+  ARG_CHECK(col0 >= 0 && ld >= col0 + S3_COLS, "sizeshape3d: bad output stride");
   ARG_CHECK(spacing[0] > 0.0 && spacing[1] > 0.0 && spacing[2] > 0.0 && spacing[0] < 1e300 && spacing[1] < 1e300 && spacing[2] < 1e300,
             "sizeshape3d: spacing must be positive and finite");
   // (see the bounds at the top of the file)

@@ -13,8 +13,9 @@
 // place the kernel knows the order:
 //   (1,0,0) (1,1,0) (0,1,0) (1,-1,0) (0,0,1) (1,0,1) (0,1,1) (1,1,1) (1,-1,1) (1,0,-1) (0,1,-1) (1,1,-1) (1,-1,-1)
 //
-// Two passes.
-//   1. k_c3_table (volume_table.h): voxel count and bounding box per (stack, label), one read of the labels.
+// Two passes; the first, the split of the rows between the two forms of the second and the kernel's prologue are volume_table.h,
+// shared with feat_coloc3d.hip.
+//   1. k_volume_table: voxel count and bounding box per (stack, label), one read of the labels.
 //   2. k_texture3d: one workgroup of 256 lanes per object.  The byte crop of the box is built once; the present grey levels are
 //      renumbered 0 .. K-1 through a 256-bit presence mask; per direction the K (K + 1) / 2 cells of the symmetric matrix are
 //      counted with integer atomics on 32-bit counters (a volume object has tens of thousands of pairs per direction: the 2-D
@@ -35,8 +36,6 @@ typedef unsigned short u16;
 #define T3_NDIR 13
 #define T3_LDS_VOXELS 24576                // bytes of the crop in LDS = voxels of the largest bounding box of the LDS form
 #define T3_MAX_CELLS (255 * 256 / 2 + 256)  // K (K + 1) / 2 at K = 255, rounded up to 32896: 128.5 KiB of counters
-#define T3_GLOBAL_BLOCKS 256
-#define T3_GLOBAL_BYTES (1ull << 30)  // ceiling of the global-scratch form's crops and counters, all workgroups together
 
 namespace {
 
@@ -44,15 +43,9 @@ __device__ const int T3_DIRS[T3_NDIR][3] = {{1, 0, 0}, {1, 1, 0}, {0, 1, 0}, {1,
                                             {1, 1, 1}, {1, -1, 1}, {1, 0, -1}, {0, 1, -1}, {1, 1, -1}, {1, -1, -1}};
 
 struct T3Args {
-  const u16* labels;
+  VolumeArgs v;        // (items: the rows whose box is above the LDS budget)
   const void* pixels;  // [F,C,Z,Y,X]
-  int F, C, Z, Y, X, channel;
-  const int* offsets;       // [F+1]
-  const unsigned* count;    // [n]
-  const unsigned* bmin;     // [n][z, y, x]
-  const unsigned* bmax;     // inclusive
-  const int* items;         // GLOBAL: rows of the objects whose box is above the LDS budget
-  int n_items;              // GLOBAL: how many; else the number of rows
+  int C, channel;
   unsigned cap;             // GLOBAL: bytes of a crop (multiple of 16) >= the largest box; else T3_LDS_VOXELS
   unsigned char* gscratch;  // GLOBAL: gridDim.x x (cap + 4 T3_MAX_CELLS) bytes
   int scale, gray_levels;
@@ -76,23 +69,22 @@ __global__ __launch_bounds__(T3_BLOCK) void k_texture3d(T3Args a) {
   unsigned char* g = GLOBAL ? (a.gscratch + (size_t)blockIdx.x * ((size_t)cap + 4 * (size_t)T3_MAX_CELLS)) : lds_raw;
   unsigned int* cells = reinterpret_cast<unsigned int*>(g + cap);
   const int tid = threadIdx.x;
-  const size_t vol = (size_t)a.Z * a.Y * a.X;
+  const size_t vol = (size_t)a.v.Z * a.v.Y * a.v.X;
 
-  for (int it = blockIdx.x; it < a.n_items; it += gridDim.x) {
-    const int row = GLOBAL ? a.items[it] : it;
+  for (int it = blockIdx.x; it < a.v.n_items; it += gridDim.x) {
+    const int row = volume_row<GLOBAL>(a.v.items, it);
     double* out = a.out + (size_t)row * a.ld + a.col0;
-    if (a.count[row] == 0) {  // a label without voxels
+    if (a.v.count[row] == 0) {  // a label without voxels
       for (int k = tid; k < T3_NDIR * TX_NSTAT; k += T3_BLOCK) out[k] = NAN;
       continue;
     }
-    const unsigned z0 = a.bmin[(size_t)row * 3], y0 = a.bmin[(size_t)row * 3 + 1], x0 = a.bmin[(size_t)row * 3 + 2];
-    const int dd = (int)(a.bmax[(size_t)row * 3] - z0 + 1), h = (int)(a.bmax[(size_t)row * 3 + 1] - y0 + 1), w = (int)(a.bmax[(size_t)row * 3 + 2] - x0 + 1);
-    const unsigned nbox = (unsigned)dd * (unsigned)h * (unsigned)w;  // (a stack holds at most 2^30 voxels)
+    const VolumeBox box = volume_box(a.v.bmin, a.v.bmax, row);
+    const int dd = (int)box.d, h = (int)box.h, w = (int)box.w;
+    const unsigned nbox = box.nbox;
     if (GLOBAL ? nbox > cap : nbox > (unsigned)T3_LDS_VOXELS) continue;  // (the other form's object; uniform)
-    int f = 0, fhi = a.F;  // the stack of this row: offsets[f] <= row < offsets[f + 1]
-    while (fhi - f > 1) { const int mid = (f + fhi) >> 1; if (a.offsets[mid] <= row) f = mid; else fhi = mid; }
-    const u16 L = (u16)(row - a.offsets[f] + 1);
-    const u16* lab = a.labels + (size_t)f * vol;
+    const int f = volume_stack_of(a.v.offsets, a.v.F, row);
+    const u16 L = (u16)(row - a.v.offsets[f] + 1);
+    const u16* lab = a.v.labels + (size_t)f * vol;
     const T* px = reinterpret_cast<const T*>(a.pixels) + ((size_t)f * a.C + a.channel) * vol;
 
     // ---- byte crop of the box, raster order (z, y, x); four voxels' loads are issued together ----------------------------
@@ -104,8 +96,7 @@ __global__ __launch_bounds__(T3_BLOCK) void k_texture3d(T3Args a) {
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const unsigned i = min(i0 + (unsigned)u * T3_BLOCK, nbox - 1);
-        const unsigned x = i % (unsigned)w, r = i / (unsigned)w;
-        const size_t idx = ((size_t)(z0 + r / (unsigned)h) * a.Y + (y0 + r % (unsigned)h)) * a.X + (x0 + x);
+        const size_t idx = box.index(i, a.v.Y, a.v.X);
         lb[u] = lab[idx];
         pv[u] = px[idx];
       }
@@ -204,11 +195,6 @@ __global__ __launch_bounds__(T3_BLOCK) void k_texture3d(T3Args a) {
   }
 }
 
-template <typename T, bool GLOBAL>
-void launch_texture3d(const T3Args& a, int grid, size_t lds, hipStream_t s) {
-  hipLaunchKernelGGL((k_texture3d<T, GLOBAL>), dim3(grid), dim3(T3_BLOCK), lds, s, a);
-}
-
 }  // namespace
 
 extern "C" int aliby_texture3d_lds_voxels(void) { return T3_LDS_VOXELS; }
@@ -222,86 +208,37 @@ extern "C" int aliby_features_texture3d(aliby_ctx* ctx, const uint16_t* labels, 
   ARG_CHECK(X <= 65536 && Y <= 65536 && Z <= 65536 && (size_t)Z * Y * X <= (1ull << 30), "texture3d: stack too large");
   ARG_CHECK(channel >= 0 && channel < C, "texture3d: channel out of range");
   ARG_CHECK(scale >= 1 && gray_levels >= 2 && gray_levels <= 256, "texture3d: scale >= 1 and 2 <= gray_levels <= 256");
-  ARG_CHECK(offsets_host[0] == 0 && col0 >= 0 && (long long)col0 + T3_NDIR * TX_NSTAT <= ld, "texture3d: bad offsets / output stride");
-  for (int f = 0; f < F; ++f) ARG_CHECK(offsets_host[f + 1] >= offsets_host[f] && offsets_host[f + 1] - offsets_host[f] <= 65535, "texture3d: bad offsets");
+  ARG_CHECK(volume_offsets_ok(offsets_host, F), "texture3d: bad offsets");
+  ARG_CHECK(col0 >= 0 && (long long)col0 + T3_NDIR * TX_NSTAT <= ld, "texture3d: bad output stride");
   const int n = offsets_host[F];
   if (n <= 0) return ALIBY_OK;
   hipStream_t s = as_stream(stream);
   { const int rcl = haralick_log2_table_ready(ctx, s); if (rcl) return rcl; }
 
-  // scratch: [count n][bmin 3n][bmax 3n][offsets F+1][items n], then (256-byte aligned) the crops and counters of the
-  // global-scratch form.  The table is read back: the host needs the rows whose box is above the LDS budget, and the largest.
-  const size_t tab_words = (size_t)n * 7, head_words = tab_words + (size_t)(F + 1) + (size_t)n;
-  const size_t head_bytes = (head_words * 4 + 255) & ~(size_t)255;
-  int rc = aliby_ensure_scratch(ctx, head_bytes);
+  // a row is measured by the volume of its box (an absent label: 0); a workgroup of the global-scratch form holds the crop of the
+  // largest box, rounded up to 16 bytes, and the counters
+  VolumePlan plan;
+  const int rc = volume_plan(
+      ctx, labels, F, Z, Y, X, offsets_host, nullptr, 0, T3_LDS_VOXELS,
+      [](unsigned count, const unsigned* lo, const unsigned* hi) {
+        return count ? (size_t)(hi[0] - lo[0] + 1) * (hi[1] - lo[1] + 1) * (hi[2] - lo[2] + 1) : (size_t)0;
+      },
+      [](size_t max_box) { return ((max_box + 15) & ~(size_t)15) + 4 * (size_t)T3_MAX_CELLS; }, 1, s, &plan, "texture3d");
   if (rc) return rc;
-  unsigned* count = (unsigned*)ctx->scratch;
-  int* d_off = (int*)(count + tab_words);
-  HIP_TRY(hipMemcpyAsync(d_off, offsets_host, sizeof(int) * (size_t)(F + 1), hipMemcpyHostToDevice, s));
-  rc = volume_table_launch(labels, F, Z, Y, X, d_off, n, count, s);
-  if (rc) return rc;
-  unsigned* table_host = (unsigned*)malloc(sizeof(unsigned) * tab_words + sizeof(int) * (size_t)n);
-  if (!table_host) { aliby_set_error("texture3d: out of host memory"); return ALIBY_ERR_INVALID; }
-  int* items_host = (int*)(table_host + tab_words);
-  hipError_t e = hipMemcpyAsync(table_host, count, sizeof(unsigned) * tab_words, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess && aliby_wait_stream(s) != ALIBY_OK) e = hipErrorUnknown;
-  if (e != hipSuccess) { free(table_host); aliby_set_error("texture3d: reading the object table back failed: %s", hipGetErrorString(e)); return ALIBY_ERR_HIP; }
-  const unsigned* bmin = table_host + n;
-  const unsigned* bmax = table_host + (size_t)n * 4;
-  size_t max_box = 0;
-  int n_big = 0;
-  for (int i = 0; i < n; ++i) {
-    if (!table_host[i]) continue;
-    const size_t box = (size_t)(bmax[3 * i] - bmin[3 * i] + 1) * (bmax[3 * i + 1] - bmin[3 * i + 1] + 1) * (bmax[3 * i + 2] - bmin[3 * i + 2] + 1);
-    if (box > T3_LDS_VOXELS) { items_host[n_big++] = i; max_box = box > max_box ? box : max_box; }
-  }
-  size_t need = 0;  // bytes of one workgroup's crop and counters in global scratch
-  int g = 0;
-  if (n_big) {
-    const size_t cap = (max_box + 15) & ~(size_t)15;
-    need = cap + 4 * (size_t)T3_MAX_CELLS;
-    size_t blocks = T3_GLOBAL_BYTES / need;
-    if (blocks < 1) blocks = 1;
-    g = (int)(blocks < T3_GLOBAL_BLOCKS ? blocks : T3_GLOBAL_BLOCKS);
-    if (g > n_big) g = n_big;
-    void* before = ctx->scratch;
-    rc = aliby_ensure_scratch(ctx, head_bytes + need * (size_t)g);
-    if (rc) { free(table_host); return rc; }
-    if (ctx->scratch != before) {  // the block moved: put the table and the offsets back
-      count = (unsigned*)ctx->scratch;
-      d_off = (int*)(count + tab_words);
-      e = hipMemcpyAsync(count, table_host, sizeof(unsigned) * tab_words, hipMemcpyHostToDevice, s);
-      if (e == hipSuccess) e = hipMemcpyAsync(d_off, offsets_host, sizeof(int) * (size_t)(F + 1), hipMemcpyHostToDevice, s);
-    }
-  }
-  int* d_items = d_off + (F + 1);
-  if (e == hipSuccess && n_big) e = hipMemcpyAsync(d_items, items_host, sizeof(int) * (size_t)n_big, hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) { free(table_host); aliby_set_error("texture3d: upload failed: %s", hipGetErrorString(e)); return ALIBY_ERR_HIP; }
 
   T3Args a;
-  a.labels = labels; a.pixels = pixels; a.F = F; a.C = C; a.Z = Z; a.Y = Y; a.X = X; a.channel = channel; a.offsets = d_off; a.count = count;
-  a.bmin = count + n; a.bmax = count + (size_t)n * 4; a.items = d_items; a.scale = scale; a.gray_levels = gray_levels; a.out = out; a.ld = ld;
+  a.v = plan.args; a.pixels = pixels; a.C = C; a.channel = channel; a.scale = scale; a.gray_levels = gray_levels; a.out = out; a.ld = ld;
   a.col0 = col0;
-  {  // rows within the LDS budget, absent labels included (a row of the other form is skipped by its workgroup at once)
-    a.n_items = n; a.cap = T3_LDS_VOXELS; a.gscratch = nullptr;
-    const size_t lds = (size_t)T3_LDS_VOXELS + 4 * (size_t)T3_MAX_CELLS;
-    const void* fn = dtype == ALIBY_U16 ? (const void*)k_texture3d<u16, false> : (const void*)k_texture3d<float, false>;
-    e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) {
-      if (dtype == ALIBY_U16) launch_texture3d<u16, false>(a, n, lds, s);
-      else launch_texture3d<float, false>(a, n, lds, s);
-      e = hipGetLastError();
-    }
+  // rows within the LDS budget, absent labels included.  Launched even when every row is of the other form (coloc3d skips it then):
+  // its workgroup skips such a row at once
+  a.cap = T3_LDS_VOXELS; a.gscratch = nullptr;
+  hipError_t e = volume_launch(dtype, k_texture3d<u16, false>, k_texture3d<float, false>, a, dim3(n), T3_BLOCK,
+                               (size_t)T3_LDS_VOXELS + 4 * (size_t)T3_MAX_CELLS, s);
+  if (e == hipSuccess && plan.n_big) {
+    a.v.n_items = plan.n_big; a.cap = (unsigned)(plan.need - 4 * (size_t)T3_MAX_CELLS); a.gscratch = plan.gscratch;
+    e = volume_launch(dtype, k_texture3d<u16, true>, k_texture3d<float, true>, a, dim3(plan.grid_big), T3_BLOCK, 0, s);
   }
-  if (e == hipSuccess && n_big) {
-    a.n_items = n_big; a.cap = (unsigned)(need - 4 * (size_t)T3_MAX_CELLS); a.gscratch = (unsigned char*)ctx->scratch + head_bytes;
-    if (dtype == ALIBY_U16) launch_texture3d<u16, true>(a, g, 0, s);
-    else launch_texture3d<float, true>(a, g, 0, s);
-    e = hipGetLastError();
-  }
-  free(table_host);
   if (e != hipSuccess) { aliby_set_error("texture3d: kernel launch failed: %s", hipGetErrorString(e)); return ALIBY_ERR_HIP; }
   // the table and the offsets live in ctx scratch: they must be consumed before the host reuses it
-  { const int rcw = aliby_wait_stream(s); if (rcw) return rcw; }
-  return ALIBY_OK;
+  return aliby_wait_stream(s);
 }

@@ -1,15 +1,22 @@
-// volume_table.h — the object table of volume labels [F, Z, Y, X]: voxel count and bounding box per (stack, label), one read of
-// the labels.  Shared by the per-object volume kernels that start from it (feat_coloc3d.hip, feat_texture3d.hip).  A lane walks
-// 16 voxels of a row and flushes once per run of equal labels; integer atomics only, so the table is exact whatever the order.
+// volume_table.h — the front end of the per-object kernels on volume labels [F, Z, Y, X] (feat_coloc3d.hip, feat_texture3d.hip):
+// the object table (k_volume_table: voxel count and bounding box per (stack, label), one read of the labels), the host's plan
+// around it (volume_plan), the arguments and the prologue every such kernel opens with, and the launch of a <dtype, GLOBAL> kernel.
 #pragma once
+#include <algorithm>
+#include <memory>
+#include <new>
 #include "common.h"
 
 #ifdef __HIPCC__
+#define VOLUME_GLOBAL_BLOCKS 256             // workgroups of the global-scratch form, at most
+#define VOLUME_GLOBAL_BYTES (1ull << 30)     // ceiling of their working sets, all workgroups together
+
 namespace {
 
-// labels [F, Z, Y, X]; offsets[f] = first row of stack f; row = offsets[f] + label - 1; bmin / bmax [row][z, y, x]
-__global__ __launch_bounds__(256) void k_c3_table(const uint16_t* __restrict__ labels, int F, int Z, int Y, int X, const int* __restrict__ offsets,
-                                                  unsigned* __restrict__ count, unsigned* __restrict__ bmin, unsigned* __restrict__ bmax) {
+// labels [F, Z, Y, X]; offsets[f] = first row of stack f; row = offsets[f] + label - 1; bmin / bmax [row][z, y, x].  A lane walks
+// 16 voxels of a row and flushes once per run of equal labels; integer atomics only, so the table is exact whatever the order.
+__global__ __launch_bounds__(256) void k_volume_table(const uint16_t* __restrict__ labels, int F, int Z, int Y, int X, const int* __restrict__ offsets,
+                                                      unsigned* __restrict__ count, unsigned* __restrict__ bmin, unsigned* __restrict__ bmax) {
   const size_t vol = (size_t)Z * Y * X;
   const int segs = (X + 15) / 16;
   const size_t total = (size_t)F * Z * Y * segs;
@@ -45,11 +52,127 @@ inline int volume_table_launch(const uint16_t* labels, int F, int Z, int Y, int 
   HIP_TRY(hipMemsetAsync(table, 0, sizeof(unsigned) * (size_t)n, s));
   HIP_TRY(hipMemsetAsync(table + n, 0xFF, sizeof(unsigned) * (size_t)n * 3, s));
   HIP_TRY(hipMemsetAsync(table + (size_t)n * 4, 0, sizeof(unsigned) * (size_t)n * 3, s));
-  const size_t total = (size_t)F * Z * Y * ((X + 15) / 16);
-  const unsigned grid = (unsigned)((total + 255) / 256 < 32768 ? (total + 255) / 256 : 32768);
-  hipLaunchKernelGGL(k_c3_table, dim3(grid), dim3(256), 0, s, labels, F, Z, Y, X, offsets_dev, table, table + n, table + (size_t)n * 4);
+  const size_t blocks = ((size_t)F * Z * Y * ((X + 15) / 16) + 255) / 256;
+  hipLaunchKernelGGL(k_volume_table, dim3((unsigned)(blocks < 32768 ? blocks : 32768)), dim3(256), 0, s, labels, F, Z, Y, X, offsets_dev, table, table + n, table + (size_t)n * 4);
   KERNEL_CHECK();
   return ALIBY_OK;
+}
+
+// What every per-object kernel is handed.  The LDS form (GLOBAL = false) walks all n rows and skips those of the other form; the
+// global-scratch form walks items[0 .. n_items).
+struct VolumeArgs {
+  const uint16_t* labels;
+  int F, Z, Y, X;
+  const int* offsets;     // [F+1]
+  const unsigned* count;  // [n]
+  const unsigned* bmin;   // [n][z, y, x]
+  const unsigned* bmax;   // inclusive
+  const int* items;       // GLOBAL: rows of the objects above the LDS budget
+  int n_items;            // GLOBAL: how many; else the number of rows
+};
+
+// (The helpers take the fields they read: a reference to the by-value kernel argument costs k_coloc3d registers.)
+template <bool GLOBAL>
+__device__ __forceinline__ int volume_row(const int* items, int it) { return GLOBAL ? items[it] : it; }
+
+// the stack of a row: offsets[f] <= row < offsets[f + 1]; its label there is row - offsets[f] + 1
+__device__ __forceinline__ int volume_stack_of(const int* offsets, int F, int row) {
+  int f = 0, fhi = F;
+  while (fhi - f > 1) { const int mid = (f + fhi) >> 1; if (offsets[mid] <= row) f = mid; else fhi = mid; }
+  return f;
+}
+
+// the bounding box of a row with voxels; voxel i of it in raster order (z, y, x) as an index into the stack
+struct VolumeBox {
+  unsigned z0, y0, x0, d, h, w, nbox;  // (a stack holds at most 2^30 voxels)
+  __device__ __forceinline__ size_t index(unsigned i, int Y, int X) const {
+    const unsigned x = i % w, r = i / w;
+    return ((size_t)(z0 + r / h) * Y + (y0 + r % h)) * X + (x0 + x);
+  }
+};
+__device__ __forceinline__ VolumeBox volume_box(const unsigned* bmin, const unsigned* bmax, int row) {
+  VolumeBox b;
+  b.z0 = bmin[(size_t)row * 3]; b.y0 = bmin[(size_t)row * 3 + 1]; b.x0 = bmin[(size_t)row * 3 + 2];
+  b.d = bmax[(size_t)row * 3] - b.z0 + 1; b.h = bmax[(size_t)row * 3 + 1] - b.y0 + 1; b.w = bmax[(size_t)row * 3 + 2] - b.x0 + 1;
+  b.nbox = b.d * b.h * b.w;
+  return b;
+}
+
+struct VolumePlan {
+  VolumeArgs args;          // labels, shape, table, offsets and items on the device; n_items = n (the LDS form's)
+  int* d_extra;             // the family's extra words on the device
+  int n, n_big, grid_big;   // rows; rows of the global-scratch form; its workgroups (x per_block_mult)
+  size_t need;              // bytes of one of its workgroups' working set
+  unsigned char* gscratch;  // grid_big * per_block_mult * need bytes
+  std::unique_ptr<unsigned[]> host;  // the table as read back and the item list: lives as long as the plan, whatever the exit
+};
+
+// size_of_row(count, bmin[3], bmax[3]) = what a row is measured by against lds_limit; bytes_for(largest such measure above the
+// limit) = one workgroup's bytes in global scratch; per_block_mult = workgroups per grid column.  Scratch: [count n][bmin 3n]
+// [bmax 3n][offsets F+1][extra][items n], then (256-byte aligned) the global-scratch form's working sets.  Needs offsets_host[F] > 0.
+template <class SizeOf, class BytesFor>
+int volume_plan(aliby_ctx* ctx, const uint16_t* labels, int F, int Z, int Y, int X, const int32_t* offsets_host, const int32_t* extra_host,
+                size_t extra_words, size_t lds_limit, SizeOf size_of_row, BytesFor bytes_for, size_t per_block_mult, hipStream_t s, VolumePlan* p,
+                const char* who) {
+  const int n = offsets_host[F];
+  const size_t tab_words = (size_t)n * 7, off_bytes = sizeof(int) * (size_t)(F + 1);
+  const size_t head_bytes = ((tab_words + (size_t)(F + 1) + extra_words + (size_t)n) * 4 + 255) & ~(size_t)255;
+  int rc = aliby_ensure_scratch(ctx, head_bytes);
+  if (rc) return rc;
+  unsigned* table = (unsigned*)ctx->scratch;
+  HIP_TRY(hipMemcpyAsync(table + tab_words, offsets_host, off_bytes, hipMemcpyHostToDevice, s));
+  rc = volume_table_launch(labels, F, Z, Y, X, (const int*)(table + tab_words), n, table, s);
+  if (rc) return rc;
+  // the table is read back: the host needs the rows above the LDS budget, and the largest
+  p->host.reset(new (std::nothrow) unsigned[tab_words + (size_t)n]);
+  if (!p->host) { aliby_set_error("%s: out of host memory", who); return ALIBY_ERR_INVALID; }
+  unsigned* table_host = p->host.get();
+  int* items_host = (int*)(table_host + tab_words);
+  hipError_t e = hipMemcpyAsync(table_host, table, sizeof(unsigned) * tab_words, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && aliby_wait_stream(s) != ALIBY_OK) e = hipErrorUnknown;
+  if (e != hipSuccess) { aliby_set_error("%s: reading the object table back failed: %s", who, hipGetErrorString(e)); return ALIBY_ERR_HIP; }
+  size_t max_big = 0;
+  p->n_big = 0;
+  for (int i = 0; i < n; ++i) {
+    const size_t size = size_of_row(table_host[i], table_host + n + 3 * (size_t)i, table_host + 4 * (size_t)n + 3 * (size_t)i);
+    if (size > lds_limit) { items_host[p->n_big++] = i; max_big = size > max_big ? size : max_big; }
+  }
+  p->need = 0, p->grid_big = 0;
+  if (p->n_big) {
+    p->need = bytes_for(max_big);
+    const size_t fit = VOLUME_GLOBAL_BYTES / p->need / per_block_mult;
+    p->grid_big = (int)std::min<size_t>({fit > 0 ? fit : 1, VOLUME_GLOBAL_BLOCKS, (size_t)p->n_big});
+    void* before = ctx->scratch;
+    rc = aliby_ensure_scratch(ctx, head_bytes + p->need * (size_t)p->grid_big * per_block_mult);
+    if (rc) return rc;
+    if (ctx->scratch != before) {  // the block moved: put the table and the offsets back
+      table = (unsigned*)ctx->scratch;
+      e = hipMemcpyAsync(table, table_host, sizeof(unsigned) * tab_words, hipMemcpyHostToDevice, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(table + tab_words, offsets_host, off_bytes, hipMemcpyHostToDevice, s);
+    }
+  }
+  int* d_off = (int*)(table + tab_words);
+  p->d_extra = d_off + (F + 1);
+  int* d_items = p->d_extra + extra_words;
+  if (e == hipSuccess && extra_words) e = hipMemcpyAsync(p->d_extra, extra_host, sizeof(int) * extra_words, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && p->n_big) e = hipMemcpyAsync(d_items, items_host, sizeof(int) * (size_t)p->n_big, hipMemcpyHostToDevice, s);
+  if (e != hipSuccess) { aliby_set_error("%s: upload failed: %s", who, hipGetErrorString(e)); return ALIBY_ERR_HIP; }
+  p->n = n;
+  p->gscratch = (unsigned char*)ctx->scratch + head_bytes;
+  p->args = VolumeArgs{labels, F, Z, Y, X, d_off, table, table + n, table + (size_t)n * 4, d_items, n};
+  return ALIBY_OK;
+}
+
+// one launch of a per-object kernel, k_u16 / k_f32 = its two pixel types at one GLOBAL; lds = dynamic LDS bytes (0: none)
+template <class Args>
+hipError_t volume_launch(int dtype, void (*k_u16)(Args), void (*k_f32)(Args), const Args& a, dim3 grid, unsigned block, size_t lds, hipStream_t s) {
+  void (*k)(Args) = dtype == ALIBY_U16 ? k_u16 : k_f32;
+  if (lds) {
+    const hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(k, grid, dim3(block), lds, s, a);
+  return hipGetLastError();
 }
 
 }  // namespace

@@ -315,13 +315,38 @@ class FeatureEngine:
                                                    _stream_ptr()))
         return out.permute(1, 0, 2, 3).contiguous(), mx
 
+    @staticmethod
+    def _volume_offsets(who: str, F: int, counts) -> np.ndarray:
+        """counts [F] -> row offsets int32 [F + 1] of a volume method, as the C entries demand them (volume_offsets_ok)."""
+        cnt = np.asarray(counts, np.int64).reshape(-1)
+        if cnt.shape != (F,) or (cnt < 0).any() or (cnt > 65535).any():
+            raise ValueError(f"{who}: counts must hold one label count (0..65535) per stack ({F}), got {counts!r}")
+        offsets = np.zeros(F + 1, np.int32)
+        np.cumsum(cnt, out=offsets[1:])
+        return offsets
+
+    @staticmethod
+    def _volume_inputs(who: str, volume, pixels, counts):
+        """Checks (volume uint16 [F,Z,Y,X], pixels uint16 or float32 [F,C,Z,Y,X], counts [F]) of a volume method -> F, C, Z, Y, X, offsets."""
+        if not (isinstance(volume, torch.Tensor) and isinstance(pixels, torch.Tensor)):
+            raise TypeError(f"{who} takes torch tensors on the device")
+        if volume.dtype != torch.uint16:
+            raise TypeError(f"{who}: volume labels must be uint16, got {volume.dtype}")
+        if pixels.dtype not in (torch.uint16, torch.float32):
+            raise TypeError(f"{who}: pixels must be uint16 or float32, got {pixels.dtype}")
+        if volume.dim() != 4 or pixels.dim() != 5 or tuple(pixels.shape[:1]) != tuple(volume.shape[:1]) or tuple(pixels.shape[2:]) != tuple(volume.shape[1:]):
+            raise ValueError(f"{who}: volume must be [F,Z,Y,X] and pixels [F,C,Z,Y,X], got {tuple(volume.shape)} and {tuple(pixels.shape)}")
+        if not (volume.is_cuda and pixels.is_cuda):
+            raise ValueError(f"{who} takes tensors on the device")
+        F, Z, Y, X = volume.shape
+        return F, int(pixels.shape[1]), Z, Y, X, FeatureEngine._volume_offsets(who, F, counts)
+
     def intensity3d(self, volume: torch.Tensor, pixels: torch.Tensor, channel: int, counts) -> torch.Tensor:
         """Volume labels uint16 [F,Z,Y,X] (1..counts[f] per stack), pixels uint16 [F,C,Z,Y,X] -> float64 [sum counts, 12]
         (features.intensity3d_names(); aliby_features_intensity3d).  Rows in (stack, label) order."""
         F, Z, Y, X = volume.shape
         assert pixels.dtype == torch.uint16 and tuple(pixels.shape[:1]) == (F,) and tuple(pixels.shape[2:]) == (Z, Y, X)
-        offsets = np.zeros(F + 1, np.int32)
-        np.cumsum(np.asarray(counts, np.int32), out=offsets[1:])
+        offsets = self._volume_offsets("intensity3d", F, counts)
         out = self.new_output(int(offsets[-1]), 12)
         if int(offsets[-1]) == 0:
             return out  # stacks without any object: an empty block (found by tests/fuzz/fuzz_volume.py — the C entry refuses a NULL output)
@@ -337,12 +362,10 @@ class FeatureEngine:
         1..counts[f] without voxels gets Volume 0 and NaN elsewhere, as in intensity3d."""
         assert volume.dtype == torch.uint16 and volume.dim() == 4 and volume.is_cuda
         F, Z, Y, X = volume.shape
-        assert len(counts) == F
         sp = np.ascontiguousarray(np.asarray(spacing, np.float64).reshape(3))
         if not (np.isfinite(sp).all() and (sp > 0).all()):
             raise ValueError(f"spacing must be three positive finite numbers (dz, dy, dx), got {spacing!r}")
-        offsets = np.zeros(F + 1, np.int32)
-        np.cumsum(np.asarray(counts, np.int32), out=offsets[1:])
+        offsets = self._volume_offsets("sizeshape3d", F, counts)
         out = self.new_output(int(offsets[-1]), 19)
         if int(offsets[-1]) == 0:
             return out  # stacks without any object: an empty block
@@ -362,32 +385,16 @@ class FeatureEngine:
         -> float64 [sum counts, 2 * len(metrics) * len(pairs)] (features.coloc3d_names(pairs, metrics); aliby_features_coloc3d):
         the 2-D colocalisation metrics over each object's voxels.  Rows in (stack, label) order, columns pair-major in the order
         of `pairs` and `metrics`.  A label of 1..counts[f] without voxels gets a row of NaN.  Bitwise independent of run and batch."""
-        if not (isinstance(volume, torch.Tensor) and isinstance(pixels, torch.Tensor)):
-            raise TypeError("coloc3d takes torch tensors on the device")
-        if volume.dtype != torch.uint16:
-            raise TypeError(f"volume labels must be uint16, got {volume.dtype}")
-        if pixels.dtype not in (torch.uint16, torch.float32):
-            raise TypeError(f"pixels must be uint16 or float32, got {pixels.dtype}")
-        if volume.dim() != 4 or pixels.dim() != 5 or tuple(pixels.shape[:1]) != tuple(volume.shape[:1]) or tuple(pixels.shape[2:]) != tuple(volume.shape[1:]):
-            raise ValueError(f"volume must be [F,Z,Y,X] and pixels [F,C,Z,Y,X], got {tuple(volume.shape)} and {tuple(pixels.shape)}")
-        if not (volume.is_cuda and pixels.is_cuda):
-            raise ValueError("coloc3d takes tensors on the device")
-        F, Z, Y, X = volume.shape
-        Cn = int(pixels.shape[1])
+        F, Cn, Z, Y, X, offsets = self._volume_inputs("coloc3d", volume, pixels, counts)
         names = feat.coloc3d_names(pairs, metrics)  # (refuses unknown or repeated metrics and malformed pairs)
         pr = np.ascontiguousarray(np.asarray([(int(a), int(b)) for a, b in pairs], np.int32).reshape(-1, 2))
         if len(pr) == 0 or len(pr) > 64:
             raise ValueError(f"coloc3d takes between 1 and 64 channel pairs per call, got {len(pr)}")
         if ((pr < 0) | (pr >= Cn)).any():
             raise ValueError(f"channel out of range for {Cn} channels: {pairs!r}")
-        cnt = np.asarray(counts, np.int64).reshape(-1)
-        if cnt.shape != (F,) or (cnt < 0).any() or (cnt > 65535).any():
-            raise ValueError(f"counts must hold one label count (0..65535) per stack ({F}), got {counts!r}")
         thr, scale_max = float(thr), float(scale_max)
         if not (np.isfinite(thr) and np.isfinite(scale_max) and scale_max > 0):
             raise ValueError(f"thr must be finite and scale_max positive and finite, got {thr!r}, {scale_max!r}")
-        offsets = np.zeros(F + 1, np.int32)
-        np.cumsum(cnt, out=offsets[1:])
         stride = 2 * len(metrics)
         out = self.new_output(int(offsets[-1]), len(names))
         if int(offsets[-1]) == 0:
@@ -410,18 +417,7 @@ class FeatureEngine:
         (features.texture3d_names(scale, gray_levels); aliby_features_texture3d): the 13 Haralick statistics of the 2-D `texture`
         in 13 directions over each object's bounding box, direction-major.  Rows in (stack, label) order.  A direction without a
         voxel pair gets 13 NaN, a label of 1..counts[f] without voxels a row of NaN.  Bitwise independent of run and batch."""
-        if not (isinstance(volume, torch.Tensor) and isinstance(pixels, torch.Tensor)):
-            raise TypeError("texture3d takes torch tensors on the device")
-        if volume.dtype != torch.uint16:
-            raise TypeError(f"volume labels must be uint16, got {volume.dtype}")
-        if pixels.dtype not in (torch.uint16, torch.float32):
-            raise TypeError(f"pixels must be uint16 or float32, got {pixels.dtype}")
-        if volume.dim() != 4 or pixels.dim() != 5 or tuple(pixels.shape[:1]) != tuple(volume.shape[:1]) or tuple(pixels.shape[2:]) != tuple(volume.shape[1:]):
-            raise ValueError(f"volume must be [F,Z,Y,X] and pixels [F,C,Z,Y,X], got {tuple(volume.shape)} and {tuple(pixels.shape)}")
-        if not (volume.is_cuda and pixels.is_cuda):
-            raise ValueError("texture3d takes tensors on the device")
-        F, Z, Y, X = volume.shape
-        Cn = int(pixels.shape[1])
+        F, Cn, Z, Y, X, offsets = self._volume_inputs("texture3d", volume, pixels, counts)
         for name, v in (("channel", channel), ("scale", scale), ("gray_levels", gray_levels)):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
                 raise TypeError(f"{name} must be an integer, got {v!r}")
@@ -430,11 +426,6 @@ class FeatureEngine:
             raise ValueError(f"channel {channel} out of range for {Cn} channels")
         if scale < 1 or not 2 <= gray_levels <= 256:
             raise ValueError(f"texture3d needs scale >= 1 and 2 <= gray_levels <= 256, got {scale}, {gray_levels}")
-        cnt = np.asarray(counts, np.int64).reshape(-1)
-        if cnt.shape != (F,) or (cnt < 0).any() or (cnt > 65535).any():
-            raise ValueError(f"counts must hold one label count (0..65535) per stack ({F}), got {counts!r}")
-        offsets = np.zeros(F + 1, np.int32)
-        np.cumsum(cnt, out=offsets[1:])
         out = self.new_output(int(offsets[-1]), len(feat.texture3d_names(scale, gray_levels)))
         if int(offsets[-1]) == 0:
             return out  # stacks without any object: an empty block
@@ -518,8 +509,6 @@ class FeatureEngine:
     def radial_zernikes_multi(self, labels, planes, dtype, channels, table: ObjectTable, out, col0s):
         """radial_zernikes of several channels of one plane block: launches of up to five channels share the channel-independent
         basis (aliby_features_radial_zernikes_multi); a channel left alone goes through `zernike(weighted=True)`."""
-        import ctypes as C
-
         F, Cn, Y, X = planes.shape
         mec = self.mec(labels, table)
         channels, col0s = list(map(int, channels)), list(map(int, col0s))

@@ -7,24 +7,18 @@ no Costes probe of any input used here is within 1e-8 of a sign change).  Parity
 Rule (README "Parity", tests/test_gpu_features.py::_compare): float columns within rtol = 1e-4, atol = 1e-9, NaN where the
 reference has NaN.  Reproducibility is asserted bit for bit.
 """
-import warnings
+from functools import partial
 
 import numpy as np
 import pytest
 
 from tests import coloc3d_ref as ref
+from tests.volume_checks import bits as _bits, check, pixel_mode as _mode, quiet_numpy  # noqa: F401 (quiet_numpy: an autouse fixture)
 
 pytestmark = pytest.mark.gpu
 
-RTOL, ATOL = 1e-4, 1e-9
 ALL3 = [(0, 1), (0, 2), (1, 2)]
-
-
-@pytest.fixture(autouse=True)
-def _quiet_numpy():
-    with warnings.catch_warnings():  # (the oracle's one-voxel variance: numpy warns, the value is the NaN that is wanted)
-        warnings.simplefilter("ignore", RuntimeWarning)
-        yield
+_check = partial(check, "coloc3d")
 
 
 def _run(engine, vols, pixels, pairs, counts=None, **kw):
@@ -39,29 +33,11 @@ def _run(engine, vols, pixels, pairs, counts=None, **kw):
     return got, counts
 
 
-def _bits(t):
-    import torch
-
-    return t.contiguous().view(torch.int64)
-
-
-def _check(got, want, tag):
-    got = got.cpu().numpy() if hasattr(got, "cpu") else got
-    assert got.shape == want.shape, tag
-    assert np.array_equal(np.isnan(got), np.isnan(want)), (tag, np.argwhere(np.isnan(got) != np.isnan(want))[:4])
-    ok = np.isclose(got, want, rtol=RTOL, atol=ATOL, equal_nan=True)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        rel = np.abs(got - want) / np.abs(want)
-    rel = rel[np.isfinite(rel)]
-    print(f"coloc3d {tag}: {want.shape[0]} objects x {want.shape[1]} columns, worst relative error {float(rel.max()) if rel.size else 0.0:.2e}")
-    assert ok.all(), (tag, [(int(r), int(c), got[r, c], want[r, c]) for r, c in np.argwhere(~ok)[:6]])
-
-
 # ------------------------------------------------------------------------------------------------ 1. against the reference
 @pytest.mark.parametrize("mode", ["u16", "f32_unit"])
 def test_ellipsoids_all_pairs_equal_the_reference(engine, mode):
     vol, n, px = ref.ellipsoids()
-    px = px if mode == "u16" else ref.unit_float(px)
+    px = _mode(px, mode)
     assert n >= 8 and px.shape[0] == 3
     got, counts = _run(engine, [vol], px[None], ALL3)
     assert counts == [n]
@@ -71,7 +47,7 @@ def test_ellipsoids_all_pairs_equal_the_reference(engine, mode):
 @pytest.mark.parametrize("mode", ["u16", "f32_unit"])
 def test_irregular_touching_labels_equal_the_reference(engine, mode):
     vol, n, px = ref.irregular()
-    px = px if mode == "u16" else ref.unit_float(px)
+    px = _mode(px, mode)
     a, b = vol[:, :, :-1], vol[:, :, 1:]
     assert n >= 8 and ((a != b) & (a > 0) & (b > 0)).any()  # objects touch
     got, counts = _run(engine, [vol], px[None], ALL3)
@@ -100,7 +76,7 @@ def test_objects_on_both_sides_of_the_lds_budget(engine, mode):
     budget = engine.coloc3d_lds_voxels
     vol, n, px, voxels = ref.budget_volume(budget)
     assert (voxels == budget).any() and (voxels == budget + 1).any() and (voxels < budget).sum() >= 2 and (voxels > 2 * budget).any()
-    px = px if mode == "u16" else ref.unit_float(px)
+    px = _mode(px, mode)
     got, counts = _run(engine, [vol], px[None], [(0, 1)])
     _check(got, ref.coloc3d_batch([vol], px[None], [(0, 1)], counts), f"budget {mode}")
 

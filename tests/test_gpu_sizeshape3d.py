@@ -241,6 +241,15 @@ def test_the_c_entry_refuses_what_it_cannot_hold(engine):
     _lib.check(fn(engine.ctx.handle, _ptr(lab), 1, 2, 8, 8, _ptr(off), _ptr(sp), _ptr(out), 19, 0, _stream_ptr()))
     row = out.cpu().numpy()[0]
     assert row[C["Volume"]] == 18 and row[C["EulerNumber"]] == 1 and row[C["Extent"]] == 1.0
+    # offsets that do not grow would put rows past the accumulators.  All-background labels: no kernel writes whatever the entry does
+    bg = torch.zeros((2, 2, 8, 8), dtype=torch.uint16, device="cuda")
+    out2 = torch.zeros((3, 19), dtype=torch.float64, device="cuda")
+    with pytest.raises(ValueError):
+        _lib.check(fn(engine.ctx.handle, _ptr(bg), 2, 2, 8, 8, _ptr(np.asarray([0, 3, 2], np.int32)), _ptr(sp), _ptr(out2), 19, 0, _stream_ptr()))
+    torch.cuda.synchronize()
+    assert float(out2.abs().sum()) == 0.0
+    with pytest.raises(ValueError):
+        engine.sizeshape3d(bg, [2, -1])
 
 
 # ------------------------------------------------------------------------------------------------ 6. end to end

@@ -8,24 +8,18 @@ Rule (README "Parity", tests/test_gpu_features.py::_compare): float columns with
 reference has NaN.  Reproducibility is asserted bit for bit.  Every test prints the worst relative error it saw; on an
 MI355X the largest over the file was 7.7e-11 (42 comparisons, most of them below 1e-11).
 """
-import warnings
+from functools import partial
 
 import numpy as np
 import pytest
 
 from tests import coloc3d_ref as c3
 from tests import texture3d_ref as ref
+from tests.volume_checks import bits as _bits, check, pixel_mode as _mode, quiet_numpy  # noqa: F401 (quiet_numpy: an autouse fixture)
 
 pytestmark = pytest.mark.gpu
 
-RTOL, ATOL = 1e-4, 1e-9
-
-
-@pytest.fixture(autouse=True)
-def _quiet_numpy():
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore", RuntimeWarning)
-        yield
+_check = partial(check, "texture3d")
 
 
 def _run(engine, vols, pixels, channel=0, counts=None, **kw):
@@ -37,29 +31,6 @@ def _run(engine, vols, pixels, channel=0, counts=None, **kw):
     got = engine.texture3d(torch.from_numpy(stack).cuda(), torch.from_numpy(np.ascontiguousarray(pixels)).cuda(), channel, counts, **kw)
     assert got.dtype == torch.float64 and tuple(got.shape) == (sum(counts), 169)
     return got, counts
-
-
-def _bits(t):
-    import torch
-
-    return t.contiguous().view(torch.int64)
-
-
-def _check(got, want, tag):
-    got = got.cpu().numpy() if hasattr(got, "cpu") else got
-    assert got.shape == want.shape, tag
-    assert np.array_equal(np.isnan(got), np.isnan(want)), (tag, np.argwhere(np.isnan(got) != np.isnan(want))[:4])
-    ok = np.isclose(got, want, rtol=RTOL, atol=ATOL, equal_nan=True)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        rel = np.abs(got - want) / np.abs(want)
-    rel = rel[np.isfinite(rel)]
-    print(f"texture3d {tag}: {want.shape[0]} objects x {want.shape[1]} columns, {int(np.isfinite(want).sum())} finite, "
-          f"worst relative error {float(rel.max()) if rel.size else 0.0:.2e}")
-    assert ok.all(), (tag, [(int(r), int(c), got[r, c], want[r, c]) for r, c in np.argwhere(~ok)[:6]])
-
-
-def _mode(px, mode):
-    return px if mode == "u16" else c3.unit_float(px)
 
 
 # ------------------------------------------------------------------------------------------------ 1. against the reference

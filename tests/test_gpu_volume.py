@@ -85,6 +85,27 @@ def test_intensity3d_matches_numpy_on_the_volume(engine):
     assert np.array_equal(again, got, equal_nan=True)  # integer sums: run-to-run identical
 
 
+def test_intensity3d_refuses_offsets_it_cannot_hold(engine):
+    """Offsets that do not grow would put rows past the accumulators.  All-background labels: no kernel writes whatever the entry does."""
+    import torch
+
+    from aliby_amd import _lib
+    from aliby_amd.extraction.engine import _ptr, _stream_ptr
+
+    bg = torch.zeros((2, 2, 8, 8), dtype=torch.uint16, device="cuda")
+    px = torch.ones((2, 1, 2, 8, 8), dtype=torch.uint16, device="cuda")
+    out = torch.zeros((3, 12), dtype=torch.float64, device="cuda")
+    fn = engine.lib.aliby_features_intensity3d
+    with pytest.raises(ValueError):
+        _lib.check(fn(engine.ctx.handle, _ptr(bg), _ptr(px), 2, 1, 2, 8, 8, 0, _ptr(np.asarray([0, 3, 2], np.int32)), _ptr(out), 12, 0, _stream_ptr()))
+    torch.cuda.synchronize()
+    assert float(out.abs().sum()) == 0.0  # refused before anything was written
+    with pytest.raises(ValueError):
+        engine.intensity3d(bg, px, 0, [2, -1])
+    _lib.check(fn(engine.ctx.handle, _ptr(bg), _ptr(px), 2, 1, 2, 8, 8, 0, _ptr(np.asarray([0, 2, 3], np.int32)), _ptr(out), 12, 0, _stream_ptr()))
+    assert bool(torch.isnan(out[:, 2]).all())  # good offsets pass: three absent labels, no mean
+
+
 def test_stitch_threshold_range_and_lut_overflow(engine):
     import torch
 
