@@ -344,6 +344,136 @@ int launch(DeepArgs& a, hipStream_t stream, const char* cap_env = nullptr) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// The same unit for 64 output channels: the up path's 128 -> 64 convolution at the 112 x 112 level (input read through the 2x
+// upsample, skip tensor as the residual), which the two K-slice launches of k_conv3x3 ran through a bf16 partial sum in HBM.
+// With 64 output channels a wave still owns 32 channels x 7 position blocks, and the four waves of a workgroup are
+// 2 channel groups x 2 POSITION groups: a tile is U_RUN = 448 consecutive positions, so that the window a workgroup stages
+// (run + 2 LW + 2) is 1.5 runs at LW = 114 where one position group would stage 2.0.  What changes against k_conv3x3_deep:
+//   * K slices of 32 channels (4 octet planes, two k-steps): the window of 448 + 2 LW + 2 positions x 64 channels is 85 KiB and
+//     would leave one workgroup per CU (3.2: 691 against 888 TFLOP/s), and its raw copy 88 registers per thread; with 32
+//     channels the planes are 44 KiB and the raw window 48 registers, as in k_conv3x3_deep;
+//   * the slice's weight ring is 6 fragments deep and the next slice's window is requested right after the slice's LAST
+//     fragment load has been issued: the vmcnt counter retires in order, so a fragment requested behind the window loads would
+//     make its MFMAs wait for HBM (the k_conv3x3_deep_ls note below); here nothing that the running slice needs is behind them;
+//   * the raw window is read at half resolution through dc_win_off<true>: the 2 x 2 positions of a raw pixel are neighbouring
+//     lanes or come from L2, HBM sees each raw pixel once per slice.
+// Any H, W with W <= U_WMAX; summation order: channels 0-15, 16-31, ... of every tap in turn, fp32 throughout.
+constexpr int U_RUN = 2 * DC_RUN;     // output positions per tile: two position groups of DC_NB blocks
+constexpr int U_WMAX = 128;           // widest image the LDS window is sized for
+constexpr int U_WIN_MAX = U_RUN + 2 * (U_WMAX + 2) + 2;
+constexpr int U_PLANE = U_WIN_MAX | 1;            // odd slot pitch, as DC_PLANE
+constexpr int U_ITERS = (U_WIN_MAX + 63) / 64;    // staging rounds: 64 positions x 4 octets per round of 256 threads
+constexpr int U_LDS_BYTES = 4 * U_PLANE * 16 + U_ITERS * 256 * 4;  // planes + per-thread input offsets
+constexpr int U_NW = 18;              // weight fragments per slice, in (k-step, tap) order
+constexpr int U_WDEPTH = 6;           // weight fragments in flight
+constexpr int U_REQ_AT = U_NW - U_WDEPTH;  // the step that issues the slice's last fragment load, then the next window's request
+static_assert(U_ITERS <= 32, "the inside / later masks hold one bit per staging round");
+
+template <int CIN, bool UP>
+__global__ __launch_bounds__(256, 2) void k_conv3x3_kloop64(DeepArgs a) {
+  constexpr int S = CIN / 32, KCT = CIN / 16;  // K slices, k-steps in the packed array
+  extern __shared__ uint4 lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int cb = wave & 1, pg = wave >> 1;  // channel group, position group
+  const int px = lane & 31, hh = lane >> 5;
+  const int pl = tid & 3, pos0 = tid >> 2;  // staging role: a fixed channel octet of position pos0 + 64 * round
+  const int LW = a.LW, HP = a.HP;
+  const int WIN = U_RUN + 2 * LW + 2;
+  const int cs = CIN / 8;
+  int* const goff = reinterpret_cast<int*>(lds + 4 * U_PLANE) + tid;  // goff[it * 256]: this thread's input offsets of the tile
+
+  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nslots = gridDim.x >> 3;
+  const int per_xcd = (a.ntiles + 7) >> 3;
+  const int t_end = min(a.ntiles, (xcd + 1) * per_xcd);
+
+  for (int tile = xcd * per_xcd + slot; tile < t_end; tile += nslots) {
+    const int q0 = a.q_begin + tile * U_RUN;
+    const int p_first = q0 - LW - 1;  // flat index of window position 0
+    unsigned inside = 0, later = 0;
+    const int n0 = max(0, ((p_first / LW) - 1) / HP);  // image of the window's first row (clamped)
+    {
+      int c, y, n;
+      dc_win_pos(p_first + pos0, LW, HP, c, y, n);
+#pragma unroll
+      for (int it = 0; it < U_ITERS; ++it) {
+        goff[it * 256] = dc_win_off<UP>(a, c, y, n, n0, cs, pl, true, it, inside, later);
+        dc_step32(c, y, n, LW, HP);
+        dc_step32(c, y, n, LW, HP);
+      }
+    }
+    const int n1 = min(n0 + 1, a.N - 1);
+    uint4 v[U_ITERS];
+    auto request = [&](int s) {
+      const uint4* inS = a.in + s * 4;
+#pragma unroll
+      for (int it = 0; it < U_ITERS; ++it) v[it] = inS[(unsigned)goff[it * 256]];
+    };
+    request(0);
+
+    const int qw = q0 + pg * DC_RUN;  // this wave's first output position
+    const int c0 = cb * 32 + hh * 16;
+    const int ocs = a.COUT / 8;
+    f32x16_t acc[DC_NB];
+    dc_seed32(a, qw, px, c0, ocs, LW, HP, acc);
+    const bf16x8_t* wbase = reinterpret_cast<const bf16x8_t*>(a.wpk) + (size_t)cb * 9 * KCT * 64 + lane;
+
+    for (int s = 0; s < S; ++s) {
+      const bf16x8_t* wp = wbase + (size_t)(2 * s) * 64;  // fragment (tap, kc) of this slice at wp[(tap * KCT + kc) * 64]
+      bf16x8_t wring[U_WDEPTH];
+      auto wfrag = [&](int i) { return wp[((i % 9) * KCT + (i / 9)) * 64]; };
+#pragma unroll
+      for (int i = 0; i < U_WDEPTH - 1; ++i) wring[i] = wfrag(i);
+      f32x2_t sc[4], sh[4], sh1[4];  // the slice's prologue constants for this thread's octet (octet 4 (s & 1) + pl of 64 channels)
+      dc_prologue_consts(a, s >> 1, (s & 1) * 4 + pl, n0, n1, sc, sh, sh1);
+      // (re-read through an empty asm: the per-round masks and selects derived from them are then computed in the staging phase
+      // instead of being kept in ~30 registers across the slices, which spills once the weight ring is 6 deep)
+      asm volatile("" : "+v"(inside), "+v"(later));
+      __syncthreads();  // every wave is done reading the previous slice's planes
+#pragma unroll
+      for (int it = 0; it < U_ITERS; ++it) {
+        f32x2_t shs[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) shs[k] = ((later >> it) & 1u) ? sh1[k] : sh[k];
+        const uint4 o = dc_act8(v[it], sc, shs, 0u - ((inside >> it) & 1u));
+        const int wp_ = pos0 + 64 * it;
+        if (wp_ < WIN) lds[pl * U_PLANE + wp_] = o;
+      }
+      __syncthreads();
+
+      // ---- 2 k-steps x 9 taps x 7 blocks
+      const bf16x8_t* L = reinterpret_cast<const bf16x8_t*>(lds) + hh * U_PLANE + pg * DC_RUN + px;
+      const int row_off[3] = {0, LW, 2 * LW};
+      constexpr int NF = U_NW * DC_NB;  // pixel fragments (= MFMAs) per slice
+      bf16x8_t pring[DC_PDEPTH];
+      auto pfrag = [&](int f) {
+        const int i = f / DC_NB, b = f % DC_NB, kc = i / 9, tap = i % 9;
+        return L[2 * kc * U_PLANE + b * 32 + row_off[tap / 3] + tap % 3];
+      };
+#pragma unroll
+      for (int f = 0; f < DC_PDEPTH - 1; ++f) pring[f] = pfrag(f);
+      sfor<U_NW>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        if constexpr (i + U_WDEPTH - 1 < U_NW) wring[(i + U_WDEPTH - 1) % U_WDEPTH] = wfrag(i + U_WDEPTH - 1);
+        if constexpr (i == U_REQ_AT) {
+          __builtin_amdgcn_sched_barrier(0);
+          if (s + 1 < S) request(s + 1);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        sfor<DC_NB>([&](auto bc) {
+          constexpr int b = decltype(bc)::value, f = i * DC_NB + b;
+          if constexpr (f + DC_PDEPTH - 1 < NF) pring[(f + DC_PDEPTH - 1) % DC_PDEPTH] = pfrag(f + DC_PDEPTH - 1);
+          acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wring[i % U_WDEPTH], pring[f % DC_PDEPTH], acc[b], 0, 0, 0);
+        });
+        __builtin_amdgcn_sched_barrier(0);
+      });
+    }
+
+    __builtin_amdgcn_sched_barrier(0);  // nothing of the epilogue is hoisted into the MFMA loop
+    dc_store32(a, qw, px, c0, ocs, LW, HP, acc);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // The same unit on v_mfma_f32_16x16x32_bf16 (round 3).  Under a dense MFMA stream the chip holds a higher clock on this shape
 // than on 32x32x16 (MI355X_MICROARCH.md "Clocks under load" item 7; timing-only check in this kernel: +4.5 %), at the same
 // cycles per FLOP and the same operand traffic.  What changes against k_conv3x3_deep:
@@ -742,6 +872,36 @@ extern "C" int aliby_debug_conv_deep_trace(aliby_ctx* ctx, void* stamps_dev) {
   return ALIBY_OK;
 }
 
+// argument checks and the tall-image geometry that the entry points of this file share; `run` = output positions per tile,
+// `nhalf` = tiles per run
+static int deep_args(DeepArgs& a, aliby_ctx* ctx, const void* in, const void* wpk, void* out, const float* scale, const float* shift,
+                     int shift_per_sample, const float* bias, const void* res, int res_up, int N, int H, int W, int CIN, int COUT,
+                     int run, int nhalf) {
+  a.in = static_cast<const uint4*>(in);
+  a.wpk = static_cast<const uint4*>(wpk);
+  a.out = static_cast<uint4*>(out);
+  a.scale = scale;
+  a.shift = shift;
+  a.bias = bias;
+  a.res = static_cast<const uint4*>(res);
+  a.shift_stride = shift_per_sample == 1 ? CIN : shift_per_sample;
+  a.res_up = res_up ? 1 : 0;
+  a.N = N; a.H = H; a.W = W; a.COUT = COUT;
+  a.LW = W + 2;
+  a.HP = H + 1;
+  const long long rows = (long long)N * a.HP + 1;  // padded tall image: zero row, then N x (H rows + zero row)
+  ARG_CHECK(rows * a.LW < (1ll << 30), "conv3x3_deep: batch too large for 32-bit flat positions");
+  ARG_CHECK((long long)N * H * W * (CIN > COUT ? CIN : COUT) / 8 < (1ll << 31), "conv3x3_deep: tensor too large for 32-bit offsets");
+  a.q_begin = a.LW;                         // row 1, column 0
+  a.q_end = (int)((rows - 1) * a.LW);       // the last row is the closing zero row
+  a.nruns = (a.q_end - a.q_begin + run - 1) / run;
+  a.nhalf = nhalf;
+  a.ntiles = a.nruns * a.nhalf;
+  a.stagger = 0;
+  a.trace = nullptr;
+  return ALIBY_OK;
+}
+
 static int deep_entry(aliby_ctx* ctx, const void* in, const void* wpk, void* out, const float* scale, const float* shift,
                       int shift_per_sample, const float* bias, const void* res, int res_up, int N, int H, int W, int CIN, int COUT,
                       int in_up, void* stream_, bool m16) {
@@ -760,26 +920,8 @@ static int deep_entry(aliby_ctx* ctx, const void* in, const void* wpk, void* out
     return ALIBY_ERR_UNSUPPORTED;
   }
   DeepArgs a;
-  a.in = static_cast<const uint4*>(in);
-  a.wpk = static_cast<const uint4*>(wpk);
-  a.out = static_cast<uint4*>(out);
-  a.scale = scale;
-  a.shift = shift;
-  a.bias = bias;
-  a.res = static_cast<const uint4*>(res);
-  a.shift_stride = shift_per_sample == 1 ? CIN : shift_per_sample;
-  a.res_up = res_up ? 1 : 0;
-  a.N = N; a.H = H; a.W = W; a.COUT = COUT;
-  a.LW = W + 2;
-  a.HP = H + 1;
-  const long long rows = (long long)N * a.HP + 1;  // padded tall image: zero row, then N x (H rows + zero row)
-  ARG_CHECK(rows * a.LW < (1ll << 30), "conv3x3_deep: batch too large for 32-bit flat positions");
-  ARG_CHECK((long long)N * H * W * (CIN > COUT ? CIN : COUT) / 8 < (1ll << 31), "conv3x3_deep: tensor too large for 32-bit offsets");
-  a.q_begin = a.LW;                         // row 1, column 0
-  a.q_end = (int)((rows - 1) * a.LW);       // the last row is the closing zero row
-  a.nruns = (a.q_end - a.q_begin + DC_RUN - 1) / DC_RUN;
-  a.nhalf = COUT / 128;
-  a.ntiles = a.nruns * a.nhalf;
+  if (const int rc = deep_args(a, ctx, in, wpk, out, scale, shift, shift_per_sample, bias, res, res_up, N, H, W, CIN, COUT, DC_RUN, COUT / 128))
+    return rc;
   static const int stagger = [] { const char* e = getenv("ALIBY_DEEP_STAGGER"); return e ? atoi(e) : 0; }();
   a.stagger = stagger;
   a.trace = g_deep_trace;
@@ -829,4 +971,26 @@ extern "C" int aliby_nn_maxpool2_bf16(aliby_ctx* ctx, const void* in, void* out,
   hipLaunchKernelGGL(k_maxpool2, dim3(grid), dim3(256), 0, stream, static_cast<const uint4*>(in), static_cast<uint4*>(out), N, H, W, C / 8);
   KERNEL_CHECK();
   return ALIBY_OK;
+}
+
+extern "C" int aliby_nn_conv3x3_kloop64_bf16(aliby_ctx* ctx, const void* in, const void* wpk, void* out, const float* scale,
+                                             const float* shift, int shift_per_sample, const float* bias, const void* res, int res_up,
+                                             int N, int H, int W, int CIN, int COUT, int in_up, void* stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  ARG_CHECK(ctx && in && wpk && out && scale && shift, "conv3x3_kloop64: null argument");
+  ARG_CHECK(N > 0 && H > 0 && W > 0, "conv3x3_kloop64: empty shape");
+  if (CIN != 128 || COUT != 64 || !in_up || W > U_WMAX) {
+    aliby_set_error("conv3x3_kloop64: unsupported (CIN=%d, COUT=%d, in_up=%d, W=%d): 128 -> 64 through the upsample, W <= %d", CIN, COUT,
+                    in_up, W, U_WMAX);
+    return ALIBY_ERR_UNSUPPORTED;
+  }
+  ARG_CHECK((H & 1) == 0 && (W & 1) == 0, "conv3x3_kloop64: upsampled input needs even H, W");
+  if (shift_per_sample != 0 && (long long)(H + 1) * (W + 2) < U_RUN + 2 * (W + 2) + 2) {
+    aliby_set_error("conv3x3_kloop64: unsupported with a per-sample shift: images of %dx%d are smaller than one tile window (a window may span two images at most)", H, W);
+    return ALIBY_ERR_UNSUPPORTED;
+  }
+  DeepArgs a;
+  if (const int rc = deep_args(a, ctx, in, wpk, out, scale, shift, shift_per_sample, bias, res, res_up, N, H, W, CIN, COUT, U_RUN, 1))
+    return rc;
+  return launch<k_conv3x3_kloop64<128, true>, U_LDS_BYTES, 64, 256>(a, stream);
 }

@@ -71,8 +71,12 @@ class _Proj:
         self.bias = b.contiguous()
 
 
-# (CIN, COUT, input read through the 2x upsample) instantiations of k_conv3x3
-_MFMA_SHAPES = {(32, 32, False), (32, 64, False), (64, 64, False), (64, 32, True), (64, 64, True), (64, 128, False), (64, 128, True)}
+# (CIN, COUT, input read through the 2x upsample) shapes that are one launch: the instantiations of k_conv3x3, and the up path's
+# 128 -> 64 convolution, which is the K-loop kernel k_conv3x3_kloop64 (csrc/nn_conv_deep.hip) for maps up to _KLOOP64_WMAX wide
+_KLOOP64 = (128, 64, True)
+_KLOOP64_WMAX = 128
+_MFMA_SHAPES = {(32, 32, False), (32, 64, False), (64, 64, False), (64, 32, True), (64, 64, True), (64, 128, False), (64, 128, True),
+                _KLOOP64}
 _POOL_SHAPES = {(32, 32, False), (32, 64, False), (64, 64, False), (64, 128, False)}
 
 
@@ -94,6 +98,8 @@ class FusedUNet:
         self.fused_first = os.environ.get("ALIBY_NET_FUSED_FIRST", "1") != "0"  # the first layer + conv1 + projection in one launch
         # deep levels (128 / 256 channels): one K-loop launch per convolution (csrc/nn_conv_deep.hip); 0 = the K/N-slice launches
         self.deep_kernel = os.environ.get("ALIBY_CONV_DEEP", "1") != "0"
+        # the up path's 128 -> 64 convolution as one K-loop launch; 0 = the two K-slice launches with a bf16 partial sum (A/B)
+        self.kloop64_kernel = os.environ.get("ALIBY_CONV_KLOOP64", "1") != "0"
         self.conv_stats = {}  # timing group -> [algorithmic bytes, flops] of the MFMA conv launches bracketed with events
         # every call made through self.lib is an asynchronous kernel launch: they keep the interpreter lock (see _lib.load_fast)
         self.lib = _lib.load_fast() if os.environ.get("ALIBY_FAST_LAUNCH", "1") != "0" else eng.lib
@@ -182,7 +188,8 @@ class FusedUNet:
         """conv3x3(relu(scale*x + shift)) + bias + res on the MFMA convolution unit.  One launch when the shape is
         one of the kernel's instantiations; otherwise the convolution is split along K (64 input channels per
         launch, each launch adding to the previous one through RES, in place) and along N (128 output channels
-        per launch, written into channel slices of the output)."""
+        per launch, written into channel slices of the output).  The up path's 128 -> 64 convolution through the upsample
+        is one launch too, of the K-loop kernel for 64 output channels (`_launch_kloop64`), on maps up to 128 wide."""
         n, cin, cout = x.shape[0], x.shape[1], unit.w32.shape[0]
         H, W = (x.shape[2] * 2, x.shape[3] * 2) if in_up else (x.shape[2], x.shape[3])
         out = self._new(n, cout, H, W)
@@ -193,7 +200,12 @@ class FusedUNet:
                 with self.eng.timed("maxpool"):
                     _lib.check(self.lib.aliby_nn_maxpool2_bf16(self.h, _ptr(out), _ptr(pooled), n, H, W, cout, _stream_ptr()))
             return (out, pooled) if pool else out
-        if (cin, cout, bool(in_up)) in (_POOL_SHAPES if pool else _MFMA_SHAPES):
+        one_launch = (cin, cout, bool(in_up)) in (_POOL_SHAPES if pool else _MFMA_SHAPES)
+        if (cin, cout, bool(in_up)) == _KLOOP64:  # by the shape alone, never by the batch: the two forms round differently
+            sh = unit.shift if shift is None else shift
+            one_launch = (not pool and self.deep_kernel and self.kloop64_kernel and W <= _KLOOP64_WMAX
+                          and (sh.ndim == 1 or (H + 1) * (W + 2) >= 450 + 2 * (W + 2)))
+        if one_launch:
             self._launch_unit(x, unit, (0, cin), (0, cout), out, shift, bias, res, res_up, in_up, pooled)
             return (out, pooled) if pool else out
         ns = 128 if cout > 128 else cout
@@ -339,12 +351,33 @@ class FusedUNet:
                 _ptr(bias) if bias is not None else 0, _ptr(res) if res is not None else 0, 1 if res_up else 0, n, H, W, cin, cout,
                 1 if in_up else 0, _stream_ptr()))
 
+    def _launch_kloop64(self, x, unit, out, shift, bias, res, res_up):
+        """One launch of the 64-output-channel K-loop kernel (aliby_nn_conv3x3_kloop64_bf16): the up path's 128 -> 64 convolution
+        through the upsample, fp32 accumulation over the whole reduction.  Booked with the other 64-channel launches."""
+        n, cin, cout = x.shape[0], x.shape[1], out.shape[1]
+        H, W = out.shape[2], out.shape[3]
+        sh = unit.shift if shift is None else shift
+        group = "conv3x3_mfma"
+        timer = self.eng.timed(group)
+        if timer.active:  # algorithmic bytes: half-resolution input + skip read once, output written once
+            st = self.conv_stats.setdefault(group, [0, 0])
+            st[0] += 2 * (x.numel() + out.numel() + (res.numel() if res is not None else 0))
+            st[1] += 2 * 9 * cin * cout * n * H * W
+        with timer:
+            _lib.check(self.lib.aliby_nn_conv3x3_kloop64_bf16(
+                self.h, _ptr(x), _ptr(self._pack(unit)), _ptr(out), _ptr(unit.scale), _ptr(sh), self._sps(sh),
+                _ptr(bias) if bias is not None else 0, _ptr(res) if res is not None else 0, 1 if res_up else 0, n, H, W, cin, cout,
+                1, _stream_ptr()))
+
     def _launch_unit(self, x, unit, kslice, nslice, out, shift, bias, res, res_up, in_up, pooled):
         n, ctot, cout_tot = x.shape[0], x.shape[1], out.shape[1]
         (k0, k1), (n0, n1) = kslice, nslice
         cin, cout = k1 - k0, n1 - n0
         H, W = out.shape[2], out.shape[3]
         assert pooled is None or (cin, cout, bool(in_up)) in _POOL_SHAPES
+        if (cin, cout, bool(in_up)) == _KLOOP64:
+            assert (ctot, cout_tot) == (cin, cout), "the K-loop kernel takes whole tensors"
+            return self._launch_kloop64(x, unit, out, shift, bias, res, res_up)
         if unit.wpk is None:
             unit.wpk = {}
         key = (k0, k1, n0, n1)

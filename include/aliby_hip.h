@@ -214,6 +214,16 @@ int aliby_nn_conv3x3_deep_bf16(aliby_ctx* ctx, const void* in, const void* wpk, 
                                const float* shift, int shift_per_sample, const float* bias, const void* res, int res_up,
                                int N, int H, int W, int CIN, int COUT, int in_up, void* stream);
 
+/* The same K-loop unit for the up path's 128 -> 64 convolution (input read through the 2x upsample, skip tensor as RES): ONE
+ * launch with fp32 accumulation over the whole 9 * 128 reduction (K loop over 32-channel slices, a workgroup = 2 channel
+ * groups x 2 position groups), instead of two K-slice launches of aliby_nn_conv3x3_bf16 with a bf16 partial sum in HBM.
+ * Arguments as aliby_nn_conv3x3_deep_bf16.  Supported: CIN = 128, COUT = 64, in_up = 1, even H and W, W <= 128,
+ * (H + 1) * (W + 2) >= 450 + 2 * (W + 2) when the shift is per sample; anything else returns ALIBY_ERR_UNSUPPORTED and
+ * launches nothing.  Replaces: cellpose `batchconv` of `resup.conv0` at the second-finest level (segment/dispatch.py:208-215). */
+int aliby_nn_conv3x3_kloop64_bf16(aliby_ctx* ctx, const void* in, const void* wpk, void* out, const float* scale,
+                                  const float* shift, int shift_per_sample, const float* bias, const void* res, int res_up,
+                                  int N, int H, int W, int CIN, int COUT, int in_up, void* stream);
+
 /* The same unit on v_mfma_f32_16x16x32_bf16 (the shape the chip holds a higher clock on: nn_conv_deep.hip).  Same arguments and
  * meaning; `wpk16` is packed by aliby_nn_pack_conv3x3_deep16_bf16 (w_oihw float32 [COUT, CIN, 3, 3], COUT a multiple of 32, CIN
  * of 64 -> COUT * CIN * 9 bf16).  Accumulates 32 input channels per instruction: agrees with aliby_nn_conv3x3_deep_bf16 to fp32
