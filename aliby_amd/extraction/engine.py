@@ -343,15 +343,21 @@ class FeatureEngine:
 
     def intensity3d(self, volume: torch.Tensor, pixels: torch.Tensor, channel: int, counts) -> torch.Tensor:
         """Volume labels uint16 [F,Z,Y,X] (1..counts[f] per stack), pixels uint16 [F,C,Z,Y,X] -> float64 [sum counts, 12]
-        (features.intensity3d_names(); aliby_features_intensity3d).  Rows in (stack, label) order."""
-        F, Z, Y, X = volume.shape
-        assert pixels.dtype == torch.uint16 and tuple(pixels.shape[:1]) == (F,) and tuple(pixels.shape[2:]) == (Z, Y, X)
-        offsets = self._volume_offsets("intensity3d", F, counts)
+        (features.intensity3d_names(); aliby_features_intensity3d).  Rows in (stack, label) order.  A label of 1..counts[f]
+        without voxels gets Volume 0 and NaN elsewhere; labels above counts[f] are not measured.  Exact 64-bit integer sums: bitwise
+        independent of run and batch."""
+        F, Cn, Z, Y, X, offsets = self._volume_inputs("intensity3d", volume, pixels, counts)
+        if pixels.dtype != torch.uint16:
+            raise TypeError(f"intensity3d: pixels must be uint16 (the family has no float form), got {pixels.dtype}")
+        if isinstance(channel, bool) or not isinstance(channel, (int, np.integer)):
+            raise TypeError(f"channel must be an integer, got {channel!r}")
+        if not 0 <= int(channel) < Cn:
+            raise ValueError(f"channel {int(channel)} out of range for {Cn} channels")
         out = self.new_output(int(offsets[-1]), 12)
         if int(offsets[-1]) == 0:
             return out  # stacks without any object: an empty block (found by tests/fuzz/fuzz_volume.py — the C entry refuses a NULL output)
         with self.timed("intensity3d"):
-            _lib.check(self.lib.aliby_features_intensity3d(self.ctx.handle, _ptr(volume.contiguous()), _ptr(pixels.contiguous()), F, pixels.shape[1], Z, Y,
+            _lib.check(self.lib.aliby_features_intensity3d(self.ctx.handle, _ptr(volume.contiguous()), _ptr(pixels.contiguous()), F, Cn, Z, Y,
                                                            X, int(channel), _ptr(offsets), _ptr(out), out.stride(0) if out.numel() else 12, 0,
                                                            _stream_ptr()))
         return out
