@@ -6,20 +6,25 @@
 //   iou[c, p] = |c ∩ p| / (|c| + |p| - |c ∩ p|) in float64; entries below the threshold are dropped; every previous
 //   object keeps only the current object(s) with its column maximum; a current object takes the previous TRACKED label
 //   of its row maximum (first maximum = smallest tracked label) or, if nothing is left, a new label.
+// The reference relabels the previous frame with its tracked labels BEFORE stitch3D sees it (update_labels), so a
+// "previous object" p above is a GROUP: all previous rows of a tile that carry the same nonzero tracked label (the two
+// daughters of a column tie both keep their mother's label) are one object, with the summed overlap, the summed area, one
+// column maximum and one candidate; a previous row tracked as 0 is background.  tests/track_ref.py is the literal form.
 //
-// MI355X shape: the (N_cur x N_prev) overlap matrix is never formed.  One workgroup per current object scans its
-// bounding box once and counts the previous labels under its mask in a small LDS hash table (integer atomics), so the
-// two label planes are read once (HBM-bound, 2·P·2 bytes per tile); at most floor(1/threshold) previous objects can
-// pass the threshold for one current object; candidates go to a fixed 16-slot list (more than 16 previous objects above the
-// threshold under one mask — only possible for thresholds below 1/16 — is reported as an error, never dropped silently).  Column maxima are one 64-bit
-// integer atomicMax per candidate on the bit pattern of the (positive) double.  New labels are handed out in current
-// label order by one workgroup per tile.
+// MI355X shape: the (N_cur x N_prev) overlap matrix is never formed.  One workgroup per tile first finds every previous
+// row's group (k_track_groups: the group's representative is its first row; areas are summed there), with no host round
+// trip.  Then one workgroup per current object scans its bounding box once and counts the previous groups under its mask
+// in a small LDS hash table (integer atomics), so the two label planes are read once (HBM-bound, 2·P·2 bytes per tile);
+// at most floor(1/threshold) previous groups can pass the threshold for one current object; candidates go to a fixed
+// 16-slot list (more than 16 groups above the threshold under one mask — only possible for thresholds below 1/16 — is
+// reported as an error, never dropped silently).  Column maxima are one 64-bit integer atomicMax per candidate on the bit
+// pattern of the (positive) double.  New labels are handed out in current label order by one workgroup per tile.
 #include "common.h"
 
 typedef unsigned short u16;
 
-#define TRK_SLOTS 1024  // LDS hash slots per object (distinct previous labels under one mask)
-#define TRK_K 16        // candidates kept per current object (a 17th previous object above the threshold under one mask is reported)
+#define TRK_SLOTS 1024  // LDS hash slots per object (distinct previous groups under one mask)
+#define TRK_K 16        // candidates kept per current object (a 17th previous group above the threshold under one mask is reported)
 
 struct TrackArgs {
   const u16* prev;
@@ -31,6 +36,8 @@ struct TrackArgs {
   const int* poff;      // [F+1] row offsets of the previous table
   const int* coff;      // [F+1] row offsets of the current table
   const int* ptracked;  // tracked label per previous row, or NULL (= own label)
+  int* grp_rep;            // [n_prev] label (row - poff + 1) of the row's group representative, 0 = background; NULL with ptracked
+  int* garea;           // [n_prev] summed area of the group, at the representative's row
   double thr;
   int* ncand;                   // [n_cur]
   int* cand_row;                // [n_cur * TRK_K] previous row
@@ -38,6 +45,42 @@ struct TrackArgs {
   unsigned long long* colmax;   // [n_prev] bit pattern of the column maximum
   int* overflow;
 };
+
+// One workgroup per tile: previous rows with the same nonzero tracked label form one group, represented by its first
+// row.  hkeys / hvals: zeroed open-addressing table in global memory, 2 * pn + 1 slots for the tile's pn rows (so a free
+// slot always ends a probe sequence), key = tracked label, value = pn - (first row of the group), kept by atomicMax.
+__global__ __launch_bounds__(256) void k_track_groups(TrackArgs a, int* __restrict__ hkeys, int* __restrict__ hvals) {
+  const int f = blockIdx.x, tid = threadIdx.x;
+  const int p0 = a.poff[f], pn = a.poff[f + 1] - p0;
+  const unsigned int cap = 2u * (unsigned int)pn + 1u;
+  int* keys = hkeys + 2 * (size_t)p0 + f;
+  int* vals = hvals + 2 * (size_t)p0 + f;
+  for (int i = tid; i < pn; i += blockDim.x) {
+    const int tl = a.ptracked[p0 + i];
+    if (tl == 0) continue;
+    unsigned int s = ((unsigned int)tl * 2654435761u) % cap;
+    for (unsigned int probes = 0; probes < cap; ++probes, s = s + 1 == cap ? 0u : s + 1) {
+      const int old = atomicCAS(&keys[s], 0, tl);
+      if (old == 0 || old == tl) { atomicMax(&vals[s], pn - i); break; }
+    }
+  }
+  __threadfence();
+  __syncthreads();
+  for (int i = tid; i < pn; i += blockDim.x) {
+    const int tl = a.ptracked[p0 + i];
+    int rep = 0;
+    if (tl != 0) {
+      unsigned int s = ((unsigned int)tl * 2654435761u) % cap;
+      for (unsigned int probes = 0; probes < cap; ++probes, s = s + 1 == cap ? 0u : s + 1) {
+        const int k = __hip_atomic_load(&keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (k == tl) { rep = pn - __hip_atomic_load(&vals[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1; break; }
+        if (k == 0) break;  // (every nonzero label was inserted above: not reached)
+      }
+    }
+    a.grp_rep[p0 + i] = rep;
+    if (rep > 0 && rep <= pn) atomicAdd(&a.garea[p0 + rep - 1], a.ptab[p0 + i].area);
+  }
+}
 
 __global__ __launch_bounds__(256) void k_track_candidates(TrackArgs a) {
   __shared__ unsigned int keys[TRK_SLOTS];
@@ -56,11 +99,16 @@ __global__ __launch_bounds__(256) void k_track_candidates(TrackArgs a) {
     const u16* prev = a.prev + (size_t)o.tile * plane;
     const int h = o.y1 - o.y0, w = o.x1 - o.x0, npix = h * w;
     const u16 L = (u16)o.label;
+    const int p0 = a.poff[o.tile], pn = a.poff[o.tile + 1] - p0;
     for (int i = tid; i < npix; i += blockDim.x) {
       const size_t idx = (size_t)(o.y0 + i / w) * a.X + (o.x0 + i % w);
       if (cur[idx] != L) continue;
-      const unsigned int lb = prev[idx];
-      if (lb == 0u) continue;
+      unsigned int lb = prev[idx];
+      if (lb == 0u || (int)lb > pn) continue;  // a previous label beyond its table cannot happen; guarded anyway
+      if (a.grp_rep) {  // count under the group's representative; a row tracked as 0 is background
+        lb = (unsigned int)a.grp_rep[p0 + (int)lb - 1];
+        if (lb == 0u || (int)lb > pn) continue;
+      }
       unsigned int s = (lb * 40503u) & (TRK_SLOTS - 1);
       int probes = 0;
       for (;; s = (s + 1) & (TRK_SLOTS - 1)) {
@@ -70,13 +118,12 @@ __global__ __launch_bounds__(256) void k_track_candidates(TrackArgs a) {
       }
     }
     __syncthreads();
-    const int p0 = a.poff[o.tile], pn = a.poff[o.tile + 1] - p0;
     for (int k = tid; k < TRK_SLOTS; k += blockDim.x) {
       const unsigned int lb = keys[k];
-      if (lb == 0u || (int)lb > pn) continue;  // a previous label beyond its table cannot happen; guarded anyway
+      if (lb == 0u) continue;
       const int prow = p0 + (int)lb - 1;
       const double ov = (double)cnt[k];
-      const double iou = ov / ((double)o.area + (double)a.ptab[prow].area - ov);
+      const double iou = ov / ((double)o.area + (double)(a.garea ? a.garea[prow] : a.ptab[prow].area) - ov);
       if (!(iou >= a.thr) || !(iou > 0.0)) continue;
       const int slot = atomicAdd(&nc, 1);
       if (slot >= TRK_K) { atomicExch(a.overflow, 2); continue; }
@@ -147,10 +194,15 @@ extern "C" int aliby_track_stitch(aliby_ctx* ctx, const uint16_t* prev, const ui
   ARG_CHECK(n_cur == 0 || (cur && prev && cur_table_dev && cur_tracked_dev), "NULL argument");
   ARG_CHECK(n_prev == 0 || prev_table_dev, "NULL argument");
   hipStream_t s = as_stream(stream);
-  // device scratch: offsets (2(F+1)), max_in (F), max_out (F), overflow (1), matched (n_cur), ncand (n_cur), cand rows, ious, colmax
-  const size_t ints = (size_t)2 * (F + 1) + 2 * (size_t)F + 1 + 2 * (size_t)n_cur + (size_t)n_cur * TRK_K;
+  // device scratch: offsets (2(F+1)), max_in (F), max_out (F), overflow (1), matched (n_cur), ncand (n_cur), cand rows, group
+  // representatives (n_prev), ious, then one zeroed block: colmax (n_prev), group areas (n_prev), group table keys, values
+  const bool groups = prev_tracked_dev != nullptr && n_prev > 0;
+  const size_t np1 = (size_t)(n_prev > 0 ? n_prev : 1);
+  const size_t hslots = groups ? 2 * (size_t)n_prev + (size_t)F : 0;
+  const size_t ints = (size_t)2 * (F + 1) + 2 * (size_t)F + 1 + 2 * (size_t)n_cur + (size_t)n_cur * TRK_K + np1;
   const size_t off_d = (ints * sizeof(int) + 15) & ~(size_t)15;
-  const size_t bytes = off_d + sizeof(double) * (size_t)n_cur * TRK_K + sizeof(unsigned long long) * (size_t)(n_prev > 0 ? n_prev : 1);
+  const size_t zeroed = sizeof(unsigned long long) * np1 + sizeof(int) * (groups ? np1 + 2 * hslots : 0);
+  const size_t bytes = off_d + sizeof(double) * (size_t)n_cur * TRK_K + zeroed;
   int rc = aliby_ensure_scratch(ctx, bytes);
   if (rc) return rc;
   int* base = (int*)ctx->scratch;
@@ -162,17 +214,26 @@ extern "C" int aliby_track_stitch(aliby_ctx* ctx, const uint16_t* prev, const ui
   int* d_matched = d_over + 1;
   int* d_ncand = d_matched + n_cur;
   int* d_crow = d_ncand + n_cur;
+  int* d_rep = d_crow + (size_t)n_cur * TRK_K;
   double* d_ciou = (double*)((char*)ctx->scratch + off_d);
   unsigned long long* d_colmax = (unsigned long long*)(d_ciou + (size_t)n_cur * TRK_K);
+  int* d_garea = (int*)(d_colmax + np1);
+  int* d_hkeys = d_garea + np1;
+  int* d_hvals = d_hkeys + hslots;
   HIP_TRY(hipMemcpyAsync(d_coff, cur_offsets_host, sizeof(int) * (F + 1), hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(d_poff, prev_offsets_host, sizeof(int) * (F + 1), hipMemcpyHostToDevice, s));
   if (max_label_in_host) HIP_TRY(hipMemcpyAsync(d_maxin, max_label_in_host, sizeof(int) * F, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemsetAsync(d_over, 0, sizeof(int), s));
-  HIP_TRY(hipMemsetAsync(d_colmax, 0, sizeof(unsigned long long) * (size_t)(n_prev > 0 ? n_prev : 1), s));
+  HIP_TRY(hipMemsetAsync(d_colmax, 0, zeroed, s));
   TrackArgs a;
   a.prev = prev; a.cur = cur; a.F = F; a.Y = Y; a.X = X; a.ctab = cur_table_dev; a.n_cur = n_cur; a.ptab = prev_table_dev;
   a.poff = d_poff; a.coff = d_coff; a.ptracked = prev_tracked_dev; a.thr = threshold; a.ncand = d_ncand; a.cand_row = d_crow;
   a.cand_iou = d_ciou; a.colmax = d_colmax; a.overflow = d_over;
+  a.grp_rep = groups ? d_rep : nullptr; a.garea = groups ? d_garea : nullptr;
+  if (groups && n_cur > 0) {
+    hipLaunchKernelGGL(k_track_groups, dim3(F), dim3(256), 0, s, a, d_hkeys, d_hvals);
+    KERNEL_CHECK();
+  }
   if (n_cur > 0) {
     hipLaunchKernelGGL(k_track_candidates, dim3(n_cur), dim3(64), 0, s, a);
     KERNEL_CHECK();

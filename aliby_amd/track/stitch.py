@@ -7,7 +7,9 @@ older frame with its tracked labels (`update_labels`) and lets `cellpose.utils.s
 frame.  As shipped it cannot be imported (`agora.utils.masks.labels_from_masks` does not exist) and cellpose is not
 vendored, so this module keeps the INTERFACE — same arguments, same `{tile: {"labels": [...], "max_label": n}}` result,
 `labels[i]` = tracked label of the newer frame's object i+1 — and implements the stitch3D rule in one batched HIP call
-(`aliby_track_stitch`, csrc/track.hip).  One deliberate difference: new labels continue from the tile's running
+(`aliby_track_stitch`, csrc/track.hip).  Because the older frame is relabelled first, its objects that carry the same tracked
+label (both daughters of a division keep their mother's label) are ONE object to the rule, with the summed area and overlap,
+and an object tracked as 0 is background.  One deliberate difference: new labels continue from the tile's running
 `max_label`, so the identity of a vanished cell is never reused (oracle/track_restated.py documents the rule).
 """
 

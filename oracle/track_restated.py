@@ -9,8 +9,11 @@ imported (it needs `agora.utils.masks.labels_from_masks`, which does not exist: 
     iou[iou < stitch_threshold] = 0 ; iou[iou < iou.max(axis=0)] = 0            (column-wise winners, ties kept)
     matched: label = argmax over prev (first maximum = smallest previous label) ; unmatched: a new label
 
-with the previous frame carrying its TRACKED labels (trackers.py:70-71 `update_labels`), and with one deliberate,
-documented difference: new labels continue from the running `max_label` of the tile instead of from the largest
+with the previous frame carrying its TRACKED labels (trackers.py:79-90 `update_labels` relabels the image before stitch3D sees
+it): previous objects that share a tracked label -- both daughters of a column tie keep their mother's label -- are ONE
+object there, with the summed area and the summed overlap, one column and one column maximum, and a previous object tracked
+as 0 is background.  tests/track_ref.py does the relabelling literally and tests/test_cpu_track_ref.py holds the two files
+together.  One deliberate, documented difference: new labels continue from the running `max_label` of the tile instead of from the largest
 label present in the previous frame, so the identity of a cell that disappeared is never handed to a new one.
 """
 
@@ -25,7 +28,7 @@ def stitch_pair(prev, cur, prev_tracked=None, max_label=None, stitch_threshold=0
     n_prev, n_cur = int(prev.max(initial=0)), int(cur.max(initial=0))
     if prev_tracked is None:
         prev_tracked = np.arange(1, n_prev + 1, dtype=np.int64)
-    prev_tracked = np.asarray(prev_tracked, dtype=np.int64)
+    prev_tracked = np.asarray(prev_tracked, dtype=np.int64)[:n_prev]  # (a longer list is cut, as the tracker cuts it)
     if max_label is None:
         max_label = int(prev_tracked.max(initial=0))
     max_label = max(int(max_label), int(prev_tracked.max(initial=0)))
@@ -35,15 +38,17 @@ def stitch_pair(prev, cur, prev_tracked=None, max_label=None, stitch_threshold=0
     overlap = np.zeros((n_cur + 1, n_prev + 1), np.int64)
     np.add.at(overlap, (cur.ravel(), prev.ravel()), 1)
     area_cur = overlap.sum(axis=1, keepdims=True)
-    area_prev = overlap.sum(axis=0, keepdims=True)
+    # columns in TRACKED-label order: stitch3D sees the previous frame relabelled with its tracked labels, so previous objects
+    # that share a tracked label are ONE column (overlaps and areas add up) and a tracked label of 0 is background
+    groups = np.unique(prev_tracked[prev_tracked > 0])
+    merged = np.zeros((n_cur + 1, groups.size), np.int64)
+    for j, t in enumerate(groups):
+        merged[:, j] = overlap[:, 1:][:, prev_tracked == t].sum(axis=1)
+    area_prev = merged.sum(axis=0, keepdims=True)
     with np.errstate(divide="ignore", invalid="ignore"):
-        iou = overlap / (area_cur + area_prev - overlap)
+        iou = merged / (area_cur + area_prev - merged)
     iou[np.isnan(iou)] = 0.0
-    iou = iou[1:, 1:]
-    # columns in TRACKED-label order: stitch3D sees the previous frame relabelled with its tracked labels
-    order = np.argsort(prev_tracked, kind="stable") if n_prev else np.zeros(0, np.int64)
-    present = area_prev[0, 1:][order] > 0 if n_prev else np.zeros(0, bool)
-    iou = iou[:, order]
+    iou = iou[1:]
     if iou.size:
         iou[iou < stitch_threshold] = 0.0
         iou[iou < iou.max(axis=0)] = 0.0
@@ -52,11 +57,10 @@ def stitch_pair(prev, cur, prev_tracked=None, max_label=None, stitch_threshold=0
             continue  # label missing from the current frame: stays 0
         row = iou[i] if iou.size else np.zeros(0)
         if row.size and row.max() > 0.0:
-            out[i] = prev_tracked[order][int(np.argmax(row))]
+            out[i] = groups[int(np.argmax(row))]
         else:
             max_label += 1
             out[i] = max_label
-    del present
     return out, max_label
 
 

@@ -16,6 +16,7 @@ from aliby_amd.track.stitch import StitchTracker  # noqa: E402
 from oracle import cellpose_restated as cr  # noqa: E402
 from oracle import tiler_ref  # noqa: E402
 from oracle.track_restated import stitch_rois as oracle_rois  # noqa: E402
+from tests.track_ref import stitch_rois as literal_rois  # noqa: E402
 
 eng = FeatureEngine()
 model = CellposeModel(flows_override=lambda x: None)
@@ -67,9 +68,11 @@ for seed in range(first, first + n):
     info_g = info_c = None
     for t in range(1, T):
         masks = [[s[t - 1], s[t]] for s in seqs]
+        info_l = literal_rois(masks, info_c, threshold=thr)
         info_g = trk(masks, info_g)
         info_c = oracle_rois(masks, info_c, stitch_threshold=thr)
         assert dict(info_g) == info_c, (seed, "track", t, thr)
+        assert dict(info_g) == info_l, (seed, "track, literal reference", t, thr)
     # ---- normalize99
     img = rng.integers(0, int(rng.choice([2, 50, 4000, 65535])), size=(int(rng.integers(1, 4)), Y, X)).astype(np.uint16)
     if rng.random() < 0.2:
