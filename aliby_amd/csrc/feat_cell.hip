@@ -56,8 +56,10 @@ __global__ __launch_bounds__(256) void k_cell(CellArgs a) {
     const aliby_object o = a.tab[oi];
     double* out = a.out + (size_t)oi * a.ld + a.col0;
     if (o.area <= 0) {
-      // an all-False mask: area 0, the rest NaN (0/0) like the reference's arithmetic
-      for (int k = tid; k < CELL_NCOL; k += blockDim.x) out[k] = (k == 0 || k == 3 || k == 5 || k == 12 || k == 13) ? 0.0 : NAN;
+      // an all-False mask, by the reference's arithmetic: the sums are 0, both axes round to 0 (the EDT of an empty frame is 0
+      // everywhere), so volume = 4 pi 0 0 / 3 = 0; the quotients (centroids, eccentricity, mean, ...) are 0/0 = NaN
+      for (int k = tid; k < CELL_NCOL; k += blockDim.x)
+        out[k] = (k == 0 || k == 3 || (k >= 5 && k <= 8) || k == 12 || k == 13) ? 0.0 : NAN;
       continue;
     }
     const u16* lab = a.labels + (size_t)o.tile * plane;

@@ -140,6 +140,8 @@ def test_label_values_up_to_uint16_limit(engine):
     assert res[0]["Intensity_MaxIntensity"][0] == px[0, 0, 0][lab == 1].max()
     assert np.isnan(res[150]["Intensity_MeanIntensity"][0])
     assert np.isclose(res[299]["Intensity_MeanIntensity"][0], px[0, 0, 0][lab == 300].mean())
+    _, vol = process_tree_masks({"None": {"None": ["volume"]}}, [lab], px, extract_tree)
+    assert len(vol) == 300 and float(vol[149]) == 0.0 and float(vol[0]) > 0 and float(vol[299]) > 0  # cell.py's volume of an all-False mask is 0
     from aliby_amd.segment.dispatch import _to_uint16_labels
 
     with pytest.raises(OverflowError):
