@@ -58,6 +58,13 @@ static inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
 // waves would spend their time in barriers.  `work` = pixels the workgroup loops over (bbox or area).
 static inline int aliby_pick_block(long long work) { return work <= 2048 ? 64 : (work <= 8192 ? 128 : 256); }
 
+// The power of two >= n that is at least lo (a power of two): the capacity of a sort buffer for up to n values.
+static inline int aliby_pow2_at_least(int n, int lo) {
+  int p = lo;
+  while (p < n) p <<= 1;
+  return p;
+}
+
 // Row offsets [F + 1] of a volume family (aliby_features_*3d): first entry 0, non-decreasing, at most 65535 rows per stack (labels
 // are uint16).  A kernel writes row offsets[f] + L - 1 for every label L <= offsets[f + 1] - offsets[f], into scratch sized by
 // offsets[F]: other offsets would put rows past its end.

@@ -17,6 +17,7 @@
 // uint16 pixels follow NumPy integer semantics: `total` is exact, `total_squared` squares in uint16
 // (wraps modulo 65536, as `trap_image[cell_mask] ** 2` does) before an exact sum.
 #include "common.h"
+#include "object_launch.h"
 
 typedef unsigned short u16;
 
@@ -250,29 +251,9 @@ extern "C" int aliby_features_cell(aliby_ctx* ctx, const uint16_t* labels, const
   a.labels = labels; a.planes = planes; a.F = F; a.C = C; a.Y = Y; a.X = X; a.channel = channel;
   a.tab = table_dev; a.n_obj = n_obj; a.out = out; a.ld = ld; a.col0 = col0;
   a.cap_cells = ((size_t)(max_h + 2) * (max_w + 2) + 3) & ~(size_t)3;
-  int cv = 64;
-  while (cv < max_area) cv <<= 1;
-  a.cap_vals = cv;
-  const size_t need = a.cap_cells * 8 + (size_t)cv * 4;
-  hipStream_t s = as_stream(stream);
-  const bool f32 = planes && dtype == ALIBY_F32;
-  if (need <= 128 * 1024) {
-    a.gscratch = nullptr;
-    if (f32) {
-      if (need > 32 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)k_cell<float, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
-      hipLaunchKernelGGL((k_cell<float, false>), dim3(n_obj), dim3(aliby_pick_block((long long)max_h * max_w)), need, s, a);
-    } else {
-      if (need > 32 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)k_cell<u16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
-      hipLaunchKernelGGL((k_cell<u16, false>), dim3(n_obj), dim3(aliby_pick_block((long long)max_h * max_w)), need, s, a);
-    }
-  } else {
-    const int gsz = n_obj < 512 ? n_obj : 512;
-    int rc = aliby_ensure_scratch(ctx, (size_t)gsz * need);
-    if (rc) return rc;
-    a.gscratch = (unsigned char*)ctx->scratch;
-    if (f32) hipLaunchKernelGGL((k_cell<float, true>), dim3(gsz), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_cell<u16, true>), dim3(gsz), dim3(256), 0, s, a);
-  }
-  KERNEL_CHECK();
-  return ALIBY_OK;
+  a.cap_vals = aliby_pow2_at_least(max_area, 64);
+  const size_t need = a.cap_cells * 8 + (size_t)a.cap_vals * 4;
+  const int px = planes && dtype == ALIBY_F32 ? ALIBY_F32 : ALIBY_U16;  // (a mask-only call runs the uint16 kernel)
+  return object_launch(ctx, object_kernel(px, k_cell<u16, false>, k_cell<float, false>), object_kernel(px, k_cell<u16, true>, k_cell<float, true>),
+                       a, n_obj, need, 128 * 1024, (long long)max_h * max_w, as_stream(stream));
 }

@@ -18,6 +18,7 @@
 // into LDS (global scratch for objects larger than the LDS budget); every statistic is an fp64 block
 // reduction over that list; ranks come from one LDS bitonic sort per channel + binary searches.
 #include "common.h"
+#include "object_launch.h"
 #include "coloc_stats.h"
 
 typedef unsigned short u16;
@@ -442,32 +443,10 @@ extern "C" int aliby_object_ranks(aliby_ctx* ctx, const uint16_t* labels, const 
   RankArgs a;
   a.labels = labels; a.planes = planes; a.F = F; a.C = C; a.Y = Y; a.X = X; a.channel = channel; a.tab = table_dev;
   a.n_obj = n_obj; a.ranks = ranks_dev; a.rmax = rmax_dev;
-  int cap = 64;
-  while (cap < max_area) cap <<= 1;
-  a.cap = cap;
-  hipStream_t s = as_stream(stream);
-  const size_t need = (size_t)cap * 16;
-  if (need <= 96 * 1024) {
-    a.gscratch = nullptr;
-    dim3 grid(n_obj), block(aliby_pick_block(max_area));
-    if (dtype == ALIBY_U16) {
-      if (need > 32 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)k_ranks<u16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
-      hipLaunchKernelGGL((k_ranks<u16, false>), grid, block, need, s, a);
-    } else {
-      if (need > 32 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)k_ranks<float, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
-      hipLaunchKernelGGL((k_ranks<float, false>), grid, block, need, s, a);
-    }
-  } else {
-    const int g = n_obj < 512 ? n_obj : 512;
-    int rc = aliby_ensure_scratch(ctx, (size_t)g * need);
-    if (rc) return rc;
-    a.gscratch = (unsigned char*)ctx->scratch;
-    dim3 grid(g), block(256);
-    if (dtype == ALIBY_U16) hipLaunchKernelGGL((k_ranks<u16, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_ranks<float, true>), grid, block, 0, s, a);
-  }
-  KERNEL_CHECK();
-  return ALIBY_OK;
+  a.cap = aliby_pow2_at_least(max_area, 64);
+  return object_launch(ctx, object_kernel(dtype, k_ranks<u16, false>, k_ranks<float, false>),
+                       object_kernel(dtype, k_ranks<u16, true>, k_ranks<float, true>), a, n_obj, (size_t)a.cap * 16, 96 * 1024, max_area,
+                       as_stream(stream));
 }
 
 extern "C" int aliby_features_coloc(aliby_ctx* ctx, const uint16_t* labels, const void* planes, int dtype,
@@ -491,34 +470,10 @@ extern "C" int aliby_features_coloc(aliby_ctx* ctx, const uint16_t* labels, cons
   a.thr = thr_percent; a.scale_max = costes_scale_max;
   a.ranks = ranks_dev; a.rmax = rmax_dev;
   ARG_CHECK(col_rwc < 0 || (ranks_dev && rmax_dev), "rwc needs the rank planes (aliby_object_ranks)");
-  int cap = 64;
-  while (cap < max_area) cap <<= 1;
-  a.cap = cap;
-  hipStream_t s = as_stream(stream);
-  const size_t need = (size_t)cap * 16;
-  if (need <= 96 * 1024) {
-    a.gscratch = nullptr;
-    dim3 grid(n_obj), block(aliby_pick_block(max_area));
-    if (dtype == ALIBY_U16) {
-      if (need > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void*)k_coloc<u16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
-      hipLaunchKernelGGL((k_coloc<u16, false>), grid, block, need, s, a);
-    } else {
-      if (need > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void*)k_coloc<float, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
-      hipLaunchKernelGGL((k_coloc<float, false>), grid, block, need, s, a);
-    }
-  } else {
-    const int g = n_obj < 512 ? n_obj : 512;
-    int rc = aliby_ensure_scratch(ctx, (size_t)g * need);
-    if (rc) return rc;
-    a.gscratch = (unsigned char*)ctx->scratch;
-    dim3 grid(g), block(256);
-    if (dtype == ALIBY_U16) hipLaunchKernelGGL((k_coloc<u16, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_coloc<float, true>), grid, block, 0, s, a);
-  }
-  KERNEL_CHECK();
-  return ALIBY_OK;
+  a.cap = aliby_pow2_at_least(max_area, 64);
+  return object_launch(ctx, object_kernel(dtype, k_coloc<u16, false>, k_coloc<float, false>),
+                       object_kernel(dtype, k_coloc<u16, true>, k_coloc<float, true>), a, n_obj, (size_t)a.cap * 16, 96 * 1024, max_area,
+                       as_stream(stream));
 }
 
 // pairs_host: n_pairs x 6 ints (ch0, ch1, col_pearson, col_manders, col_rwc, col_costes; a column of -1 skips the metric).
@@ -559,23 +514,16 @@ extern "C" int aliby_features_coloc_pairs(aliby_ctx* ctx, const uint16_t* labels
     if (q[4] >= 0) a.any_rwc = 1;
   }
   ARG_CHECK(!a.any_rwc || (ranks_dev && rmax_dev), "rwc needs the rank planes (aliby_object_ranks)");
-  int cap = 64;
-  while (cap < max_area) cap <<= 1;
-  a.cap = cap;
-  const size_t need = (size_t)a.nch * cap * 4 * (a.any_rwc ? 2 : 1);
+  a.cap = aliby_pow2_at_least(max_area, 64);
+  const size_t need = (size_t)a.nch * a.cap * 4 * (a.any_rwc ? 2 : 1);
   if (need > 144 * 1024) {
     aliby_set_error("coloc_pairs: %zu bytes of pixel lists per object exceed the LDS budget", need);
     return ALIBY_ERR_TOO_LARGE;
   }
   hipStream_t s = as_stream(stream);
-  dim3 grid(n_obj), block(256);
-  if (dtype == ALIBY_U16) {
-    HIP_TRY(hipFuncSetAttribute((const void*)k_coloc_pairs<u16>, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-    hipLaunchKernelGGL((k_coloc_pairs<u16>), grid, block, need, s, a);
-  } else {
-    HIP_TRY(hipFuncSetAttribute((const void*)k_coloc_pairs<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-    hipLaunchKernelGGL((k_coloc_pairs<float>), grid, block, need, s, a);
-  }
+  auto k = object_kernel(dtype, k_coloc_pairs<u16>, k_coloc_pairs<float>);
+  HIP_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
+  hipLaunchKernelGGL(k, dim3(n_obj), dim3(256), need, s, a);
   KERNEL_CHECK();
   return ALIBY_OK;
 }

@@ -15,6 +15,7 @@
 // in LDS, bitonic sort in LDS for the order statistics, fp64 accumulation with a fixed
 // thread->pixel assignment so results are run-to-run deterministic.
 #include "common.h"
+#include "object_launch.h"
 
 typedef unsigned short u16;
 
@@ -27,7 +28,7 @@ struct IntensityArgs {
   const aliby_object* tab;
   int n_obj;
   int cap;          // power of two >= max area
-  float* gscratch;  // global fallback (cap floats per workgroup) or NULL -> LDS
+  unsigned char* gscratch;  // global fallback (cap + cap / 32 + 1 floats per workgroup) or NULL -> LDS
   int edge;
   double* out;
   int ld, col0;
@@ -43,7 +44,7 @@ __global__ __launch_bounds__(256) void k_intensity(IntensityArgs a) {
   __shared__ int s_cnt;
   __shared__ double s_res[5];  // lq, med, uq, mad(k), mad(k+1)
 
-  float* vals = GLOBAL ? (a.gscratch + (size_t)blockIdx.x * (a.cap + a.cap / 32 + 1)) : lds_vals;
+  float* vals = GLOBAL ? (reinterpret_cast<float*>(a.gscratch) + (size_t)blockIdx.x * (a.cap + a.cap / 32 + 1)) : lds_vals;
   unsigned int* eflag = reinterpret_cast<unsigned int*>(vals + a.cap);  // edge bit of the staged value at the same position
   const int tid = threadIdx.x;
   const size_t plane = (size_t)a.Y * a.X;
@@ -296,35 +297,9 @@ extern "C" int aliby_features_intensity(aliby_ctx* ctx, const uint16_t* labels, 
   a.labels = labels; a.planes = planes; a.F = F; a.C = C; a.Y = Y; a.X = X; a.channel = channel;
   a.tab = table_dev; a.n_obj = n_obj; a.edge = edge_measurements ? 1 : 0;
   a.out = out; a.ld = ld; a.col0 = col0;
-  int cap = 64;
-  while (cap < max_area) cap <<= 1;
-  a.cap = cap;
-  hipStream_t s = as_stream(stream);
-  const size_t lds_need = ((size_t)cap + cap / 32 + 1) * sizeof(float);  // values + one edge bit each
-  const size_t lds_cap = 128 * 1024;
-  if (lds_need <= lds_cap) {
-    a.gscratch = nullptr;
-    dim3 grid(n_obj), block(aliby_pick_block(max_area));
-    if (dtype == ALIBY_U16) {
-      if (lds_need > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void*)k_intensity<u16, false>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_need));
-      hipLaunchKernelGGL((k_intensity<u16, false>), grid, block, lds_need, s, a);
-    } else {
-      if (lds_need > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void*)k_intensity<float, false>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_need));
-      hipLaunchKernelGGL((k_intensity<float, false>), grid, block, lds_need, s, a);
-    }
-  } else {
-    int g = n_obj < 512 ? n_obj : 512;
-    int rc = aliby_ensure_scratch(ctx, (size_t)g * (cap + cap / 32 + 1) * sizeof(float));
-    if (rc) return rc;
-    a.gscratch = (float*)ctx->scratch;
-    dim3 grid(g), block(256);
-    if (dtype == ALIBY_U16) hipLaunchKernelGGL((k_intensity<u16, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_intensity<float, true>), grid, block, 0, s, a);
-  }
-  KERNEL_CHECK();
-  return ALIBY_OK;
+  a.cap = aliby_pow2_at_least(max_area, 64);
+  const size_t need = ((size_t)a.cap + a.cap / 32 + 1) * sizeof(float);  // values + one edge bit each
+  return object_launch(ctx, object_kernel(dtype, k_intensity<u16, false>, k_intensity<float, false>),
+                       object_kernel(dtype, k_intensity<u16, true>, k_intensity<float, true>), a, n_obj, need, 128 * 1024, max_area,
+                       as_stream(stream));
 }

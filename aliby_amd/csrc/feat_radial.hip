@@ -18,6 +18,7 @@
 // (object, channel).  Path lengths are kept as exact (edge steps, diagonal steps) integer pairs packed
 // in one 32-bit LDS word, so the relaxation is race-free and bit-reproducible.
 #include "common.h"
+#include "object_launch.h"
 
 typedef unsigned short u16;
 
@@ -260,22 +261,8 @@ int aliby_radial_geometry_unscaled(aliby_ctx* ctx, const uint16_t* labels, int F
   a.max_radius = maximum_radius;
   a.binmap = binmap_dev;
   a.cap_cells = ((size_t)(max_h + 2) * (max_w + 2) + 3) & ~(size_t)3;
-  const size_t need = a.cap_cells * 8;
-  hipStream_t s = as_stream(stream);
-  if (need <= 128 * 1024) {
-    a.gscratch = nullptr;
-    if (need > 32 * 1024)
-      HIP_TRY(hipFuncSetAttribute((const void*)k_radial_geometry<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
-    hipLaunchKernelGGL((k_radial_geometry<false>), dim3(n_obj), dim3(aliby_pick_block((long long)max_h * max_w)), need, s, a);
-  } else {
-    const int g = n_obj < 512 ? n_obj : 512;
-    int rc = aliby_ensure_scratch(ctx, (size_t)g * need);
-    if (rc) return rc;
-    a.gscratch = (unsigned char*)ctx->scratch;
-    hipLaunchKernelGGL((k_radial_geometry<true>), dim3(g), dim3(256), 0, s, a);
-  }
-  KERNEL_CHECK();
-  return ALIBY_OK;
+  return object_launch(ctx, k_radial_geometry<false>, k_radial_geometry<true>, a, n_obj, a.cap_cells * 8, 128 * 1024, (long long)max_h * max_w,
+                       as_stream(stream));
 }
 
 int aliby_features_radial_distribution(aliby_ctx* ctx, const uint16_t* labels, const uint8_t* binmap_dev,
@@ -304,8 +291,7 @@ int aliby_features_radial_distribution_rings(aliby_ctx* ctx, const uint16_t* lab
   a.nout = rings_out;
   a.out = out; a.ld = ld; a.col0 = col0;
   hipStream_t s = as_stream(stream);
-  if (dtype == ALIBY_U16) hipLaunchKernelGGL((k_radial_stats<u16>), dim3(n_obj), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((k_radial_stats<float>), dim3(n_obj), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(object_kernel(dtype, k_radial_stats<u16>, k_radial_stats<float>), dim3(n_obj), dim3(256), 0, s, a);
   KERNEL_CHECK();
   return ALIBY_OK;
 }

@@ -19,6 +19,7 @@
 //
 // Column layout (78, alphabetical inside each block) is mirrored by aliby_amd/extraction/features.py.
 #include "common.h"
+#include "object_launch.h"
 #include "hull.h"
 
 typedef unsigned short u16;
@@ -516,21 +517,7 @@ static int launch_hull(aliby_ctx* ctx, const uint16_t* labels, int F, int Y, int
   const size_t chain_cap = 2 * (size_t)(2 * max_h + 1) + 2;
   const size_t need = ints * sizeof(int) + 4 * chain_cap * sizeof(P2);
   a.cap_bytes = (need + 15) & ~(size_t)15;
-  if (a.cap_bytes <= 96 * 1024) {
-    a.gscratch = nullptr;
-    if (a.cap_bytes > 48 * 1024)
-      HIP_TRY(hipFuncSetAttribute((const void*)k_shape_hull<false>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.cap_bytes));
-    hipLaunchKernelGGL((k_shape_hull<false>), dim3(n_obj), dim3(aliby_pick_block((long long)max_h * max_h)), a.cap_bytes, s, a);
-  } else {
-    const int g = n_obj < 512 ? n_obj : 512;
-    int rc = aliby_ensure_scratch(ctx, (size_t)g * a.cap_bytes);
-    if (rc) return rc;
-    a.gscratch = (unsigned char*)ctx->scratch;
-    hipLaunchKernelGGL((k_shape_hull<true>), dim3(g), dim3(256), 0, s, a);
-  }
-  KERNEL_CHECK();
-  return ALIBY_OK;
+  return object_launch(ctx, k_shape_hull<false>, k_shape_hull<true>, a, n_obj, a.cap_bytes, 96 * 1024, (long long)max_h * max_h, s);
 }
 
 extern "C" int aliby_features_feret(aliby_ctx* ctx, const uint16_t* labels, int F, int Y, int X,
@@ -545,12 +532,6 @@ extern "C" int aliby_features_feret(aliby_ctx* ctx, const uint16_t* labels, int 
                      as_stream(stream));
 }
 
-static int pow2_at_least(int n, int lo) {
-  int p = lo;
-  while (p < n) p <<= 1;
-  return p;
-}
-
 extern "C" int aliby_features_sizeshape(aliby_ctx* ctx, const uint16_t* labels, int F, int Y, int X,
                                         const aliby_object* table_dev, int n_obj, int max_h, int max_w,
                                         int max_area, double* out, int ld, int col0, void* stream) {
@@ -560,51 +541,25 @@ extern "C" int aliby_features_sizeshape(aliby_ctx* ctx, const uint16_t* labels, 
   ARG_CHECK(F > 0 && Y > 0 && X > 0 && max_h >= 0 && max_w >= 0, "bad shape");
   ARG_CHECK(col0 >= 0 && col0 + SS_NCOL <= ld, "columns exceed row stride");
   hipStream_t s = as_stream(stream);
-  const size_t lds_cap = 96 * 1024;
 
   {  // core
     ShapeArgs a;
     a.labels = labels; a.F = F; a.Y = Y; a.X = X; a.tab = table_dev; a.n_obj = n_obj;
     a.out = out; a.ld = ld; a.col0 = col0;
-    const size_t need = (size_t)(max_h + 4) * (max_w + 4);
-    a.cap = (int)((need + 15) & ~(size_t)15);
-    if (need <= lds_cap) {
-      a.gscratch = nullptr;
-      if (need > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void*)k_shape_core<false>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.cap));
-      hipLaunchKernelGGL((k_shape_core<false>), dim3(n_obj), dim3(aliby_pick_block((long long)max_h * max_w)), a.cap, s, a);
-    } else {
-      const int g = n_obj < 512 ? n_obj : 512;
-      int rc = aliby_ensure_scratch(ctx, (size_t)g * a.cap);
-      if (rc) return rc;
-      a.gscratch = (unsigned char*)ctx->scratch;
-      hipLaunchKernelGGL((k_shape_core<true>), dim3(g), dim3(256), 0, s, a);
-    }
-    KERNEL_CHECK();
+    a.cap = (int)(((size_t)(max_h + 4) * (max_w + 4) + 15) & ~(size_t)15);
+    const int rc = object_launch(ctx, k_shape_core<false>, k_shape_core<true>, a, n_obj, (size_t)a.cap, 96 * 1024, (long long)max_h * max_w, s);
+    if (rc) return rc;
   }
   {  // edt radii
     EdtArgs a;
     a.labels = labels; a.F = F; a.Y = Y; a.X = X; a.tab = table_dev; a.n_obj = n_obj;
     a.out = out; a.ld = ld; a.col0 = col0;
     const size_t cells = (size_t)(max_h + 2) * (max_w + 2);
-    const size_t sortn = (size_t)pow2_at_least(max_area, 64);
+    const size_t sortn = (size_t)aliby_pow2_at_least(max_area, 64);
     const size_t need = cells * sizeof(int) + (cells > sortn ? cells : sortn) * sizeof(float);
     a.cap_bytes = (need + 15) & ~(size_t)15;
-    if (a.cap_bytes <= 128 * 1024) {
-      a.gscratch = nullptr;
-      if (a.cap_bytes > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void*)k_shape_edt<false>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.cap_bytes));
-      hipLaunchKernelGGL((k_shape_edt<false>), dim3(n_obj), dim3(aliby_pick_block((long long)max_h * max_w)), a.cap_bytes, s, a);
-    } else {
-      const int g = n_obj < 512 ? n_obj : 512;
-      int rc = aliby_ensure_scratch(ctx, (size_t)g * a.cap_bytes);
-      if (rc) return rc;
-      a.gscratch = (unsigned char*)ctx->scratch;
-      hipLaunchKernelGGL((k_shape_edt<true>), dim3(g), dim3(256), 0, s, a);
-    }
-    KERNEL_CHECK();
+    const int rc = object_launch(ctx, k_shape_edt<false>, k_shape_edt<true>, a, n_obj, a.cap_bytes, 128 * 1024, (long long)max_h * max_w, s);
+    if (rc) return rc;
   }
   return launch_hull(ctx, labels, F, Y, X, table_dev, n_obj, max_h, out, ld, col0, nullptr, 0, 0, s);
 }

@@ -17,6 +17,7 @@
 // (p_x, p_{x+y}, p_{x-y}) are integer LDS histograms, so every statistic is exact-integer counts
 // divided once by the total: no atomics on floats, run-to-run deterministic.
 #include "common.h"
+#include "object_launch.h"
 #include "haralick_stats.h"  // grey_of, the log2 table, cells -> marginals -> the 13 statistics (shared with feat_texture3d.hip)
 
 typedef unsigned short u16;
@@ -252,34 +253,13 @@ extern "C" int aliby_features_texture(aliby_ctx* ctx, const uint16_t* labels, co
   a.grey_shift = dtype == ALIBY_U8W ? 0 : 8;
   if (dtype == ALIBY_U8W) dtype = ALIBY_U16;
   a.cap_pix = (int)(((size_t)max_h * max_w + 15) & ~(size_t)15);
-  int ck = 2048;  // >= 4096 16-bit cells for the direct-counting path (K <= 90 distinct grey levels)
-  while (ck < max_area) ck <<= 1;
+  const int ck = aliby_pow2_at_least(max_area, 2048);  // >= 4096 16-bit cells for the direct-counting path (K <= 90 distinct grey levels)
   a.cap_keys = ck;
   a.cap_cells = max_area < 65536 ? 2 * ck : 0;
   const size_t need = (size_t)a.cap_pix + (size_t)ck * 4;
   hipStream_t s = as_stream(stream);
   { const int rc = haralick_log2_table_ready(ctx, s); if (rc) return rc; }
-  if (need <= 96 * 1024) {
-    a.gscratch = nullptr;
-    dim3 grid(n_obj), block(aliby_pick_block((long long)max_h * max_w));
-    if (dtype == ALIBY_U16) {
-      if (need > 32 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void*)k_texture<u16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
-      hipLaunchKernelGGL((k_texture<u16, false>), grid, block, need, s, a);
-    } else {
-      if (need > 32 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void*)k_texture<float, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
-      hipLaunchKernelGGL((k_texture<float, false>), grid, block, need, s, a);
-    }
-  } else {
-    const int g = n_obj < 512 ? n_obj : 512;
-    int rc = aliby_ensure_scratch(ctx, (size_t)g * need);
-    if (rc) return rc;
-    a.gscratch = (unsigned char*)ctx->scratch;
-    dim3 grid(g), block(256);
-    if (dtype == ALIBY_U16) hipLaunchKernelGGL((k_texture<u16, false ? false : true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_texture<float, true>), grid, block, 0, s, a);
-  }
-  KERNEL_CHECK();
-  return ALIBY_OK;
+  return object_launch(ctx, object_kernel(dtype, k_texture<u16, false>, k_texture<float, false>),
+                       object_kernel(dtype, k_texture<u16, true>, k_texture<float, true>), a, n_obj, need, 96 * 1024,
+                       (long long)max_h * max_w, s);
 }

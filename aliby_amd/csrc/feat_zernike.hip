@@ -14,6 +14,7 @@
 // The minimum enclosing circle is computed exactly on the convex-hull vertices with the
 // Elzinga-Hearn iteration; every step's "farthest vertex" search is a block-wide reduction.
 #include "common.h"
+#include "object_launch.h"
 #include "hull.h"
 
 typedef unsigned short u16;
@@ -508,21 +509,7 @@ int aliby_object_mec(aliby_ctx* ctx, const uint16_t* labels, int F, int Y, int X
   a.labels = labels; a.F = F; a.Y = Y; a.X = X; a.tab = table_dev; a.n_obj = n_obj; a.max_h = max_h; a.mec = mec_dev;
   const size_t need = 2 * (size_t)max_h * sizeof(int) + 2 * (size_t)(2 * max_h + 2) * sizeof(P2);
   a.cap_bytes = (need + 15) & ~(size_t)15;
-  hipStream_t s = as_stream(stream);
-  if (a.cap_bytes <= 96 * 1024) {
-    a.gscratch = nullptr;
-    if (a.cap_bytes > 48 * 1024)
-      HIP_TRY(hipFuncSetAttribute((const void*)k_mec<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.cap_bytes));
-    hipLaunchKernelGGL((k_mec<false>), dim3(n_obj), dim3(aliby_pick_block((long long)max_h * max_h)), a.cap_bytes, s, a);
-  } else {
-    const int g = n_obj < 512 ? n_obj : 512;
-    int rc = aliby_ensure_scratch(ctx, (size_t)g * a.cap_bytes);
-    if (rc) return rc;
-    a.gscratch = (unsigned char*)ctx->scratch;
-    hipLaunchKernelGGL((k_mec<true>), dim3(g), dim3(256), 0, s, a);
-  }
-  KERNEL_CHECK();
-  return ALIBY_OK;
+  return object_launch(ctx, k_mec<false>, k_mec<true>, a, n_obj, a.cap_bytes, 96 * 1024, (long long)max_h * max_h, as_stream(stream));
 }
 
 int aliby_features_zernike(aliby_ctx* ctx, const uint16_t* labels, const void* planes, int dtype, int F, int C,

@@ -166,7 +166,8 @@ class _FanOut:
     """Per-object kernels are one small workgroup per object: latency-bound and far from filling 256 CUs, so
     independent instructions (different channels / families / channel pairs) go to a few side HIP streams and run
     concurrently.  fork(): side streams wait for the main stream; join(): the main stream waits for them.  Only
-    taken when every object window is LDS-resident (the global-scratch variants share the context's scratch)."""
+    taken when every object window is LDS-resident: a global-scratch launch borrows the context's scratch, so only one may be
+    in flight per context (the rule, and what this condition does and does not guarantee: aliby_amd/csrc/object_launch.h)."""
 
     def __init__(self, eng, table, out):
         import os
