@@ -1,6 +1,6 @@
 // object_launch.h — the launch front end of the 2-D feature kernels that work on one object per workgroup (feat_intensity.hip,
-// feat_texture.hip, feat_coloc.hip, feat_cell.hip, feat_shape.hip, feat_zernike.hip, feat_radial.hip).  Host side only; the
-// counterpart of volume_launch in volume_table.h.
+// feat_texture.hip, feat_coloc.hip, feat_cell.hip, feat_shape.hip, feat_zernike.hip, feat_radial.hip, feat_localisation.hip).
+// Host side only; the counterpart of volume_launch in volume_table.h.
 //
 // Every such kernel exists in two forms, <GLOBAL = false> and <GLOBAL = true>, with one argument struct that carries
 // `unsigned char* gscratch`:

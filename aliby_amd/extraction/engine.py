@@ -623,6 +623,33 @@ class FeatureEngine:
             )
         return out
 
+    def nuc_est_conv(self, labels, planes, dtype, channel, table: ObjectTable, out, col0, alpha=0.95, object_radius_estimation=0.085,
+                     gaussian_sigma=None, median=None):
+        """Column col0 of out [n_obj, .]: nuc_est_conv of the reference (custom/localisation.py:75-120) for `channel` of planes
+        [F,C,Y,X].  alpha / object_radius_estimation None: the defaults, as there; gaussian_sigma None: derived per object.
+        `median`: the objects' medians, float64 [n_obj] on the device (column `median` of cell_metrics, which is where they are
+        taken from when not given)."""
+        F, Cn, Y, X = planes.shape
+        alpha = 0.95 if alpha is None else float(alpha)
+        ore = 0.085 if object_radius_estimation is None else float(object_radius_estimation)
+        if gaussian_sigma is not None and not (float(gaussian_sigma) > 0.0 and np.isfinite(float(gaussian_sigma))):
+            raise ValueError(f"gaussian_sigma must be positive and finite, got {gaussian_sigma!r} (the reference divides by it)")
+        if median is None:
+            median = self.cell_metrics(labels, planes, dtype, channel, table)[:, self.CELL_COLUMNS.index("median")]
+        median = median.contiguous()
+        if median.dtype != torch.float64 or median.numel() < table.n_obj:
+            raise ValueError("median must hold one float64 per object")
+        with self.timed("nuc_est_conv"):
+            _lib.check(
+                self.lib.aliby_features_nuc_est_conv(
+                    self.ctx.handle, _ptr(labels), _ptr(planes), _kdt(dtype), F, Cn, Y, X, int(channel), _ptr(table.dev), table.n_obj,
+                    table.max_h, table.max_w, table.max_area, _ptr(median), alpha, ore,
+                    0.0 if gaussian_sigma is None else float(gaussian_sigma), _ptr(out), out.stride(0) if table.n_obj else max(col0 + 1, 1),
+                    col0, _stream_ptr(),
+                )
+            )
+        return 1
+
     def cell_ratio(self, labels, planes, dtype, ch0, ch1, table: ObjectTable) -> torch.Tensor:
         """[n_obj] float64: cell.ratio of the reference (cell.py:268-279) for the channel pair (ch0, ch1) of planes [F,C,Y,X]."""
         F, Cn, Y, X = planes.shape

@@ -138,6 +138,23 @@ for _m in _CELL_PIXELS:
     MONO[_m] = dict(names=lambda kw: None, launch=_make_cell_launch(_m), needs_pixels=True, cell=True)
 
 
+def _launch_nuc_est_conv(eng, labels, table, plane, dt, ch, out, col0, kw, cell_cache=None):
+    # custom/localisation.py, with its defaults (an entry of cp_measure_kwargs named after an in-repo function is not looked at).
+    # The median it subtracts is a column of the (plane, channel)'s cell.py block, shared with the metrics above.
+    if plane is None:
+        raise Exception("nuc_est_conv needs the pixels of a channel")
+    key = (plane.data_ptr(), ch)
+    if cell_cache is None:
+        cell_cache = {}
+    if key not in cell_cache:
+        cell_cache[key] = eng.cell_metrics(labels, plane, dt, ch, table)
+    eng.nuc_est_conv(labels, plane, dt, ch, table, out, col0, median=cell_cache[key][:, eng.CELL_COLUMNS.index("median")])
+
+
+# An extension of this fork's registry: the reference reaches the function through its custom loader, not load_cellfuns_core.
+MONO["nuc_est_conv"] = dict(names=lambda kw: None, launch=_launch_nuc_est_conv, needs_pixels=True, cell=True)
+
+
 def _launch_ratio(eng, labels, table, plane, dt, ch, out, col0, kw):
     # cell.ratio needs a [Y, X, 2] image (cell.py:270); the extraction path hands every metric ONE z-reduced plane, so the
     # reference returns NaN for every object here.  The two-channel form is FeatureEngine.cell_ratio / functions.ratio.

@@ -2,13 +2,15 @@
 The reference's in-repo functions that are not reached through the feature tree, with their own signatures:
 
   ratio(cell_mask, trap_image)            src/extraction/core/functions/cell.py:268-279
+  nuc_est_conv(cell_mask, trap_image, ..) src/extraction/core/functions/custom/localisation.py:75-120
   imBackground(cell_masks, trap_image)    src/extraction/core/functions/trap.py:6-23
   background_max5(cell_masks, trap_image) src/extraction/core/functions/trap.py:26-43
 
   reduce_z(trap_image, fun, axis=0)       src/extraction/core/functions/distributors.py:6-24
 
-Host arrays in, Python floats (reduce_z: a NumPy array of NumPy's own result dtype) out, the arithmetic in csrc/feat_extra.hip (batched forms: FeatureEngine.cell_ratio /
-FeatureEngine.trap_background, which take a whole [F,Y,X] label stack).  No CPU fallback.
+Host arrays in, Python floats (reduce_z: a NumPy array of NumPy's own result dtype) out, the arithmetic in csrc/feat_extra.hip and
+csrc/feat_localisation.hip (batched forms: FeatureEngine.cell_ratio / FeatureEngine.nuc_est_conv / FeatureEngine.trap_background,
+which take a whole [F,Y,X] label stack).  No CPU fallback.
 """
 
 from __future__ import annotations
@@ -40,6 +42,25 @@ def ratio(cell_mask, trap_image) -> float:
     if table.n_obj == 0:
         return float("nan")  # np.median of an empty selection
     return float(eng.cell_ratio(labels, planes, dt, 0, 1, table)[0])
+
+
+def nuc_est_conv(cell_mask, trap_image, alpha=0.95, object_radius_estimation=0.085, gaussian_filter_shape=None, gaussian_sigma=None) -> float:
+    """Nuclear localisation of one cell: the maximum of its median-subtracted pixels convolved with a Gaussian sized to the
+    expected nucleus, normalised (localisation.py:75-120).  gaussian_filter_shape is accepted and ignored: the reference
+    overwrites it with (2 ceil(2 r) + 1,) * 2.  NaN for an empty mask and for a cell without a non-zero pixel."""
+    trap_image = _as_pixels(trap_image)
+    if trap_image.ndim != 2:
+        raise ValueError(f"trap_image must be [Y, X], got shape {trap_image.shape}")
+    eng = FeatureEngine()
+    labels = to_device_u16(np.asarray(cell_mask, dtype=bool).astype(np.uint16)[None])
+    planes, dt = to_device_planes(trap_image[None, None])  # [1, 1, Y, X]
+    table = eng.object_table(labels)
+    if table.n_obj == 0:
+        return float("nan")  # np.median of an empty selection
+    out = eng.new_output(1, 1)
+    eng.nuc_est_conv(labels, planes, dt, 0, table, out, 0, alpha=alpha, object_radius_estimation=object_radius_estimation,
+                     gaussian_sigma=gaussian_sigma)
+    return float(out[0, 0])
 
 
 def _background(cell_masks, trap_image):

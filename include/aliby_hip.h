@@ -435,6 +435,17 @@ int aliby_features_cell(aliby_ctx* ctx, const uint16_t* labels, const void* plan
 int aliby_features_cell_ratio(aliby_ctx* ctx, const uint16_t* labels, const void* planes, int dtype, int F, int C, int Y,
                               int X, int channel0, int channel1, const aliby_object* table_dev, int n_obj, int max_area,
                               double* out, void* stream);
+/* custom/localisation.py:75-120, nuc_est_conv: out[row * ld + col0] = the maximum over the tile of the object's median-subtracted
+ * pixels (0 outside the object) convolved ("same") with a Gaussian sized to the expected nucleus, divided by
+ * sum(h^2) alpha pi chi sigma^2, where N = the object's non-zero pixels, r = sqrt(object_radius_estimation N / pi), the filter
+ * half-width ceil(2 r), chi = -2 ln(1 - alpha) and sigma = gaussian_sigma, or r / sqrt(chi) when gaussian_sigma <= 0.
+ * median_dev [dev] holds one float64 per object: its np.median (column 10 of aliby_features_cell).  NaN for an absent label and,
+ * with a derived sigma, for an object without a non-zero pixel.  alpha outside (0, 1), object_radius_estimation <= 0 or a
+ * non-finite gaussian_sigma is ALIBY_ERR_INVALID.  Working set and launch forms: csrc/feat_localisation.hip. */
+int aliby_features_nuc_est_conv(aliby_ctx* ctx, const uint16_t* labels, const void* planes, int dtype, int F, int C, int Y,
+                                int X, int channel, const aliby_object* table_dev, int n_obj, int max_h, int max_w,
+                                int max_area, const double* median_dev, double alpha, double object_radius_estimation,
+                                double gaussian_sigma, double* out, int ld, int col0, void* stream);
 /* trap.imBackground / trap.background_max5 (src/extraction/core/functions/trap.py:6-43): per tile, over the pixels of
  * `channel` under NO mask (labels == 0): out[f*2] = their median (numpy.median), out[f*2+1] = the mean of the five largest
  * (of all of them when fewer); NaN for a tile without background. */
