@@ -650,6 +650,25 @@ class FeatureEngine:
             )
         return 1
 
+    def nuc_conv_3d(self, labels, stack, dtype, channel, table: ObjectTable, out, col0, pixel_size=0.23, z_spacing=0.6):
+        """Column col0 of out [n_obj, .]: nuc_conv_3d of the reference (custom/localisation.py:123-140) for `channel` of the
+        un-reduced stack [F,C,Z,Y,X]; the objects' 2-D masks are repeated on every plane.  The median and the non-zero count are
+        found in the kernel."""
+        if stack.ndim != 5:
+            raise ValueError(f"stack must be [F,C,Z,Y,X], got shape {tuple(stack.shape)}")
+        F, Cn, Z, Y, X = stack.shape
+        if tuple(labels.shape) != (F, Y, X):
+            raise ValueError(f"labels {tuple(labels.shape)} do not match the stack's [F,Y,X] = {(F, Y, X)}")
+        with self.timed("nuc_conv_3d"):
+            _lib.check(
+                self.lib.aliby_features_nuc_conv_3d(
+                    self.ctx.handle, _ptr(labels), _ptr(stack), _kdt(dtype), F, Cn, Z, Y, X, int(channel), _ptr(table.dev), table.n_obj,
+                    table.max_h, table.max_w, table.max_area, float(pixel_size), float(z_spacing), _ptr(out),
+                    out.stride(0) if table.n_obj else max(col0 + 1, 1), col0, _stream_ptr(),
+                )
+            )
+        return 1
+
     def cell_ratio(self, labels, planes, dtype, ch0, ch1, table: ObjectTable) -> torch.Tensor:
         """[n_obj] float64: cell.ratio of the reference (cell.py:268-279) for the channel pair (ch0, ch1) of planes [F,C,Y,X]."""
         F, Cn, Y, X = planes.shape

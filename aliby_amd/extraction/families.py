@@ -101,7 +101,7 @@ def _launch_granularity(eng, labels, table, plane, dt, ch, out, col0, kw, **_):
 
 _GRANULARITY_KWARGS = ("subsample_size", "image_sample_size", "element_size", "granular_spectrum_length", "image_mask", "mask_order")
 
-# name -> {names(kw) -> list[str] | None (scalar), launch, needs_pixels}
+# name -> {names(kw) -> list[str] | None (scalar), launch, needs_pixels[, cell, stack]}
 MONO = {
     "intensity": dict(names=lambda kw: feat.intensity_names(kw.get("edge_measurements", True)),
                       launch=_launch_intensity, needs_pixels=True),
@@ -153,6 +153,18 @@ def _launch_nuc_est_conv(eng, labels, table, plane, dt, ch, out, col0, kw, cell_
 
 # An extension of this fork's registry: the reference reaches the function through its custom loader, not load_cellfuns_core.
 MONO["nuc_est_conv"] = dict(names=lambda kw: None, launch=_launch_nuc_est_conv, needs_pixels=True, cell=True)
+
+
+def _launch_nuc_conv_3d(eng, labels, table, stack, dt, ch, out, col0, kw, cell_cache=None):
+    # custom/localisation.py:123-140, with its defaults.  `stack` is the un-reduced [F,C,Z,Y,X] block (see `stack=True` below).
+    eng.nuc_conv_3d(labels, stack, dt, ch, table, out, col0)
+
+
+# Another extension.  `stack=True`: the metric is handed the un-reduced stack instead of one z-reduced plane, and is valid only
+# under a channel with the reducer key "None", ALIBY's spelling of "do not reduce" (the reference's reduce_z raises on it, and
+# upstream reaches the function through its custom loader).  Every other metric under "None" keeps raising "invalid reducer".
+# `cell=True`: launched on the main stream after the fan-out has joined, since large objects take the global-scratch form.
+MONO["nuc_conv_3d"] = dict(names=lambda kw: None, launch=_launch_nuc_conv_3d, needs_pixels=True, cell=True, stack=True)
 
 
 def _launch_ratio(eng, labels, table, plane, dt, ch, out, col0, kw):
@@ -270,6 +282,9 @@ def evaluate(eng, labels, table, planes, instructions, cp_measure_kwargs, multi=
         unbuilt = sorted(set(kw) - set(BUILT_KWARGS.get(metric, ()))) if metric in CP_MEASURE_NAMES else ()
         if unbuilt:
             raise NotImplementedError(f"cp_measure_kwargs[{metric!r}]: {unbuilt} not built (built: {sorted(BUILT_KWARGS.get(metric, ()))})")
+        if reg[metric].get("stack") and (inst[0] == "None" or inst[1] != "None"):
+            raise Exception(f"{metric} needs the un-reduced stack of a channel: list it under a channel with the reducer key "
+                            f"'None', not under {inst[0]!r} / {inst[1]!r}")
         names = reg[metric]["names"](kw)
         blocks.append((col, names))
         specs.append((inst, reg[metric], kw, col, 1 if names is None else len(names)))
@@ -388,7 +403,11 @@ def evaluate(eng, labels, table, planes, instructions, cp_measure_kwargs, multi=
     for inst, reg, kw, col0, ncols in after:
         ch, red_z = inst[0], inst[1]
         extra = {"cell_cache": cell_cache}
-        if ch == "None" or not reg["needs_pixels"]:
+        if reg.get("stack"):
+            if cache is None:
+                raise Exception("pixels are required for this instruction")
+            reg["launch"](eng, labels, table, cache.tensor, cache.dtype, ch, out, col0, kw, **extra)
+        elif ch == "None" or not reg["needs_pixels"]:
             if ch != "None" and cache is not None:
                 cache.get(red_z)
             reg["launch"](eng, labels, table, None, 0, None, out, col0, kw, **extra)

@@ -3,14 +3,15 @@ The reference's in-repo functions that are not reached through the feature tree,
 
   ratio(cell_mask, trap_image)            src/extraction/core/functions/cell.py:268-279
   nuc_est_conv(cell_mask, trap_image, ..) src/extraction/core/functions/custom/localisation.py:75-120
+  nuc_conv_3d(cell_mask, trap_image, ..)  src/extraction/core/functions/custom/localisation.py:123-140
   imBackground(cell_masks, trap_image)    src/extraction/core/functions/trap.py:6-23
   background_max5(cell_masks, trap_image) src/extraction/core/functions/trap.py:26-43
 
   reduce_z(trap_image, fun, axis=0)       src/extraction/core/functions/distributors.py:6-24
 
 Host arrays in, Python floats (reduce_z: a NumPy array of NumPy's own result dtype) out, the arithmetic in csrc/feat_extra.hip and
-csrc/feat_localisation.hip (batched forms: FeatureEngine.cell_ratio / FeatureEngine.nuc_est_conv / FeatureEngine.trap_background,
-which take a whole [F,Y,X] label stack).  No CPU fallback.
+csrc/feat_localisation.hip (batched forms: FeatureEngine.cell_ratio / FeatureEngine.nuc_est_conv / FeatureEngine.nuc_conv_3d /
+FeatureEngine.trap_background, which take a whole [F,Y,X] label stack).  No CPU fallback.
 """
 
 from __future__ import annotations
@@ -60,6 +61,27 @@ def nuc_est_conv(cell_mask, trap_image, alpha=0.95, object_radius_estimation=0.0
     out = eng.new_output(1, 1)
     eng.nuc_est_conv(labels, planes, dt, 0, table, out, 0, alpha=alpha, object_radius_estimation=object_radius_estimation,
                      gaussian_sigma=gaussian_sigma)
+    return float(out[0, 0])
+
+
+def nuc_conv_3d(cell_mask, trap_image, pixel_size=0.23, z_spacing=0.6) -> float:
+    """Nuclear localisation of one cell over a Z stack: cell_mask [Y, X] is repeated on every plane of trap_image [Z, Y, X], and
+    the maximum of the median-subtracted voxels convolved with the reference's 3-D Gaussian, sized to the expected nucleus, is
+    normalised (localisation.py:123-140).  NaN for an empty mask and for a cell without a non-zero voxel."""
+    trap_image = _as_pixels(trap_image)
+    if trap_image.ndim != 3:
+        raise ValueError(f"trap_image must be [Z, Y, X], got shape {trap_image.shape}")
+    cell_mask = np.asarray(cell_mask, dtype=bool)
+    if cell_mask.shape != trap_image.shape[1:]:
+        raise ValueError(f"cell_mask {cell_mask.shape} does not match the planes of trap_image {trap_image.shape}")
+    eng = FeatureEngine()
+    labels = to_device_u16(cell_mask.astype(np.uint16)[None])
+    stack, dt = to_device_planes(trap_image[None, None])  # [1, 1, Z, Y, X]
+    table = eng.object_table(labels)
+    if table.n_obj == 0:
+        return float("nan")  # np.median of an empty selection
+    out = eng.new_output(1, 1)
+    eng.nuc_conv_3d(labels, stack, dt, 0, table, out, 0, pixel_size=pixel_size, z_spacing=z_spacing)
     return float(out[0, 0])
 
 

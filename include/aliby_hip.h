@@ -446,6 +446,17 @@ int aliby_features_nuc_est_conv(aliby_ctx* ctx, const uint16_t* labels, const vo
                                 int X, int channel, const aliby_object* table_dev, int n_obj, int max_h, int max_w,
                                 int max_area, const double* median_dev, double alpha, double object_radius_estimation,
                                 double gaussian_sigma, double* out, int ld, int col0, void* stream);
+/* custom/localisation.py:123-140, nuc_conv_3d: the Z-stack sibling of nuc_est_conv.  stack is [F,C,Z,Y,X] (ALIBY_U16 or ALIBY_F32);
+ * the object's 2-D mask is repeated on every plane.  out[row * ld + col0] = the maximum over the [Z,Y,X] stack of the object's
+ * median-subtracted voxels (0 off the mask) convolved ("same") with the reference's gauss3D of half-width ceil(2 r) on all three
+ * axes, divided by sum(h^2) 0.95 pi chi sd^2, where N = the object's non-zero voxels, r = sqrt(0.085 N / pi),
+ * chi = -2 ln(0.05), sd = r / sqrt(chi); the filter's exponents are x^2 / (2 sd), y^2 / (2 sd), z^2 / (2 sd z_spacing / pixel_size),
+ * as the reference writes them.  N and the median are found in the kernel.  NaN for an absent label and for an object without a
+ * non-zero voxel.  Z < 1, or a pixel_size or z_spacing that is not positive and finite, is ALIBY_ERR_INVALID.  Working set and
+ * launch forms: csrc/feat_localisation.hip. */
+int aliby_features_nuc_conv_3d(aliby_ctx* ctx, const uint16_t* labels, const void* stack, int dtype, int F, int C, int Z, int Y,
+                               int X, int channel, const aliby_object* table_dev, int n_obj, int max_h, int max_w, int max_area,
+                               double pixel_size, double z_spacing, double* out, int ld, int col0, void* stream);
 /* trap.imBackground / trap.background_max5 (src/extraction/core/functions/trap.py:6-43): per tile, over the pixels of
  * `channel` under NO mask (labels == 0): out[f*2] = their median (numpy.median), out[f*2+1] = the mean of the five largest
  * (of all of them when fewer); NaN for a tile without background. */
