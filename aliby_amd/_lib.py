@@ -23,6 +23,7 @@ U16, F32 = 0, 1
 U8W = 4  # uint8 / bool pixels in uint16 storage: texture's grey level is the value itself (ALIBY_U8W)
 U64, F64 = 2, 3  # aliby_reduce_z output dtypes (NumPy's result types for uint16 add / divide)
 RED_MAX, RED_ADD, RED_DIV = 0, 1, 2
+CROP_CLIP, CROP_8BIT, CROP_STD = 1, 2, 4  # stages of aliby_crop_tiles_u16 (ALIBY_CROP_*)
 
 
 class AlibyHipError(RuntimeError):
@@ -77,6 +78,10 @@ _SIGNATURES = {
     "aliby_stream_sync": (_i, [_vp, _vp]),
     "aliby_crop_pad_u16": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "aliby_reduce_z": (_i, [_vp, _vp, _i, _sz, _i, _sz, _i, _vp, _i, _vp]),
+    "aliby_crop_tiles_u16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, C.c_double, _vp, _i, _vp, _vp]),
+    "aliby_crop_hist_u16": (_i, [_vp, _vp, _i, _sz, _vp, _vp]),
+    "aliby_crop_stats": (_i, [_vp, _vp, _i, _sz, _i, C.c_double, _vp, _vp]),
+    "aliby_crop_cut_u16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "aliby_label_max": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "aliby_object_table": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "aliby_relabel_sequential": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),

@@ -100,6 +100,29 @@ int aliby_crop_pad_u16(aliby_ctx* ctx, const uint16_t* stack, int C, int Z, int 
 int aliby_reduce_z(aliby_ctx* ctx, const void* in, int dtype, size_t outer, int Z, size_t inner,
                    int op, void* out, int out_dtype, void* stream);
 
+/* ---- crop tiler ------------------------------------------------------------ */
+/* CropTiler.get_fczyx (src/aliby/tile/tiler.py:75-189): per-channel whole-frame normalisation, then a grid of
+ * non-overlapping tile_size x tile_size tiles, n_th = (Y - ts) / ts + 1 by n_tw = (X - ts) / ts + 1 (remainder rows and
+ * columns dropped; a tile larger than the frame: no tile, nothing written).  Stages, in this order, each optional: */
+enum { ALIBY_CROP_CLIP = 1 /* clip_outliers: (v - pmin) / (pmax - pmin) clipped to [0, 1] */,
+       ALIBY_CROP_8BIT = 2 /* convert_8bit: trunc(x * 255) as uint8; on raw integers (v * 255) mod 256, as NumPy wraps */,
+       ALIBY_CROP_STD = 4 /* standard_scale: (x - mean) / std, population std */ };
+/* stack [dev] is uint16 [C,Z,Y,X], out [dev] is [n_th * n_tw, C, Z, ts, ts] of out_dtype: ALIBY_U16 while no float stage is
+ * on (raw crop; 8-bit results as 8-bit-in-uint16), else ALIBY_F64 (the reference's values) or ALIBY_F32 (those rounded once).
+ * pmin / pmax are NumPy's percentile(method="linear") at clip and 100 - clip per channel (clip <= 0: min / max), mean and std
+ * those of the values after the earlier stages; a constant channel gives NaN (0 / 0) in float outputs and 0 after the 8-bit
+ * cast.  stats_out [dev, C x 4 float64, may be NULL] receives (pmin, pmax, mean, std), NaN where a stage is off.  Everything
+ * runs on the device in stream order; histogram and statistics use ctx scratch.  Z*Y*X < 2^32. */
+int aliby_crop_tiles_u16(aliby_ctx* ctx, const uint16_t* stack, int C, int Z, int Y, int X, int tile_size, int flags,
+                         double clip, void* out, int out_dtype, double* stats_out, void* stream);
+/* Its three parts.  hist [dev] is [C,65536] uint32 counts of stack [C, n] (zeroed here; integer atomics: independent of the
+ * launch geometry); stats [dev] [C,4] from such a histogram; the tile pass with given statistics (NULL when flags has neither
+ * ALIBY_CROP_CLIP nor ALIBY_CROP_STD). */
+int aliby_crop_hist_u16(aliby_ctx* ctx, const uint16_t* stack, int C, size_t n, uint32_t* hist, void* stream);
+int aliby_crop_stats(aliby_ctx* ctx, const uint32_t* hist, int C, size_t n, int flags, double clip, double* stats, void* stream);
+int aliby_crop_cut_u16(aliby_ctx* ctx, const uint16_t* stack, int C, int Z, int Y, int X, int tile_size, int flags,
+                       const double* stats, void* out, int out_dtype, void* stream);
+
 /* ---- a7/a8: object table (replaces transform_2d_to_3d) ------------------ */
 /* process_tree_masks enumerates labels 1..mask.max() per tile
  * (extract.py:276-281); transform_2d_to_3d (agora/utils/masks.py:35-37) explodes
