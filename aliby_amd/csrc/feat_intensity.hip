@@ -269,7 +269,7 @@ __global__ __launch_bounds__(256) void k_intensity(IntensityArgs a) {
       out[k++] = s_res[2];
       out[k++] = cmi_x;
       out[k++] = cmi_y;
-      out[k++] = 0.0;
+      out[k++] = SV == 0.0 ? NAN : 0.0;  // 0 * SV / SV (mesh_z == 0 on a plane): 0 / 0 on an all-zero object, like X and Y
       out[k++] = (double)(AMAX % a.X);
       out[k++] = (double)(AMAX / a.X);
       out[k++] = 0.0;
