@@ -38,43 +38,45 @@ __device__ __forceinline__ double bilinear(LoadF load, int n0, int n1, double y,
   return (a * (1.0 - fx) + b * fx) * (1.0 - fy) + (c * (1.0 - fx) + d * fx) * fy;
 }
 
+// The four sampling kernels below take their positions as i / size, as the reference divides: i * (1 / size) can differ in the
+// last place, which at the far edge decides between the pixel and 0 (size 0.7 at 61, 121, 241 pixels, ...).
 template <typename T>
-__global__ void k_gran_sample_frame(const T* __restrict__ planes, int C, int channel, GranGeom g, double inv, double* __restrict__ dst) {
+__global__ void k_gran_sample_frame(const T* __restrict__ planes, int C, int channel, GranGeom g, double size, double* __restrict__ dst) {
   const size_t total = (size_t)g.F * g.sh * g.sw, plane = (size_t)g.Y * g.X;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int x = (int)(i % g.sw), y = (int)((i / g.sw) % g.sh), f = (int)(i / ((size_t)g.sw * g.sh));
     const T* p = planes + ((size_t)f * C + channel) * plane;
-    dst[i] = bilinear([&](int yy, int xx) { return (double)px_load<T>(p, (size_t)yy * g.X + xx); }, g.Y, g.X, (double)y * inv, (double)x * inv);
+    dst[i] = bilinear([&](int yy, int xx) { return (double)px_load<T>(p, (size_t)yy * g.X + xx); }, g.Y, g.X, (double)y / size, (double)x / size);
   }
 }
 
 // mask of the subsampled frame when the image mask is "objects": bilinear sample of (labels > 0) > 0.9 (mask_order = 1)
-__global__ void k_gran_sample_mask(const u16* __restrict__ labels, GranGeom g, double inv, unsigned char* __restrict__ dst) {
+__global__ void k_gran_sample_mask(const u16* __restrict__ labels, GranGeom g, double size, unsigned char* __restrict__ dst) {
   const size_t total = (size_t)g.F * g.sh * g.sw, plane = (size_t)g.Y * g.X;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int x = (int)(i % g.sw), y = (int)((i / g.sw) % g.sh), f = (int)(i / ((size_t)g.sw * g.sh));
     const u16* p = labels + (size_t)f * plane;
-    dst[i] = bilinear([&](int yy, int xx) { return p[(size_t)yy * g.X + xx] ? 1.0 : 0.0; }, g.Y, g.X, (double)y * inv, (double)x * inv) > 0.9;
+    dst[i] = bilinear([&](int yy, int xx) { return p[(size_t)yy * g.X + xx] ? 1.0 : 0.0; }, g.Y, g.X, (double)y / size, (double)x / size) > 0.9;
   }
 }
 
-// generic [F,h,w] double -> [F,h2,w2] double resample at (i, j) * scale (order 1)
-__global__ void k_gran_resample(const double* __restrict__ src, int F, int h, int w, int h2, int w2, double sy, double sx,
+// generic [F,h,w] double -> [F,h2,w2] double resample at (i, j) / size (order 1)
+__global__ void k_gran_resample(const double* __restrict__ src, int F, int h, int w, int h2, int w2, double size,
                                 double* __restrict__ dst) {
   const size_t total = (size_t)F * h2 * w2;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int x = (int)(i % w2), y = (int)((i / w2) % h2), f = (int)(i / ((size_t)w2 * h2));
     const double* p = src + (size_t)f * h * w;
-    dst[i] = bilinear([&](int yy, int xx) { return p[(size_t)yy * w + xx]; }, h, w, (double)y * sy, (double)x * sx);
+    dst[i] = bilinear([&](int yy, int xx) { return p[(size_t)yy * w + xx]; }, h, w, (double)y / size, (double)x / size);
   }
 }
-__global__ void k_gran_resample_mask(const unsigned char* __restrict__ src, int F, int h, int w, int h2, int w2, double sy, double sx,
+__global__ void k_gran_resample_mask(const unsigned char* __restrict__ src, int F, int h, int w, int h2, int w2, double size,
                                      unsigned char* __restrict__ dst) {
   const size_t total = (size_t)F * h2 * w2;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int x = (int)(i % w2), y = (int)((i / w2) % h2), f = (int)(i / ((size_t)w2 * h2));
     const unsigned char* p = src + (size_t)f * h * w;
-    dst[i] = bilinear([&](int yy, int xx) { return (double)p[(size_t)yy * w + xx]; }, h, w, (double)y * sy, (double)x * sx) > 0.9;
+    dst[i] = bilinear([&](int yy, int xx) { return (double)p[(size_t)yy * w + xx]; }, h, w, (double)y / size, (double)x / size) > 0.9;
   }
 }
 
@@ -256,16 +258,14 @@ extern "C" int aliby_features_granularity(aliby_ctx* ctx, const uint16_t* labels
   unsigned char* bmsk = image_mask_objects ? w : nullptr;
 
   // 1. subsample (bufA = sub)
-  const double inv = subsample_size < 1 ? 1.0 / subsample_size : 1.0;
-  if (dtype == ALIBY_U16) hipLaunchKernelGGL((k_gran_sample_frame<u16>), dim3(grid_for(ns)), dim3(256), 0, s, (const u16*)planes, C, channel, g, inv, bufA);
-  else hipLaunchKernelGGL((k_gran_sample_frame<float>), dim3(grid_for(ns)), dim3(256), 0, s, (const float*)planes, C, channel, g, inv, bufA);
-  if (msk) hipLaunchKernelGGL(k_gran_sample_mask, dim3(grid_for(ns)), dim3(256), 0, s, labels, g, inv, msk);
+  if (dtype == ALIBY_U16) hipLaunchKernelGGL((k_gran_sample_frame<u16>), dim3(grid_for(ns)), dim3(256), 0, s, (const u16*)planes, C, channel, g, subsample_size, bufA);
+  else hipLaunchKernelGGL((k_gran_sample_frame<float>), dim3(grid_for(ns)), dim3(256), 0, s, (const float*)planes, C, channel, g, subsample_size, bufA);
+  if (msk) hipLaunchKernelGGL(k_gran_sample_mask, dim3(grid_for(ns)), dim3(256), 0, s, labels, g, subsample_size, msk);
   // 2. background: subsample again, masked erode, masked dilate, resize back, subtract, clamp (bufB = pix, bufC = ero)
-  const double binv = image_sample_size < 1 ? 1.0 / image_sample_size : 1.0;
   const double* back_src = bufA;
   if (image_sample_size < 1) {
-    hipLaunchKernelGGL(k_gran_resample, dim3(grid_for(nb)), dim3(256), 0, s, bufA, F, g.sh, g.sw, g.bh, g.bw, binv, binv, backA);
-    if (msk) hipLaunchKernelGGL(k_gran_resample_mask, dim3(grid_for(nb)), dim3(256), 0, s, msk, F, g.sh, g.sw, g.bh, g.bw, binv, binv, bmsk);
+    hipLaunchKernelGGL(k_gran_resample, dim3(grid_for(nb)), dim3(256), 0, s, bufA, F, g.sh, g.sw, g.bh, g.bw, image_sample_size, backA);
+    if (msk) hipLaunchKernelGGL(k_gran_resample_mask, dim3(grid_for(nb)), dim3(256), 0, s, msk, F, g.sh, g.sw, g.bh, g.bw, image_sample_size, bmsk);
     back_src = backA;
   } else if (msk) {
     bmsk = msk;
