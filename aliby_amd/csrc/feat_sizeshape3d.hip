@@ -5,7 +5,9 @@
 //
 // 19 columns per object: Volume, BoundingBoxMinimum_X/Y/Z, BoundingBoxMaximum_X/Y/Z (exclusive), BoundingBoxVolume,
 // Center_X/Y/Z, Extent, EquivalentDiameter, EulerNumber, MajorAxisLength, MinorAxisLength, InertiaTensorEigenvalues_0/1/2.
-// SurfaceArea and Solidity are left out on purpose.
+// SurfaceArea is the opt-in 20th column, written by feat_surface3d.hip (scikit-image 0.18.3's Lewiner mesh at level 0 through a table of
+// cell areas; vertices on the outside voxels' centres: one voxel measures 4 sqrt(3), not 6).  Solidity is left out on purpose: a
+// 3-D convex hull has nothing to be exact with here.
 //
 // One pass over the labels.  A workgroup stages an 8 x 8 x 64 tile of the (Z+1) x (Y+1) x (X+1) corner grid, i.e. the voxels
 // of the tile plus a one-voxel halo on the low side of every axis (9 x 9 x 65 uint16 = 10.3 KB of LDS; 1.29 x the tile's own

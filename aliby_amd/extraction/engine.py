@@ -362,22 +362,54 @@ class FeatureEngine:
                                                            _stream_ptr()))
         return out
 
-    def sizeshape3d(self, volume: torch.Tensor, counts, spacing=(1.0, 1.0, 1.0)) -> torch.Tensor:
-        """Volume labels uint16 [F,Z,Y,X] (1..counts[f] per stack) -> float64 [sum counts, 19] (features.sizeshape3d_names();
-        aliby_features_sizeshape3d).  Rows in (stack, label) order; spacing = physical voxel size (dz, dy, dx).  A label of
-        1..counts[f] without voxels gets Volume 0 and NaN elsewhere, as in intensity3d."""
-        assert volume.dtype == torch.uint16 and volume.dim() == 4 and volume.is_cuda
-        F, Z, Y, X = volume.shape
+    @staticmethod
+    def _spacing3d(spacing) -> np.ndarray:
         sp = np.ascontiguousarray(np.asarray(spacing, np.float64).reshape(3))
         if not (np.isfinite(sp).all() and (sp > 0).all()):
             raise ValueError(f"spacing must be three positive finite numbers (dz, dy, dx), got {spacing!r}")
+        return sp
+
+    @staticmethod
+    def surface3d_table(spacing=(1.0, 1.0, 1.0)) -> np.ndarray:
+        """The 256 per-cell areas behind `SurfaceArea` at a voxel size (dz, dy, dx) -> float64 [256] (aliby_surface3d_table):
+        entry c is the area of the triangles scikit-image's Lewiner marching cubes at level 0 emits for a 2 x 2 x 2 cell whose voxel
+        (z + dz, y + dy, x + dx) carries the label where bit 4 dz + 2 dy + dx of c is set.  Host arithmetic: needs no device."""
+        sp = FeatureEngine._spacing3d(spacing)
+        area = np.zeros(256, np.float64)
+        _lib.check(_lib.load().aliby_surface3d_table(_ptr(sp), _ptr(area)))
+        return area
+
+    @staticmethod
+    def _surface3d_shape(Z: int, Y: int, X: int) -> None:
+        if min(int(Z), int(Y), int(X)) < 2:
+            raise ValueError(f"SurfaceArea needs a volume of at least 2 x 2 x 2 voxels (a marching-cubes cell), got {(int(Z), int(Y), int(X))}")
+
+    def sizeshape3d(self, volume: torch.Tensor, counts, spacing=(1.0, 1.0, 1.0), surface_area: bool = False) -> torch.Tensor:
+        """Volume labels uint16 [F,Z,Y,X] (1..counts[f] per stack) -> float64 [sum counts, 19] (features.sizeshape3d_names();
+        aliby_features_sizeshape3d).  Rows in (stack, label) order; spacing = physical voxel size (dz, dy, dx).  A label of
+        1..counts[f] without voxels gets Volume 0 and NaN elsewhere, as in intensity3d.
+        surface_area=True -> [sum counts, 20]: the same 19 columns from the same launch, and column 19 "SurfaceArea"
+        (aliby_features_surface3d): the area of scikit-image's Lewiner marching-cubes mesh at level 0 of each object, as CellProfiler
+        measures it, from exact per-object counts of the 2 x 2 x 2 cell configurations and `surface3d_table(spacing)`.  The mesh is
+        open where an object touches a face of the volume; its vertices sit on the outside voxels' centres (one voxel: 4 sqrt(3)).
+        An object that fills the whole volume gets 0 (scikit-image raises there); Z, Y, X must be at least 2."""
+        assert volume.dtype == torch.uint16 and volume.dim() == 4 and volume.is_cuda
+        F, Z, Y, X = volume.shape
+        sp = self._spacing3d(spacing)
+        if surface_area:
+            self._surface3d_shape(Z, Y, X)
         offsets = self._volume_offsets("sizeshape3d", F, counts)
-        out = self.new_output(int(offsets[-1]), 19)
+        out = self.new_output(int(offsets[-1]), 20 if surface_area else 19)
         if int(offsets[-1]) == 0:
             return out  # stacks without any object: an empty block
+        volume = volume.contiguous()
         with self.timed("sizeshape3d"):
-            _lib.check(self.lib.aliby_features_sizeshape3d(self.ctx.handle, _ptr(volume.contiguous()), F, Z, Y, X, _ptr(offsets), _ptr(sp), _ptr(out),
+            _lib.check(self.lib.aliby_features_sizeshape3d(self.ctx.handle, _ptr(volume), F, Z, Y, X, _ptr(offsets), _ptr(sp), _ptr(out),
                                                            out.stride(0), 0, _stream_ptr()))
+        if surface_area:
+            with self.timed("surface3d"):
+                _lib.check(self.lib.aliby_features_surface3d(self.ctx.handle, _ptr(volume), F, Z, Y, X, _ptr(offsets), _ptr(sp), _ptr(out),
+                                                             out.stride(0), 19, _stream_ptr()))
         return out
 
     @property

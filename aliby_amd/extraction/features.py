@@ -177,13 +177,18 @@ def intensity3d_names() -> list[str]:
             "Location_Center_X", "Location_Center_Y", "Location_Center_Z"]
 
 
-def sizeshape3d_names() -> list[str]:
+def sizeshape3d_names(surface_area: bool = False) -> list[str]:
     """Size and shape of volume labels (csrc/feat_sizeshape3d.hip), named after CellProfiler's 3-D MeasureObjectSizeShape (the
-    names cp_measure's `sizeshape` uses for 3-D input; parity with it is unpinned, like intensity3d).  SurfaceArea and Solidity
-    are deliberately absent."""
-    return ["Volume", "BoundingBoxMinimum_X", "BoundingBoxMinimum_Y", "BoundingBoxMinimum_Z", "BoundingBoxMaximum_X", "BoundingBoxMaximum_Y",
-            "BoundingBoxMaximum_Z", "BoundingBoxVolume", "Center_X", "Center_Y", "Center_Z", "Extent", "EquivalentDiameter", "EulerNumber",
-            "MajorAxisLength", "MinorAxisLength", "InertiaTensorEigenvalues_0", "InertiaTensorEigenvalues_1", "InertiaTensorEigenvalues_2"]
+    names cp_measure's `sizeshape` uses for 3-D input; parity with it is unpinned, like intensity3d).  19 columns; with
+    `surface_area=True` "SurfaceArea" is appended as column 19 (csrc/feat_surface3d.hip).  That column is opt-in and pinned to
+    scikit-image 0.18.3's Lewiner marching-cubes mesh at level 0, the function CellProfiler calls, through a table of per-cell
+    areas recorded from it (tests/golden/skimage_marching_cubes_level0.json); at level 0 the vertices sit on the centres of the
+    outside voxels, so a single voxel measures 4 sqrt(3), not 6.  Solidity stays absent: a 3-D convex hull has nothing to be exact
+    with here (DESIGN.md)."""
+    names = ["Volume", "BoundingBoxMinimum_X", "BoundingBoxMinimum_Y", "BoundingBoxMinimum_Z", "BoundingBoxMaximum_X", "BoundingBoxMaximum_Y",
+             "BoundingBoxMaximum_Z", "BoundingBoxVolume", "Center_X", "Center_Y", "Center_Z", "Extent", "EquivalentDiameter", "EulerNumber",
+             "MajorAxisLength", "MinorAxisLength", "InertiaTensorEigenvalues_0", "InertiaTensorEigenvalues_1", "InertiaTensorEigenvalues_2"]
+    return names + ["SurfaceArea"] if surface_area else names
 
 
 def coloc3d_names(pairs, metrics=("pearson", "manders_fold", "rwc", "costes")) -> list[str]:

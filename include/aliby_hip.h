@@ -599,6 +599,19 @@ int aliby_features_intensity3d(aliby_ctx* ctx, const uint16_t* labels, const uin
  * voxels gets Volume 0 and NaN elsewhere.  Exact integer sums: run-to-run deterministic and independent of the batch. */
 int aliby_features_sizeshape3d(aliby_ctx* ctx, const uint16_t* labels, int F, int Z, int Y, int X, const int32_t* offsets_host,
                                const double* spacing, double* out, int ld, int col0, void* stream);
+/* SurfaceArea of the same labelled stacks, CellProfiler's 3-D MeasureObjectSizeShape column: one float64 per object at
+ * out[row * ld + col], rows as in aliby_features_sizeshape3d.  The area of the mesh that scikit-image's
+ * marching_cubes(method="lewiner", level=0) builds on the object's mask in its bounding box grown by one voxel and clipped to the
+ * volume (mesh_surface_area), computed as the sum over the (Z-1)(Y-1)(X-1) cells of the volume grid of area256[configuration],
+ * configuration bit 4 dz + 2 dy + dx = voxel (z + dz, y + dy, x + dx) carries the label.  Counts are exact integers and the sum runs
+ * over the configurations in increasing order: bitwise independent of the run and of the batch.  An object on a face of the volume
+ * is open there; at level 0 the vertices sit on the outside voxels' centres (one voxel measures 4 sqrt(3)).  A label of 1..n_f
+ * without voxels gets NaN, an object that fills the whole volume 0 (scikit-image raises there).  Z, Y, X >= 2.
+ * aliby_surface3d_table fills the 256 areas for a spacing (host double[3] (dz, dy, dx), positive) from the triangle table
+ * recorded from scikit-image 0.18.3 (csrc/mc_level0_table.h): host arithmetic only, no device is touched. */
+int aliby_surface3d_table(const double* spacing_zyx, double* area256);
+int aliby_features_surface3d(aliby_ctx* ctx, const uint16_t* labels, int F, int Z, int Y, int X, const int32_t* offsets_host,
+                             const double* spacing, double* out, int ld, int col, void* stream);
 /* Colocalisation of channel pairs inside the objects of the same labelled stacks: labels uint16 [F,Z,Y,X], pixels [F,C,Z,Y,X] of
  * dtype ALIBY_U16 or ALIBY_F32, pairs_host = n_pairs x (ch0, ch1) with ch0 != ch1 (at most 64).  Over the voxels of object
  * (f, label) = row offsets_host[f] + label - 1 in raster order (z, y, x), the metrics of aliby_features_coloc with the same

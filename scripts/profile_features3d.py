@@ -4,7 +4,9 @@ ellipsoids relabelled 1..n; pixels of channel 0): `FeatureEngine.intensity3d` (4
 `FeatureEngine.sizeshape3d` (2 bytes per voxel, 2.57 with the low-side halo of its 8 x 8 x 64 tiles), one stack and a batch of 8,
 and `FeatureEngine.coloc3d` on both channels (one pair, all four metrics: the labels once for the object table, then per object
 the labels of its bounding box and its voxels of both channels; `coloc3d_bytes`), and `FeatureEngine.texture3d` on channel 0
-(scale 3, 256 grey levels: the labels once for the object table, then labels and pixels of every bounding box; `texture3d_bytes`).
+(scale 3, 256 grey levels: the labels once for the object table, then labels and pixels of every bounding box; `texture3d_bytes`),
+and `FeatureEngine.sizeshape3d(..., surface_area=True)`: the same sizeshape3d launch followed by the SurfaceArea pass (section
+"surface3d": histogram memset, table and offsets upload, k_surface3d and its finish; 2 bytes per voxel again).
 Times are the engine's own `timed(...)` events around each call (memsets, offsets upload, accumulation and finalise kernels), the
 families alternating, warm-up calls discarded; prints one JSON line.  The 16.8 MB of labels of one stack stay resident in
 the 256 MB Infinity Cache between repeats, so the "fraction of HBM peak" of F = 1 is a rate against the HBM figure, not proof of
@@ -86,6 +88,7 @@ def main(warmup=3, reps=20):
         for _ in range(warmup):
             eng.intensity3d(vol, px, 0, counts)
             eng.sizeshape3d(vol, counts)
+            eng.sizeshape3d(vol, counts, surface_area=True)
             eng.coloc3d(vol, px2, [(0, 1)], counts)
             eng.texture3d(vol, px, 0, counts)
         torch.cuda.synchronize()
@@ -93,17 +96,22 @@ def main(warmup=3, reps=20):
         for _ in range(reps):
             eng.intensity3d(vol, px, 0, counts)
             eng.sizeshape3d(vol, counts)
+            eng.sizeshape3d(vol, counts, surface_area=True)
             eng.coloc3d(vol, px2, [(0, 1)], counts)
             eng.texture3d(vol, px, 0, counts)
         torch.cuda.synchronize()
         ms = {k: [a.elapsed_time(b) for a, b in v] for k, v in eng.profile.items()}
         eng.profile = None
+        # "sizeshape3d" was bracketed twice per repeat: the plain call, then the same launch inside the call with surface_area
+        plain, flagged = ms["sizeshape3d"][0::2], ms["sizeshape3d"][1::2]
+        ms["sizeshape3d"] = plain
+        with_area = [a + b for a, b in zip(flagged, ms["surface3d"])]
         voxels = vol.numel()
         c3_bytes, c3_largest = coloc3d_bytes(labels, len(present), F)
         t3_bytes, t3_boxes = texture3d_bytes(labels, len(present), F)
-        moved = {"intensity3d": 4 * voxels, "sizeshape3d": 2 * voxels, "coloc3d": c3_bytes, "texture3d": t3_bytes}
+        moved = {"intensity3d": 4 * voxels, "sizeshape3d": 2 * voxels, "surface3d": 2 * voxels, "coloc3d": c3_bytes, "texture3d": t3_bytes}
         out = {}
-        for name in ("intensity3d", "sizeshape3d", "coloc3d", "texture3d"):
+        for name in ("intensity3d", "sizeshape3d", "surface3d", "coloc3d", "texture3d"):
             med, best = statistics.median(ms[name]), min(ms[name])
             out[name] = dict(ms_median=round(med, 4), ms_min=round(best, 4), ms_max=round(max(ms[name]), 4), bytes_algorithmic=moved[name],
                              fraction_of_hbm_peak=round(moved[name] / (med * 1e-3) / HBM_PEAK, 4))
@@ -112,6 +120,9 @@ def main(warmup=3, reps=20):
                               objects_in_global_scratch_form=int((np.bincount(lut[gt].ravel())[1:] > eng.coloc3d_lds_voxels).sum()) * F)
         out["texture3d"].update(largest_box_voxels=int(t3_boxes.max()), lds_budget_box_voxels=eng.texture3d_lds_voxels,
                                 objects_in_global_scratch_form=int((t3_boxes > eng.texture3d_lds_voxels).sum()) * F)
+        out["sizeshape3d_with_surface_area"] = dict(ms_median=round(statistics.median(with_area), 4), ms_min=round(min(with_area), 4),
+                                                    ms_max=round(max(with_area), 4),
+                                                    over_plain=round(statistics.median(with_area) / out["sizeshape3d"]["ms_median"], 3))
         out["sizeshape3d_over_intensity3d"] = round(out["sizeshape3d"]["ms_median"] / out["intensity3d"]["ms_median"], 3)
         res[f"F{F}"] = out
     print(json.dumps(res))
