@@ -176,8 +176,8 @@ extern "C" int aliby_features_coloc3d(aliby_ctx* ctx, const uint16_t* labels, co
                                       double costes_scale_max, void* stream) {
   ARG_CHECK(ctx && labels && pixels && pairs_host && offsets_host && out, "coloc3d: null argument");
   ARG_CHECK(dtype == ALIBY_U16 || dtype == ALIBY_F32, "coloc3d: dtype must be ALIBY_U16 or ALIBY_F32");
-  ARG_CHECK(F > 0 && C > 0 && Z > 0 && Y > 0 && X > 0, "coloc3d: bad shape");
-  ARG_CHECK(X <= 65536 && Y <= 65536 && Z <= 65536 && (size_t)Z * Y * X <= (1ull << 30), "coloc3d: stack too large");
+  if (!volume_shape_ok("coloc3d", F, Z, Y, X, offsets_host, 1ull << 30)) return ALIBY_ERR_INVALID;
+  ARG_CHECK(C > 0, "coloc3d: bad shape");
   ARG_CHECK(n_pairs > 0 && n_pairs <= C3_MAX_PAIRS, "coloc3d: between 1 and 64 channel pairs per call");
   for (int p = 0; p < n_pairs; ++p) {
     ARG_CHECK(pairs_host[2 * p] >= 0 && pairs_host[2 * p] < C && pairs_host[2 * p + 1] >= 0 && pairs_host[2 * p + 1] < C,
@@ -186,7 +186,6 @@ extern "C" int aliby_features_coloc3d(aliby_ctx* ctx, const uint16_t* labels, co
   }
   const int cols[4] = {col_pearson, col_manders, col_rwc, col_costes};
   for (int k = 0; k < 4; ++k) ARG_CHECK(cols[k] < 0 || cols[k] + 2 <= pair_stride, "coloc3d: a metric's columns exceed the pair's block");
-  ARG_CHECK(volume_offsets_ok(offsets_host, F), "coloc3d: bad offsets");
   ARG_CHECK(col0 >= 0 && pair_stride >= 0 && (long long)col0 + (long long)n_pairs * pair_stride <= ld, "coloc3d: bad output stride");
   ARG_CHECK(costes_scale_max > 0.0 && costes_scale_max < 1e300 && thr_percent == thr_percent, "coloc3d: bad thr / scale_max");
   const int n = offsets_host[F];

@@ -13,7 +13,7 @@
 // object that fits a stack), so the result does not depend on the order of the atomics: run-to-run deterministic.  A lane walks
 // 16 consecutive voxels of a row and flushes its running sums whenever the label changes: one set of atomics per run of equal
 // labels, not per voxel.  HBM-bound: (2 + 2) bytes per voxel.
-#include "common.h"
+#include "volume_pass.h"
 
 typedef unsigned short u16;
 typedef unsigned long long u64;
@@ -47,16 +47,12 @@ __global__ __launch_bounds__(256) void k_intensity3d(const u16* __restrict__ lab
   const int segs = (X + 15) / 16;  // 16-voxel segments per row
   const size_t total = (size_t)F * Z * Y * segs;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int sg = (int)(i % segs);
-    size_t rest = i / segs;
-    const int y = (int)(rest % Y);
-    rest /= Y;
-    const int z = (int)(rest % Z), f = (int)(rest / Z);
-    const size_t row = (size_t)f * vol + ((size_t)z * Y + y) * X;
-    const u16* lb = labels + row;
-    const u16* px = pixels + ((size_t)f * C + c) * vol + ((size_t)z * Y + y) * X;
-    const int x0 = sg * 16, x1 = min(X, x0 + 16);
-    const int base = offsets[f], nrows = offsets[f + 1] - base;
+    const StackIndex g = stack_index(i, Z, Y, segs);
+    const size_t row = ((size_t)g.z * Y + g.y) * X;
+    const u16* lb = labels + (size_t)g.f * vol + row;
+    const u16* px = pixels + ((size_t)g.f * C + c) * vol + row;
+    const int x0 = g.x * 16, x1 = min(X, x0 + 16);
+    const int base = offsets[g.f], nrows = offsets[g.f + 1] - base;
     Run r;
     r.reset();
     unsigned cur = 0;
@@ -67,7 +63,7 @@ __global__ __launch_bounds__(256) void k_intensity3d(const u16* __restrict__ lab
         r.reset();
         cur = L;
       }
-      if (L) r.add(px[x], (unsigned)x, (unsigned)y, (unsigned)z);
+      if (L) r.add(px[x], (unsigned)x, (unsigned)g.y, (unsigned)g.z);
     }
     if (cur && (int)cur <= nrows) flush(r, acc + (size_t)(base + cur - 1) * I3_ACC, vmin + base + cur - 1, vmax + base + cur - 1);
   }
@@ -109,11 +105,10 @@ __global__ void k_intensity3d_finish(const u64* __restrict__ acc, const unsigned
 extern "C" int aliby_features_intensity3d(aliby_ctx* ctx, const uint16_t* labels, const uint16_t* pixels, int F, int C, int Z, int Y, int X,
                                           int channel, const int32_t* offsets_host, double* out, int ld, int col0, void* stream) {
   ARG_CHECK(ctx && labels && pixels && offsets_host && out, "intensity3d: null argument");
-  ARG_CHECK(F > 0 && C > 0 && Z > 0 && Y > 0 && X > 0 && channel >= 0 && channel < C, "intensity3d: bad shape");
-  ARG_CHECK(volume_offsets_ok(offsets_host, F), "intensity3d: bad offsets");  // (else labelled voxels would write past the accumulators)
-  ARG_CHECK(col0 >= 0 && ld >= col0 + 12, "intensity3d: bad output stride");
   // (x, y, z < 65536 and at most 2^32 voxels per object keep every sum below 2^63)
-  ARG_CHECK(X <= 65536 && Y <= 65536 && Z <= 65536 && (size_t)Z * Y * X <= (1ull << 32), "intensity3d: stack too large for exact 64-bit sums");
+  if (!volume_shape_ok("intensity3d", F, Z, Y, X, offsets_host, 1ull << 32)) return ALIBY_ERR_INVALID;
+  ARG_CHECK(C > 0 && channel >= 0 && channel < C, "intensity3d: channel out of range");
+  ARG_CHECK(col0 >= 0 && ld >= col0 + 12, "intensity3d: bad output stride");
   const int n = offsets_host[F];
   if (n <= 0) return ALIBY_OK;
   hipStream_t s = as_stream(stream);
@@ -135,6 +130,5 @@ extern "C" int aliby_features_intensity3d(aliby_ctx* ctx, const uint16_t* labels
   hipLaunchKernelGGL(k_intensity3d_finish, dim3((n + 255) / 256), dim3(256), 0, s, acc, vmin, vmax, n, out, ld, col0);
   KERNEL_CHECK();
   // the offsets live in ctx scratch: they must be consumed before the host reuses it
-  { const int rcw = aliby_wait_stream(s); if (rcw) return rcw; }
-  return ALIBY_OK;
+  return aliby_wait_stream(s);
 }

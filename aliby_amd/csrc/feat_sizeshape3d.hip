@@ -22,20 +22,13 @@
 // geometry, or on what else is in the batch.  Bounds (X, Y, Z <= 65536, Z*Y*X <= 2^32): sum x^2 over any object is below
 // Z*Y * X^3/3 = (Z*Y*X) * X^2/3 <= 2^64/3 < 2^63, a mixed sum below (Z*Y*X) * (X*Y)/4 <= 2^62, a first moment below 2^48;
 // the Euler counter is bounded by 8 elements per corner, |chi| < 2^36.
-#include "common.h"
+#include "volume_pass.h"
 
 typedef unsigned short u16;
 typedef unsigned long long u64;
 
 #define S3_ACC 10  // n, sum z, sum y, sum x, sum zz, sum yy, sum xx, sum zy, sum zx, sum yx
 #define S3_COLS 19
-#define S3_TZ 8
-#define S3_TY 8
-#define S3_TX 64
-#define S3_RUN 16  // corners per lane: 8 * 8 * (64 / 16) = 256 lanes
-#define S3_HZ (S3_TZ + 1)
-#define S3_HY (S3_TY + 1)
-#define S3_HX (S3_TX + 1)
 
 namespace {
 
@@ -65,41 +58,29 @@ __device__ __forceinline__ int chi_low_side(unsigned m) {
 __global__ __launch_bounds__(256) void k_sizeshape3d(const u16* __restrict__ labels, int F, int Z, int Y, int X, const int* __restrict__ offsets,
                                                      u64* __restrict__ acc, long long* __restrict__ euler, unsigned* __restrict__ bmin,
                                                      unsigned* __restrict__ bmax) {
-  __shared__ u16 tile[S3_HZ * S3_HY * S3_HX];
+  __shared__ u16 tile[VP_HZ * VP_HY * VP_HX];
   const size_t vol = (size_t)Z * Y * X;
-  const int ntx = X / S3_TX + 1, nty = Y / S3_TY + 1, ntz = Z / S3_TZ + 1;  // tiles of the corner grid, (X + 1) corners per row
+  const int ntx = X / VP_TX + 1, nty = Y / VP_TY + 1, ntz = Z / VP_TZ + 1;  // tiles of the corner grid, (X + 1) corners per row
   const size_t tiles = (size_t)F * ntz * nty * ntx;
   const int tid = threadIdx.x;
   const int seg = tid & 3, ly = (tid >> 2) & 7, lz = tid >> 5;
   for (size_t t = blockIdx.x; t < tiles; t += gridDim.x) {
-    const int x0 = (int)(t % ntx) * S3_TX;
-    size_t rest = t / ntx;
-    const int y0 = (int)(rest % nty) * S3_TY;
-    rest /= nty;
-    const int z0 = (int)(rest % ntz) * S3_TZ, f = (int)(rest / ntz);
-    const u16* lab = labels + (size_t)f * vol;
-    __syncthreads();  // the previous tile has been read
-    for (int i = tid; i < S3_HZ * S3_HY * S3_HX; i += 256) {
-      const int hx = i % S3_HX, r = i / S3_HX, hy = r % S3_HY, hz = r / S3_HY;
-      const int gz = z0 - 1 + hz, gy = y0 - 1 + hy, gx = x0 - 1 + hx;
-      u16 v = 0;  // outside the volume: background
-      if (gz >= 0 && gz < Z && gy >= 0 && gy < Y && gx >= 0 && gx < X) v = lab[((size_t)gz * Y + gy) * X + gx];
-      tile[i] = v;
-    }
-    __syncthreads();
-    const int base = offsets[f], nrows = offsets[f + 1] - base;
+    const StackIndex tl = stack_index(t, ntz, nty, ntx);
+    const int z0 = tl.z * VP_TZ, y0 = tl.y * VP_TY, x0 = tl.x * VP_TX;
+    window_stage<true>(tile, labels + (size_t)tl.f * vol, Z, Y, X, z0 - 1, y0 - 1, x0 - 1);
+    const int base = offsets[tl.f], nrows = offsets[tl.f + 1] - base;
     const unsigned cz = (unsigned)(z0 + lz), cy = (unsigned)(y0 + ly);
     // rows of the window: r00 = (z, y), r01 = (z, y - 1), r10 = (z - 1, y), r11 = (z - 1, y - 1); voxel x sits at [x - x0 + 1]
-    const u16* r00 = tile + ((lz + 1) * S3_HY + (ly + 1)) * S3_HX + seg * S3_RUN;
-    const u16* r01 = tile + ((lz + 1) * S3_HY + ly) * S3_HX + seg * S3_RUN;
-    const u16* r10 = tile + (lz * S3_HY + (ly + 1)) * S3_HX + seg * S3_RUN;
-    const u16* r11 = tile + (lz * S3_HY + ly) * S3_HX + seg * S3_RUN;
+    const u16* r00 = tile + ((lz + 1) * VP_HY + (ly + 1)) * VP_HX + seg * VP_RUN;
+    const u16* r01 = tile + ((lz + 1) * VP_HY + ly) * VP_HX + seg * VP_RUN;
+    const u16* r10 = tile + (lz * VP_HY + (ly + 1)) * VP_HX + seg * VP_RUN;
+    const u16* r11 = tile + (lz * VP_HY + ly) * VP_HX + seg * VP_RUN;
     unsigned p00 = r00[0], p01 = r01[0], p10 = r10[0], p11 = r11[0];
     unsigned run = 0, run_x = 0;  // the open run of voxels: label, first x
     unsigned e_lab = 0;           // the open Euler contribution: label, sum
     long long e_sum = 0;
-    const unsigned xb = (unsigned)(x0 + seg * S3_RUN);
-    for (int c = 0; c < S3_RUN; ++c) {
+    const unsigned xb = (unsigned)(x0 + seg * VP_RUN);
+    for (int c = 0; c < VP_RUN; ++c) {
       const unsigned x = xb + c;
       const unsigned c00 = r00[c + 1], c01 = r01[c + 1], c10 = r10[c + 1], c11 = r11[c + 1];
       if (c00 != run) {
@@ -108,36 +89,20 @@ __global__ __launch_bounds__(256) void k_sizeshape3d(const u16* __restrict__ lab
         run = c00;
         run_x = x;
       }
-      const unsigned any = c00 | p00 | c01 | p01 | c10 | p10 | c11 | p11;
-      const bool same = c00 == p00 && c00 == c01 && c00 == p01 && c00 == c10 && c00 == p10 && c00 == c11 && c00 == p11;
-      if (any && !same) {
-        const unsigned w[8] = {c00, p00, c01, p01, c10, p10, c11, p11};
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const unsigned L = w[k];
-          unsigned m = 0;
-          bool first = L != 0;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            if (w[j] == L) {
-              m |= 1u << j;
-              if (j < k) first = false;
-            }
-          }
-          if (!first || (int)L > nrows) continue;
-          const int chi = chi_low_side(m);
-          if (!chi) continue;
-          if (L != e_lab) {
-            if (e_lab && e_sum) atomicAdd((u64*)&euler[base + e_lab - 1], (u64)e_sum);
-            e_lab = L;
-            e_sum = 0;
-          }
-          e_sum += chi;
+      const unsigned w[8] = {c00, p00, c01, p01, c10, p10, c11, p11};
+      window_labels(w, nrows, [&](unsigned L, unsigned m) {
+        const int chi = chi_low_side(m);
+        if (!chi) return;
+        if (L != e_lab) {
+          if (e_lab && e_sum) atomicAdd((u64*)&euler[base + e_lab - 1], (u64)e_sum);
+          e_lab = L;
+          e_sum = 0;
         }
-      }
+        e_sum += chi;
+      });
       p00 = c00; p01 = c01; p10 = c10; p11 = c11;
     }
-    if (run && (int)run <= nrows) flush_run(run_x, xb + S3_RUN, cy, cz, acc + (size_t)(base + run - 1) * S3_ACC, bmin + (size_t)(base + run - 1) * 3,
+    if (run && (int)run <= nrows) flush_run(run_x, xb + VP_RUN, cy, cz, acc + (size_t)(base + run - 1) * S3_ACC, bmin + (size_t)(base + run - 1) * 3,
                                             bmax + (size_t)(base + run - 1) * 3);
     if (e_lab && e_sum) atomicAdd((u64*)&euler[base + e_lab - 1], (u64)e_sum);
   }
@@ -221,13 +186,10 @@ __global__ void k_sizeshape3d_finish(const u64* __restrict__ acc, const long lon
 extern "C" int aliby_features_sizeshape3d(aliby_ctx* ctx, const uint16_t* labels, int F, int Z, int Y, int X, const int32_t* offsets_host,
                                           const double* spacing, double* out, int ld, int col0, void* stream) {
   ARG_CHECK(ctx && labels && offsets_host && spacing && out, "sizeshape3d: null argument");
-  ARG_CHECK(F > 0 && Z > 0 && Y > 0 && X > 0, "sizeshape3d: bad shape");
-  ARG_CHECK(volume_offsets_ok(offsets_host, F), "sizeshape3d: bad offsets");  // (else labelled voxels would write past the accumulators)
-  ARG_CHECK(col0 >= 0 && ld >= col0 + S3_COLS, "sizeshape3d: bad output stride");
-  ARG_CHECK(spacing[0] > 0.0 && spacing[1] > 0.0 && spacing[2] > 0.0 && spacing[0] < 1e300 && spacing[1] < 1e300 && spacing[2] < 1e300,
-            "sizeshape3d: spacing must be positive and finite");
   // (see the bounds at the top of the file)
-  ARG_CHECK(X <= 65536 && Y <= 65536 && Z <= 65536 && (size_t)Z * Y * X <= (1ull << 32), "sizeshape3d: stack too large for exact 64-bit sums");
+  if (!volume_shape_ok("sizeshape3d", F, Z, Y, X, offsets_host, 1ull << 32)) return ALIBY_ERR_INVALID;
+  ARG_CHECK(col0 >= 0 && ld >= col0 + S3_COLS, "sizeshape3d: bad output stride");
+  ARG_CHECK(spacing_ok(spacing), "sizeshape3d: spacing must be positive and finite");
   const int n = offsets_host[F];
   if (n <= 0) return ALIBY_OK;
   hipStream_t s = as_stream(stream);
@@ -243,7 +205,7 @@ extern "C" int aliby_features_sizeshape3d(aliby_ctx* ctx, const uint16_t* labels
   HIP_TRY(hipMemsetAsync(bmin, 0xFF, box_bytes, s));
   HIP_TRY(hipMemsetAsync(bmax, 0, box_bytes, s));
   HIP_TRY(hipMemcpyAsync(d_off, offsets_host, sizeof(int) * (size_t)(F + 1), hipMemcpyHostToDevice, s));
-  const size_t tiles = (size_t)F * (Z / S3_TZ + 1) * (Y / S3_TY + 1) * (X / S3_TX + 1);
+  const size_t tiles = (size_t)F * (Z / VP_TZ + 1) * (Y / VP_TY + 1) * (X / VP_TX + 1);
   const unsigned grid = (unsigned)(tiles < 65536 ? tiles : 65536);
   hipLaunchKernelGGL(k_sizeshape3d, dim3(grid), dim3(256), 0, s, labels, F, Z, Y, X, d_off, acc, euler, bmin, bmax);
   KERNEL_CHECK();
@@ -251,6 +213,5 @@ extern "C" int aliby_features_sizeshape3d(aliby_ctx* ctx, const uint16_t* labels
                      out, ld, col0);
   KERNEL_CHECK();
   // the offsets live in ctx scratch: they must be consumed before the host reuses it
-  { const int rcw = aliby_wait_stream(s); if (rcw) return rcw; }
-  return ALIBY_OK;
+  return aliby_wait_stream(s);
 }

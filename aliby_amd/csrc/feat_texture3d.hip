@@ -204,11 +204,9 @@ extern "C" int aliby_features_texture3d(aliby_ctx* ctx, const uint16_t* labels, 
                                         void* stream) {
   ARG_CHECK(ctx && labels && pixels && offsets_host && out, "texture3d: null argument");
   ARG_CHECK(dtype == ALIBY_U16 || dtype == ALIBY_F32, "texture3d: dtype must be ALIBY_U16 or ALIBY_F32");
-  ARG_CHECK(F > 0 && C > 0 && Z > 0 && Y > 0 && X > 0, "texture3d: bad shape");
-  ARG_CHECK(X <= 65536 && Y <= 65536 && Z <= 65536 && (size_t)Z * Y * X <= (1ull << 30), "texture3d: stack too large");
-  ARG_CHECK(channel >= 0 && channel < C, "texture3d: channel out of range");
+  if (!volume_shape_ok("texture3d", F, Z, Y, X, offsets_host, 1ull << 30)) return ALIBY_ERR_INVALID;
+  ARG_CHECK(C > 0 && channel >= 0 && channel < C, "texture3d: channel out of range");
   ARG_CHECK(scale >= 1 && gray_levels >= 2 && gray_levels <= 256, "texture3d: scale >= 1 and 2 <= gray_levels <= 256");
-  ARG_CHECK(volume_offsets_ok(offsets_host, F), "texture3d: bad offsets");
   ARG_CHECK(col0 >= 0 && (long long)col0 + T3_NDIR * TX_NSTAT <= ld, "texture3d: bad output stride");
   const int n = offsets_host[F];
   if (n <= 0) return ALIBY_OK;

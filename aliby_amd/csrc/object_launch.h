@@ -1,6 +1,7 @@
 // object_launch.h — the launch front end of the 2-D feature kernels that work on one object per workgroup (feat_intensity.hip,
 // feat_texture.hip, feat_coloc.hip, feat_cell.hip, feat_shape.hip, feat_zernike.hip, feat_radial.hip, feat_localisation.hip).
-// Host side only; the counterpart of volume_launch in volume_table.h.
+// Host side only; the counterparts on volume labels are volume_launch in volume_table.h (one object per workgroup) and
+// volume_pass.h (the kernels that walk a whole stack).
 //
 // Every such kernel exists in two forms, <GLOBAL = false> and <GLOBAL = true>, with one argument struct that carries
 // `unsigned char* gscratch`:

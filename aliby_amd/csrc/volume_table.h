@@ -1,11 +1,12 @@
 // volume_table.h — the front end of the per-object kernels on volume labels [F, Z, Y, X] (feat_coloc3d.hip, feat_texture3d.hip):
 // the object table (k_volume_table: voxel count and bounding box per (stack, label), one read of the labels), the host's plan
 // around it (volume_plan), the arguments and the prologue every such kernel opens with, and the launch of a <dtype, GLOBAL> kernel.
+// (The index decode of k_volume_table and the entries' shape check are volume_pass.h, shared with the whole-stack kernels.)
 #pragma once
 #include <algorithm>
 #include <memory>
 #include <new>
-#include "common.h"
+#include "volume_pass.h"
 
 #ifdef __HIPCC__
 #define VOLUME_GLOBAL_BLOCKS 256             // workgroups of the global-scratch form, at most
@@ -21,15 +22,11 @@ __global__ __launch_bounds__(256) void k_volume_table(const uint16_t* __restrict
   const int segs = (X + 15) / 16;
   const size_t total = (size_t)F * Z * Y * segs;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int sg = (int)(i % segs);
-    size_t rest = i / segs;
-    const unsigned y = (unsigned)(rest % Y);
-    rest /= Y;
-    const unsigned z = (unsigned)(rest % Z);
-    const int f = (int)(rest / Z);
-    const uint16_t* lb = labels + (size_t)f * vol + ((size_t)z * Y + y) * X;
-    const int x0 = sg * 16, x1 = min(X, x0 + 16);
-    const int base = offsets[f], nrows = offsets[f + 1] - base;
+    const StackIndex g = stack_index(i, Z, Y, segs);
+    const unsigned z = (unsigned)g.z, y = (unsigned)g.y;
+    const uint16_t* lb = labels + (size_t)g.f * vol + ((size_t)z * Y + y) * X;
+    const int x0 = g.x * 16, x1 = min(X, x0 + 16);
+    const int base = offsets[g.f], nrows = offsets[g.f + 1] - base;
     unsigned cur = 0;
     int xs = x0;
     for (int x = x0; x <= x1; ++x) {

@@ -326,19 +326,30 @@ class FeatureEngine:
         return offsets
 
     @staticmethod
-    def _volume_inputs(who: str, volume, pixels, counts):
-        """Checks (volume uint16 [F,Z,Y,X], pixels uint16 or float32 [F,C,Z,Y,X], counts [F]) of a volume method -> F, C, Z, Y, X, offsets."""
-        if not (isinstance(volume, torch.Tensor) and isinstance(pixels, torch.Tensor)):
+    def _volume_labels(who: str, volume):
+        """Checks the labels of a volume method (uint16 [F,Z,Y,X] on the device) -> F, Z, Y, X."""
+        if not isinstance(volume, torch.Tensor):
             raise TypeError(f"{who} takes torch tensors on the device")
         if volume.dtype != torch.uint16:
             raise TypeError(f"{who}: volume labels must be uint16, got {volume.dtype}")
+        if volume.dim() != 4:
+            raise ValueError(f"{who}: volume must be [F,Z,Y,X], got {tuple(volume.shape)}")
+        if not volume.is_cuda:
+            raise ValueError(f"{who} takes tensors on the device")
+        return tuple(int(v) for v in volume.shape)
+
+    @staticmethod
+    def _volume_inputs(who: str, volume, pixels, counts):
+        """Checks (volume uint16 [F,Z,Y,X], pixels uint16 or float32 [F,C,Z,Y,X], counts [F]) of a volume method -> F, C, Z, Y, X, offsets."""
+        if not isinstance(pixels, torch.Tensor):
+            raise TypeError(f"{who} takes torch tensors on the device")
         if pixels.dtype not in (torch.uint16, torch.float32):
             raise TypeError(f"{who}: pixels must be uint16 or float32, got {pixels.dtype}")
-        if volume.dim() != 4 or pixels.dim() != 5 or tuple(pixels.shape[:1]) != tuple(volume.shape[:1]) or tuple(pixels.shape[2:]) != tuple(volume.shape[1:]):
+        F, Z, Y, X = FeatureEngine._volume_labels(who, volume)  # (after the pixels' types: a TypeError of either comes before any ValueError)
+        if pixels.dim() != 5 or tuple(pixels.shape[:1]) != (F,) or tuple(pixels.shape[2:]) != (Z, Y, X):
             raise ValueError(f"{who}: volume must be [F,Z,Y,X] and pixels [F,C,Z,Y,X], got {tuple(volume.shape)} and {tuple(pixels.shape)}")
-        if not (volume.is_cuda and pixels.is_cuda):
+        if not pixels.is_cuda:
             raise ValueError(f"{who} takes tensors on the device")
-        F, Z, Y, X = volume.shape
         return F, int(pixels.shape[1]), Z, Y, X, FeatureEngine._volume_offsets(who, F, counts)
 
     def intensity3d(self, volume: torch.Tensor, pixels: torch.Tensor, channel: int, counts) -> torch.Tensor:
@@ -393,8 +404,7 @@ class FeatureEngine:
         measures it, from exact per-object counts of the 2 x 2 x 2 cell configurations and `surface3d_table(spacing)`.  The mesh is
         open where an object touches a face of the volume; its vertices sit on the outside voxels' centres (one voxel: 4 sqrt(3)).
         An object that fills the whole volume gets 0 (scikit-image raises there); Z, Y, X must be at least 2."""
-        assert volume.dtype == torch.uint16 and volume.dim() == 4 and volume.is_cuda
-        F, Z, Y, X = volume.shape
+        F, Z, Y, X = self._volume_labels("sizeshape3d", volume)
         sp = self._spacing3d(spacing)
         if surface_area:
             self._surface3d_shape(Z, Y, X)

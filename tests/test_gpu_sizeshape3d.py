@@ -78,9 +78,9 @@ def _has_touching_objects(vol):
 
 # ------------------------------------------------------------------------------------------------ 1. random irregular labels
 @pytest.mark.parametrize("seed,shape", [(0, (5, 64, 64)), (1, (32, 48, 56)), (2, (7, 61, 83)), (3, (9, 17, 130)), (4, (8, 8, 64)),
-                                        (5, (16, 16, 128))])
+                                        (5, (16, 16, 128)), (6, (9, 9, 65))])
 def test_random_labels_equal_the_restatement(engine, seed, shape):
-    """Objects touch each other and every face of the volume; shapes below, at and above the 8 x 8 x 64 tile of the kernel."""
+    """Objects touch each other and every face of the volume; shapes below, at, one voxel past and above the 8 x 8 x 64 tile of the kernel."""
     vol, n = ref.random_labels(seed, shape)
     assert n >= 3 and _touches_every_face(vol) and _has_touching_objects(vol)
     got, counts = _run(engine, [vol])
@@ -250,6 +250,25 @@ def test_the_c_entry_refuses_what_it_cannot_hold(engine):
     assert float(out2.abs().sum()) == 0.0
     with pytest.raises(ValueError):
         engine.sizeshape3d(bg, [2, -1])
+
+
+def test_python_refuses_bad_labels_before_any_launch(engine):
+    """The label checks of the other volume families (tests/test_gpu_intensity3d.py), with their exception types."""
+    import torch
+
+    vol = torch.zeros((1, 2, 8, 8), dtype=torch.uint16, device="cuda")
+    vol[0, :, 2:5, 2:5] = 1
+    ok = engine.sizeshape3d(vol, [1])
+    assert tuple(ok.shape) == (1, 19) and float(ok[0, C["Volume"]]) == 18.0
+    for surface_area in (False, True):
+        with pytest.raises(ValueError):
+            engine.sizeshape3d(vol.cpu(), [1], surface_area=surface_area)  # labels on the host
+        with pytest.raises(TypeError):
+            engine.sizeshape3d(vol.cpu().numpy(), [1], surface_area=surface_area)
+        with pytest.raises(TypeError):
+            engine.sizeshape3d(vol.to(torch.int32), [1], surface_area=surface_area)
+        with pytest.raises(ValueError):
+            engine.sizeshape3d(vol[0], [1], surface_area=surface_area)  # labels of rank 3
 
 
 # ------------------------------------------------------------------------------------------------ 6. end to end

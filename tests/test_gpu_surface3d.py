@@ -48,9 +48,10 @@ def _touches_every_face(vol):
 # ------------------------------------------------------------------------------------------------ 1. random irregular labels
 @pytest.mark.parametrize("spacing", [UNIT, ANISO], ids=["unit", "aniso"])
 @pytest.mark.parametrize("seed,shape", [(0, (2, 2, 2)), (1, (2, 3, 70)), (2, (5, 64, 64)), (3, (7, 61, 83)), (4, (9, 17, 130)), (5, (8, 8, 64)),
-                                        (6, (9, 9, 65))])
+                                        (6, (9, 9, 65)), (7, (10, 10, 66))])
 def test_random_labels_equal_the_restatement_bit_for_bit(engine, seed, shape, spacing):
-    """One cell, Z at its minimum, sizes that are no tile multiple, exactly one tile of voxels, one tile of cells (9 x 9 x 65)."""
+    """One cell, Z at its minimum, sizes that are no tile multiple, exactly one tile of voxels, one tile of cells (9 x 9 x 65), one cell
+    past it on every axis (10 x 10 x 66)."""
     vol, n = ref.random_labels(seed, shape)
     assert n >= 1
     if min(shape) > 2:

@@ -9,10 +9,10 @@ source lines) and the order in which each kernel numbers its work items:
 import numpy as np
 
 SEGMENT = 16
-# feat_intensity3d.hip:49,132 (k_intensity3d) and volume_table.h:23,56 (k_volume_table, the front end of coloc3d and texture3d):
+# feat_intensity3d.hip:49,127 (k_intensity3d) and volume_table.h:24,53 (k_volume_table, the front end of coloc3d and texture3d):
 # 32768 workgroups of 256 lanes, a lane per 16-voxel segment; item = ((f * Z + z) * Y + y) * ceil(X / 16) + x / 16
 SEGMENT_CAP = 32768 * 256
-# feat_sizeshape3d.hip:72,245 (k_sizeshape3d): 65536 workgroups, one per tile of 8 x 8 x 64 corners of the (Z + 1)(Y + 1)(X + 1)
+# feat_sizeshape3d.hip:67,209 (k_sizeshape3d): 65536 workgroups, one per tile of 8 x 8 x 64 corners of the (Z + 1)(Y + 1)(X + 1)
 # corner grid; tile = ((f * (Z / 8 + 1) + z / 8) * (Y / 8 + 1) + y / 8) * (X / 64 + 1) + x / 64.  Voxel (z, y, x) is read by the
 # corners (z .. z + 1, y .. y + 1, x .. x + 1)
 TILE_CAP = 65536
