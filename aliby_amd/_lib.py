@@ -97,6 +97,7 @@ _SIGNATURES = {
     "aliby_nn_conv3x3_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "aliby_nn_conv3x3_deep_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "aliby_nn_conv3x3_kloop64_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "aliby_nn_conv3x3_kloop_limits": (_i, [C.POINTER(_i)]),
     "aliby_nn_conv3x3_deep16_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "aliby_nn_pack_conv3x3_deep16_bf16": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "aliby_nn_maxpool2_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),

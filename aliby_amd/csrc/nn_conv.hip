@@ -18,6 +18,7 @@
 // the weights is permuted at pack time so that those 16 channels are contiguous in memory
 // (MFMA row (reg&3) + 8*(reg>>2) + 4*(lane>>5)  <->  channel 16*(lane>>5) + reg).
 #include "common.h"
+#include "conv_launch.h"
 #include <utility>
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
@@ -1232,113 +1233,72 @@ __global__ void k_pack_conv3x3(const float* w, int cout, int cin_src, int cin, i
 unsigned long long* g_conv_trace = nullptr;
 
 template <int CIN, int COUT, bool UP, bool PACK = false>
-int launch_conv_dma(aliby_ctx* ctx, ConvArgs& a, hipStream_t stream) {
+int launch_conv_dma(ConvArgs& a, hipStream_t stream) {
   using cfg = DmaCfg<CIN, COUT, UP, PACK>;
-  a.G = PACK ? 224 / a.W : 1;
-  a.tiles_x = PACK ? 224 / cfg::TW : (a.W + cfg::TW - 1) / cfg::TW;
-  a.tiles_y = (a.H + cfg::TH - 1) / cfg::TH;
-  const long long nt = (long long)(a.N / a.G) * a.tiles_x * a.tiles_y;
-  ARG_CHECK(nt < INT_MAX, "conv3x3: too many tiles");
-  a.ntiles = (int)nt;
-  static bool attr_done = false;
-  if (!attr_done) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3_dma<CIN, COUT, UP, PACK>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, cfg::LDS_BYTES));
-    attr_done = true;
-  }
-  const int per_xcd = (a.ntiles + 7) / 8;
+  if (const int rc = conv_tiles<cfg, PACK>(a)) return rc;
   const int cap = 32 * cfg::WAVES_PER_SIMD;  // workgroups per XCD: 32 CUs x (1 or 2) resident workgroups
-  const int nslots = per_xcd < cap ? per_xcd : cap;
-  hipLaunchKernelGGL((k_conv3x3_dma<CIN, COUT, UP, PACK>), dim3(8 * nslots), dim3(256), cfg::LDS_BYTES, stream, a);
-  KERNEL_CHECK();
-  return ALIBY_OK;
+  return launch<k_conv3x3_dma<CIN, COUT, UP, PACK>, 256>(a, cfg::LDS_BYTES, cap, stream);
 }
 
 template <int CIN, int COUT, bool UP, bool TALL, bool PACK = false>
-int launch_conv_reg(aliby_ctx* ctx, ConvArgs& a, hipStream_t stream) {
+int launch_conv_reg(ConvArgs& a, hipStream_t stream) {
   using cfg = ConvCfg<CIN, COUT, TALL, PACK>;
-  a.G = PACK ? 224 / a.W : 1;
-  a.tiles_x = PACK ? 224 / cfg::TW : (a.W + cfg::TW - 1) / cfg::TW;
-  a.tiles_y = (a.H + cfg::TH - 1) / cfg::TH;
-  const long long nt = (long long)(a.N / a.G) * a.tiles_x * a.tiles_y;
-  ARG_CHECK(nt < INT_MAX, "conv3x3: too many tiles");
-  a.ntiles = (int)nt;
-  static bool attr_done = false;
+  if (const int rc = conv_tiles<cfg, PACK>(a)) return rc;
   constexpr int PKV = PACK ? 0 : (!UP && CIN == 32 && COUT == 32) ? 1 : ((!UP && CIN == 64 && COUT == 64) ? 2 : 0);  // projection input: 16 / 32 channels
   constexpr int P_BYTES = PKV ? 2 * PKV * ((cfg::TH * cfg::TW) | 1) * 16 : 0;
-  if (!attr_done) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3<CIN, COUT, UP, false, 0, TALL, PACK>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, cfg::LDS_BYTES));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3<CIN, COUT, UP, true, 0, TALL, PACK>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, cfg::LDS_BYTES));
-    if constexpr (PKV > 0)
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3<CIN, COUT, UP, false, PKV, TALL>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, cfg::LDS_BYTES + P_BYTES));
-    attr_done = true;
+  constexpr int CAP = 64;  // 2 workgroups per CU, 32 CUs per XCD
+  if (!a.pin && !a.hout) {
+    if (!a.pool) return launch<k_conv3x3<CIN, COUT, UP, false, 0, TALL, PACK>, 256>(a, cfg::LDS_BYTES, CAP, stream);
+    return launch<k_conv3x3<CIN, COUT, UP, true, 0, TALL, PACK>, 256>(a, cfg::LDS_BYTES, CAP, stream);
   }
-  const int per_xcd = (a.ntiles + 7) / 8;
-  const int nslots = per_xcd < 64 ? per_xcd : 64;  // 2 workgroups per CU, 32 CUs per XCD
   if (a.pin) {
     if constexpr (PKV > 0) {
       ARG_CHECK(!a.pool && a.pcs >= 1 && a.pcs <= 2 * PKV, "conv3x3: fused projection: unsupported input width");
-      hipLaunchKernelGGL((k_conv3x3<CIN, COUT, UP, false, PKV, TALL>), dim3(8 * nslots), dim3(256), cfg::LDS_BYTES + P_BYTES, stream, a);
+      return launch<k_conv3x3<CIN, COUT, UP, false, PKV, TALL>, 256>(a, cfg::LDS_BYTES + P_BYTES, CAP, stream);
     } else {
       aliby_set_error("conv3x3: fused projection is built for (32,32) and (64,64) without upsampling only");
       return ALIBY_ERR_UNSUPPORTED;
     }
-  } else if (a.hout) {
-    if constexpr (COUT == 32 && CIN == 32 && !UP && !PACK) {
-      static bool head_attr = false;
-      if (!head_attr) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3x3<CIN, COUT, UP, false, 0, TALL, false, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, cfg::LDS_BYTES));
-        head_attr = true;
-      }
-      ARG_CHECK(!a.pool && a.hO >= 1 && a.hO <= 3, "conv3x3: fused head: 1..3 output channels, no pooled output");
-      hipLaunchKernelGGL((k_conv3x3<CIN, COUT, UP, false, 0, TALL, false, true>), dim3(8 * nslots), dim3(256), cfg::LDS_BYTES, stream, a);
-    } else {
-      aliby_set_error("conv3x3: the fused output head is built for the (32,32) unit only");
-      return ALIBY_ERR_UNSUPPORTED;
-    }
-  } else if (a.pool) {
-    hipLaunchKernelGGL((k_conv3x3<CIN, COUT, UP, true, 0, TALL, PACK>), dim3(8 * nslots), dim3(256), cfg::LDS_BYTES, stream, a);
-  } else {
-    hipLaunchKernelGGL((k_conv3x3<CIN, COUT, UP, false, 0, TALL, PACK>), dim3(8 * nslots), dim3(256), cfg::LDS_BYTES, stream, a);
   }
-  KERNEL_CHECK();
-  return ALIBY_OK;
+  if constexpr (COUT == 32 && CIN == 32 && !UP && !PACK) {  // a.hout: the output head in the epilogue
+    ARG_CHECK(!a.pool && a.hO >= 1 && a.hO <= 3, "conv3x3: fused head: 1..3 output channels, no pooled output");
+    return launch<k_conv3x3<CIN, COUT, UP, false, 0, TALL, false, true>, 256>(a, cfg::LDS_BYTES, CAP, stream);
+  } else {
+    aliby_set_error("conv3x3: the fused output head is built for the (32,32) unit only");
+    return ALIBY_ERR_UNSUPPORTED;
+  }
 }
 
 template <int CIN, int COUT, bool UP>
-int launch_conv(aliby_ctx* ctx, ConvArgs& a, hipStream_t stream) {
+int launch_conv(ConvArgs& a, hipStream_t stream) {
   // measured per shape (scripts/bench_conv.py): the DMA pipeline wins where the raw window is small (upsampled
   // input); ALIBY_CONV_DMA=0/1 forces one variant for A/B runs
-  static const bool use_dma = [] { const char* e = getenv("ALIBY_CONV_DMA"); return e ? atoi(e) != 0 : UP; }();
+  static const bool use_dma = env_int("ALIBY_CONV_DMA", UP) != 0;
   if (use_dma && !a.pool && !a.pin && !a.hout) {  // the pooled output is an epilogue of the register-staged variant
     if constexpr (UP && COUT >= 64) {
-      static const int pack_up = [] { const char* e = getenv("ALIBY_CONV_PACK"); return e ? atoi(e) : 7; }();  // bit 2: upsampled shapes
+      static const int pack_up = env_int("ALIBY_CONV_PACK", 7);  // bit 2: upsampled shapes
       if ((pack_up & 4) && (a.W == 56 || a.W == 112) && a.N % (224 / a.W) == 0 && a.H % DmaCfg<CIN, COUT, UP, true>::TH == 0)
-        return launch_conv_dma<CIN, COUT, UP, true>(ctx, a, stream);
+        return launch_conv_dma<CIN, COUT, UP, true>(a, stream);
     }
-    return launch_conv_dma<CIN, COUT, UP>(ctx, a, stream);
+    return launch_conv_dma<CIN, COUT, UP>(a, stream);
   }
   // a taller tile where it divides the image and fits two workgroups per CU (measured: 64->128 at 56 rows +10 %,
   // 32->32 at 224 rows +3..7 %: the fixed per-tile latency chain is amortised over twice the pixels)
   constexpr bool CAN_TALL = (CIN >= 64 && COUT >= 128) || (CIN == 32 && COUT == 32);
   // images narrower than the 224-pixel level-0 tile are packed side by side so that no MFMA column runs empty
   if constexpr (!UP && COUT >= 64) {
-    static const int pack_on = [] { const char* e = getenv("ALIBY_CONV_PACK"); return e ? atoi(e) : 7; }();  // bit 0: 128-cout shapes, bit 1: 64-cout
+    static const int pack_on = env_int("ALIBY_CONV_PACK", 7);  // bit 0: 128-cout shapes, bit 1: 64-cout
     if ((pack_on & (COUT >= 128 ? 1 : 2)) && !a.pin && (a.W == 28 || a.W == 56 || a.W == 112) && a.N % (224 / a.W) == 0 &&
         a.H % ConvCfg<CIN, COUT, false, true>::TH == 0) {
       if constexpr (CIN == 64 && COUT == 64) {
-        static const bool tall64 = [] { const char* e = getenv("ALIBY_CONV_TALL64"); return e ? atoi(e) != 0 : true; }();
-        if (tall64 && a.H % ConvCfg<CIN, COUT, true, true>::TH == 0) return launch_conv_reg<CIN, COUT, UP, true, true>(ctx, a, stream);
+        static const bool tall64 = env_int("ALIBY_CONV_TALL64", 1) != 0;
+        if (tall64 && a.H % ConvCfg<CIN, COUT, true, true>::TH == 0) return launch_conv_reg<CIN, COUT, UP, true, true>(a, stream);
       }
-      return launch_conv_reg<CIN, COUT, UP, false, true>(ctx, a, stream);
+      return launch_conv_reg<CIN, COUT, UP, false, true>(a, stream);
     }
   }
-  if (CAN_TALL && !a.pin && a.H % (2 * ConvCfg<CIN, COUT, false>::TH) == 0) return launch_conv_reg<CIN, COUT, UP, CAN_TALL>(ctx, a, stream);
-  return launch_conv_reg<CIN, COUT, UP, false>(ctx, a, stream);
+  if (CAN_TALL && !a.pin && a.H % (2 * ConvCfg<CIN, COUT, false>::TH) == 0) return launch_conv_reg<CIN, COUT, UP, CAN_TALL>(a, stream);
+  return launch_conv_reg<CIN, COUT, UP, false>(a, stream);
 }
 
 }  // namespace
@@ -1390,12 +1350,12 @@ static int conv3x3_entry(aliby_ctx* ctx, const void* in, const void* wpk, void* 
   a.cs = in_channels / 8;
   a.coff = in_channel0 / 8;
   a.N = N; a.H = H; a.W = W;
-  if (CIN == 32 && COUT == 32 && !in_up) return launch_conv<32, 32, false>(ctx, a, stream);
-  if (CIN == 64 && COUT == 32 && in_up) return launch_conv<64, 32, true>(ctx, a, stream);
-  if (CIN == 64 && COUT == 64 && !in_up) return launch_conv<64, 64, false>(ctx, a, stream);
-  if (CIN == 64 && COUT == 64 && in_up) return launch_conv<64, 64, true>(ctx, a, stream);
-  if (CIN == 64 && COUT == 128) return in_up ? launch_conv<64, 128, true>(ctx, a, stream) : launch_conv<64, 128, false>(ctx, a, stream);
-  if (CIN == 32 && COUT == 64 && !in_up) return launch_conv<32, 64, false>(ctx, a, stream);
+  if (CIN == 32 && COUT == 32 && !in_up) return launch_conv<32, 32, false>(a, stream);
+  if (CIN == 64 && COUT == 32 && in_up) return launch_conv<64, 32, true>(a, stream);
+  if (CIN == 64 && COUT == 64 && !in_up) return launch_conv<64, 64, false>(a, stream);
+  if (CIN == 64 && COUT == 64 && in_up) return launch_conv<64, 64, true>(a, stream);
+  if (CIN == 64 && COUT == 128) return in_up ? launch_conv<64, 128, true>(a, stream) : launch_conv<64, 128, false>(a, stream);
+  if (CIN == 32 && COUT == 64 && !in_up) return launch_conv<32, 64, false>(a, stream);
   aliby_set_error("conv3x3: unsupported (CIN=%d, COUT=%d, upsample=%d) combination", CIN, COUT, in_up);
   return ALIBY_ERR_UNSUPPORTED;
 }
@@ -1463,21 +1423,10 @@ extern "C" int aliby_nn_conv3x3_pair_bf16(aliby_ctx* ctx, const void* in, const 
   const long long nt = (long long)N * a.tiles_x * a.tiles_y;
   ARG_CHECK(nt < INT_MAX, "conv3x3_pair: too many tiles");
   a.ntiles = (int)nt;
-  static bool attr_done = false;
-  if (!attr_done) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_pair32<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, PairCfg::LDS_BYTES));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_pair32<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, PairCfg::LDS_BYTES));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_pair32<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, PairCfg::LDS_BYTES));
-    attr_done = true;
-  }
-  const int per_xcd = (a.ntiles + 7) / 8;
-  const int nslots = per_xcd < 32 ? per_xcd : 32;  // one 8-wave workgroup per CU, 32 CUs per XCD
-  const dim3 grid(8 * nslots), block(512);
-  if (head_out) hipLaunchKernelGGL((k_conv_pair32<false, true>), grid, block, PairCfg::LDS_BYTES, stream, a);
-  else if (pool_out) hipLaunchKernelGGL((k_conv_pair32<true, false>), grid, block, PairCfg::LDS_BYTES, stream, a);
-  else hipLaunchKernelGGL((k_conv_pair32<false, false>), grid, block, PairCfg::LDS_BYTES, stream, a);
-  KERNEL_CHECK();
-  return ALIBY_OK;
+  constexpr int CAP = 32;  // one 8-wave workgroup per CU, 32 CUs per XCD
+  if (!head_out && !pool_out) return launch<k_conv_pair32<false, false>, 512>(a, PairCfg::LDS_BYTES, CAP, stream);
+  if (!head_out) return launch<k_conv_pair32<true, false>, 512>(a, PairCfg::LDS_BYTES, CAP, stream);
+  return launch<k_conv_pair32<false, true>, 512>(a, PairCfg::LDS_BYTES, CAP, stream);
 }
 
 extern "C" int aliby_nn_first_pair_bf16(aliby_ctx* ctx, const float* tiles, int N, int Cin, int H, int W, const float* scale0,
@@ -1499,16 +1448,7 @@ extern "C" int aliby_nn_first_pair_bf16(aliby_ctx* ctx, const float* tiles, int 
   const long long nt = (long long)N * a.tiles_x * a.tiles_y;
   ARG_CHECK(nt < INT_MAX, "first_pair: too many tiles");
   a.ntiles = (int)nt;
-  static bool attr_done = false;
-  if (!attr_done) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_first_pair), hipFuncAttributeMaxDynamicSharedMemorySize, FirstPairCfg::LDS_BYTES));
-    attr_done = true;
-  }
-  const int per_xcd = (a.ntiles + 7) / 8;
-  const int nslots = per_xcd < 32 ? per_xcd : 32;  // one 8-wave workgroup per CU, 32 CUs per XCD
-  hipLaunchKernelGGL(k_conv_first_pair, dim3(8 * nslots), dim3(512), FirstPairCfg::LDS_BYTES, stream, a);
-  KERNEL_CHECK();
-  return ALIBY_OK;
+  return launch<k_conv_first_pair, 512>(a, FirstPairCfg::LDS_BYTES, 32, stream);  // one 8-wave workgroup per CU, 32 CUs per XCD
 }
 
 extern "C" int aliby_nn_out_head_bf16(aliby_ctx* ctx, const void* x, const float* scale, const float* shift, const float* w,

@@ -24,7 +24,7 @@
 //     through a 3-deep ring, seven MFMAs of cover each;
 //   * two workgroups per CU (<= 256 VGPRs, 44 KiB of LDS each) overlap each other's staging and MFMA phases.
 #include "common.h"
-#include <stdlib.h>
+#include "conv_launch.h"
 #include <utility>
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
@@ -324,23 +324,6 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep(DeepArgs a) {
     dc_store32(a, q0, px, c0, ocs, LW, HP, acc);
     DC_STAMP(2 + 4 * S);
   }
-}
-
-// One launch for the three forms: persistent workgroups, 8 XCDs x at most CAP slots (the kernel's workgroups per CU x 32 CUs per
-// XCD; `cap_env` names an environment variable that overrides it)
-template <auto Kernel, int LDS_BYTES, int CAP, int THREADS>
-int launch(DeepArgs& a, hipStream_t stream, const char* cap_env = nullptr) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    attr_done = true;
-  }
-  static const int cap = [&] { const char* e = cap_env ? getenv(cap_env) : nullptr; return e ? atoi(e) : CAP; }();
-  const int per_xcd = (a.ntiles + 7) / 8;
-  const int nslots = per_xcd < cap ? per_xcd : cap;
-  hipLaunchKernelGGL(Kernel, dim3(8 * nslots), dim3(THREADS), LDS_BYTES, stream, a);
-  KERNEL_CHECK();
-  return ALIBY_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -922,17 +905,18 @@ static int deep_entry(aliby_ctx* ctx, const void* in, const void* wpk, void* out
   DeepArgs a;
   if (const int rc = deep_args(a, ctx, in, wpk, out, scale, shift, shift_per_sample, bias, res, res_up, N, H, W, CIN, COUT, DC_RUN, COUT / 128))
     return rc;
-  static const int stagger = [] { const char* e = getenv("ALIBY_DEEP_STAGGER"); return e ? atoi(e) : 0; }();
+  static const int stagger = env_int("ALIBY_DEEP_STAGGER", 0);
   a.stagger = stagger;
   a.trace = g_deep_trace;
-  const char* ls_env = getenv("ALIBY_DEEP_LS");  // loader-specialised form: measured slower, kept for A/B; read per call
-  const bool ls = ls_env && atoi(ls_env);
+  const bool ls = env_int("ALIBY_DEEP_LS", 0) != 0;  // loader-specialised form: measured slower, kept for A/B; read per call
+  // caps: the kernel's workgroups per CU (2; the loader-specialised form 1) x 32 CUs per XCD; ALIBY_DEEP_SLOTS overrides the product form's
+  static const int slots = env_int("ALIBY_DEEP_SLOTS", 64);
   auto go = [&](auto cin, auto up) {
     constexpr int C = decltype(cin)::value;
     constexpr bool U = decltype(up)::value;
-    if (m16) return launch<k_conv3x3_deep16<C, U>, DC16_LDS_BYTES, 64, 256>(a, stream);
-    if (ls) return launch<k_conv3x3_deep_ls<C, U>, DL_LDS_BYTES, 32, 256 + DL_LT>(a, stream);  // one workgroup per CU
-    return launch<k_conv3x3_deep<C, U>, DC_LDS_BYTES, 64, 256>(a, stream, "ALIBY_DEEP_SLOTS");
+    if (m16) return launch<k_conv3x3_deep16<C, U>, 256>(a, DC16_LDS_BYTES, 64, stream);
+    if (ls) return launch<k_conv3x3_deep_ls<C, U>, 256 + DL_LT>(a, DL_LDS_BYTES, 32, stream);
+    return launch<k_conv3x3_deep<C, U>, 256>(a, DC_LDS_BYTES, slots, stream);
   };
   auto by_up = [&](auto cin) { return in_up ? go(cin, std::true_type{}) : go(cin, std::false_type{}); };
   if (CIN == 64) return by_up(std::integral_constant<int, 64>{});
@@ -992,5 +976,11 @@ extern "C" int aliby_nn_conv3x3_kloop64_bf16(aliby_ctx* ctx, const void* in, con
   DeepArgs a;
   if (const int rc = deep_args(a, ctx, in, wpk, out, scale, shift, shift_per_sample, bias, res, res_up, N, H, W, CIN, COUT, U_RUN, 1))
     return rc;
-  return launch<k_conv3x3_kloop64<128, true>, U_LDS_BYTES, 64, 256>(a, stream);
+  return launch<k_conv3x3_kloop64<128, true>, 256>(a, U_LDS_BYTES, 64, stream);  // 2 workgroups per CU, 32 CUs per XCD
+}
+
+extern "C" int aliby_nn_conv3x3_kloop_limits(int limits[4]) {
+  ARG_CHECK(limits != nullptr, "kloop_limits: null argument");
+  limits[0] = DC_RUN; limits[1] = DC_WMAX; limits[2] = U_RUN; limits[3] = U_WMAX;
+  return ALIBY_OK;
 }

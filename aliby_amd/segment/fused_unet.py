@@ -18,7 +18,9 @@ Same arithmetic as `ResidualUNet.forward` in eval mode, reorganised for MI355X:
 
 from __future__ import annotations
 
+import ctypes
 import os
+from functools import partialmethod
 
 import torch
 import torch.nn.functional as F
@@ -48,7 +50,7 @@ class _Unit:
             self.shift = F.pad(self.shift, (0, pad_in - self.shift.shape[0]))
         self.w = w.to(dtype).contiguous(memory_format=CL)
         self.w32 = w.contiguous()  # fp32 OIHW, packed for the MFMA unit on demand
-        self.wpk = None
+        self.wpk = {}  # (k0, k1, n0, n1) -> packed slice (FusedUNet._packed)
         self.bias = conv.bias.detach().float().contiguous()  # folded into the next fused pointwise pass
         self.pad = conv.padding
 
@@ -66,15 +68,13 @@ class _Proj:
             w = F.pad(w, (0, 0, 0, 0, 0, pad_in - w.shape[1]))
         self.w = w.to(dtype).contiguous(memory_format=CL)
         self.w32 = w[:, :, 0, 0].contiguous()  # [O, I] fp32, BatchNorm folded: packed for the fused projection on demand
-        self.wpk = None   # packed for the projection fused into conv1 (levels 0-1)
-        self.wpk1 = None  # packed for the standalone 1x1 kernel
+        self.wpk = {}  # (cout, padded cin) -> packed for the 1x1 kernel or a projection fused into conv1 (FusedUNet._packed_proj)
         self.bias = b.contiguous()
 
 
 # (CIN, COUT, input read through the 2x upsample) shapes that are one launch: the instantiations of k_conv3x3, and the up path's
-# 128 -> 64 convolution, which is the K-loop kernel k_conv3x3_kloop64 (csrc/nn_conv_deep.hip) for maps up to _KLOOP64_WMAX wide
+# 128 -> 64 convolution, which is the K-loop kernel k_conv3x3_kloop64 (csrc/nn_conv_deep.hip) for maps up to its widest (u_wmax)
 _KLOOP64 = (128, 64, True)
-_KLOOP64_WMAX = 128
 _MFMA_SHAPES = {(32, 32, False), (32, 64, False), (64, 64, False), (64, 32, True), (64, 64, True), (64, 128, False), (64, 128, True),
                 _KLOOP64}
 _POOL_SHAPES = {(32, 32, False), (32, 64, False), (64, 64, False), (64, 128, False)}
@@ -103,6 +103,11 @@ class FusedUNet:
         self.conv_stats = {}  # timing group -> [algorithmic bytes, flops] of the MFMA conv launches bracketed with events
         # every call made through self.lib is an asynchronous kernel launch: they keep the interpreter lock (see _lib.load_fast)
         self.lib = _lib.load_fast() if os.environ.get("ALIBY_FAST_LAUNCH", "1") != "0" else eng.lib
+        # what the K-loop kernels take (csrc/nn_conv_deep.hip): positions per tile and widest map of k_conv3x3_deep / k_conv3x3_kloop64;
+        # a per-sample shift needs images of at least one tile window, _min_px
+        lim = (ctypes.c_int * 4)()
+        _lib.check(self.lib.aliby_nn_conv3x3_kloop_limits(lim))
+        self.dc_run, self.dc_wmax, self.u_run, self.u_wmax = lim
         net = net.float().eval()
         self.down = []
         for i, blk in enumerate(net.down):
@@ -176,12 +181,10 @@ class FusedUNet:
         cout = proj.w32.shape[0]
         if cin not in (32, 64, 128, 256) or not (cout in (32, 64) or cout % 128 == 0) or proj.w32.shape[1] != cin:
             return self._conv(x, proj, pad=0)
-        if proj.wpk1 is None:
-            proj.wpk1 = torch.empty(cout * cin, dtype=torch.bfloat16, device="cuda")
-            _lib.check(self.lib.aliby_nn_pack_conv1x1_bf16(self.h, _ptr(proj.w32), cout, cin, cin, _ptr(proj.wpk1), _stream_ptr()))
+        wpk = self._packed_proj(proj, cout, cin)
         out = self._new(n, cout, H, W)
         with self.eng.timed("conv1x1_mfma"):
-            _lib.check(self.lib.aliby_nn_conv1x1_bf16(self.h, _ptr(x), _ptr(proj.wpk1), 0, _ptr(out), n, H, W, cin, cout, _stream_ptr()))
+            _lib.check(self.lib.aliby_nn_conv1x1_bf16(self.h, _ptr(x), _ptr(wpk), 0, _ptr(out), n, H, W, cin, cout, _stream_ptr()))
         return out
 
     def _unit(self, x, unit, shift=None, bias=None, res=None, res_up=False, in_up=False, pool=False):
@@ -189,12 +192,13 @@ class FusedUNet:
         one of the kernel's instantiations; otherwise the convolution is split along K (64 input channels per
         launch, each launch adding to the previous one through RES, in place) and along N (128 output channels
         per launch, written into channel slices of the output).  The up path's 128 -> 64 convolution through the upsample
-        is one launch too, of the K-loop kernel for 64 output channels (`_launch_kloop64`), on maps up to 128 wide."""
+        is one launch too, of the K-loop kernel for 64 output channels (`_launch_kloop64`), on maps up to its widest."""
         n, cin, cout = x.shape[0], x.shape[1], unit.w32.shape[0]
         H, W = (x.shape[2] * 2, x.shape[3] * 2) if in_up else (x.shape[2], x.shape[3])
         out = self._new(n, cout, H, W)
         pooled = self._new(n, cout, H // 2, W // 2) if pool else None
-        if self.deep_kernel and cout % 128 == 0 and cin in (64, 128, 256) and W <= 56 and (H + 1) * (W + 2) >= 226 + 2 * (W + 2):
+        px = (H + 1) * (W + 2)  # positions of one image in the K-loop kernels' tall image
+        if self.deep_kernel and cout % 128 == 0 and cin in (64, 128, 256) and W <= self.dc_wmax and px >= self._min_px(self.dc_run, W):
             self._launch_deep(x, unit, out, shift, bias, res, res_up, in_up)
             if pool:
                 with self.eng.timed("maxpool"):
@@ -203,8 +207,8 @@ class FusedUNet:
         one_launch = (cin, cout, bool(in_up)) in (_POOL_SHAPES if pool else _MFMA_SHAPES)
         if (cin, cout, bool(in_up)) == _KLOOP64:  # by the shape alone, never by the batch: the two forms round differently
             sh = unit.shift if shift is None else shift
-            one_launch = (not pool and self.deep_kernel and self.kloop64_kernel and W <= _KLOOP64_WMAX
-                          and (sh.ndim == 1 or (H + 1) * (W + 2) >= 450 + 2 * (W + 2)))
+            one_launch = (not pool and self.deep_kernel and self.kloop64_kernel and W <= self.u_wmax
+                          and (sh.ndim == 1 or px >= self._min_px(self.u_run, W)))
         if one_launch:
             self._launch_unit(x, unit, (0, cin), (0, cout), out, shift, bias, res, res_up, in_up, pooled)
             return (out, pooled) if pool else out
@@ -220,16 +224,37 @@ class FusedUNet:
                 cur, cur_up = out, False
         return (out, pooled) if pool else out
 
-    def _pack(self, unit):
-        cout, cin = unit.w32.shape[0], unit.w32.shape[1]
-        if unit.wpk is None:
-            unit.wpk = {}
-        key = (0, cin, 0, cout)
+    @staticmethod
+    def _min_px(run, W):
+        """Positions of one tile window of a K-loop kernel (`run` outputs and the rows above and below): a window may span two
+        images at most, so with a per-sample shift an image has at least this many."""
+        return run + 2 * (W + 2) + 2
+
+    def _packed(self, unit, kslice=None, nslice=None):
+        """The unit's 3x3 weights, or their [n0:n1, k0:k1] slice, in the MFMA layout: packed at first use."""
+        (k0, k1), (n0, n1) = kslice or (0, unit.w32.shape[1]), nslice or (0, unit.w32.shape[0])
+        key = (k0, k1, n0, n1)
         if key not in unit.wpk:
-            pk = torch.empty(cout * cin * 9, dtype=torch.bfloat16, device="cuda")
-            _lib.check(self.lib.aliby_nn_pack_conv3x3_bf16(self.h, _ptr(unit.w32), cout, cin, cin, _ptr(pk), _stream_ptr()))
+            w = unit.w32[n0:n1, k0:k1].contiguous()
+            pk = torch.empty(w.numel(), dtype=torch.bfloat16, device="cuda")
+            _lib.check(self.lib.aliby_nn_pack_conv3x3_bf16(self.h, _ptr(w), n1 - n0, k1 - k0, k1 - k0, _ptr(pk), _stream_ptr()))
             unit.wpk[key] = pk
         return unit.wpk[key]
+
+    def _packed_proj(self, proj, cout, pad):
+        """The 1x1 projection's weights for `cout` outputs, its input channels padded to `pad`, in the MFMA layout.  Keyed by both:
+        the first pair, the projection fused into conv1 and the 1x1 kernel each name the packing they read."""
+        if (cout, pad) not in proj.wpk:
+            pk = torch.empty(cout * pad, dtype=torch.bfloat16, device="cuda")
+            _lib.check(self.lib.aliby_nn_pack_conv1x1_bf16(self.h, _ptr(proj.w32), cout, proj.w32.shape[1], pad, _ptr(pk), _stream_ptr()))
+            proj.wpk[cout, pad] = pk
+        return proj.wpk[cout, pad]
+
+    def _book(self, group, nbytes, flops):
+        """Algorithmic bytes and flops of a launch that is bracketed with events (callers: only while its timer is active)."""
+        st = self.conv_stats.setdefault(group, [0, 0])
+        st[0] += nbytes
+        st[1] += flops
 
     def _pair(self, x, ua, ub, shift_a, shift_b, bias_a, bias_b, res, pool=False, head_out=None):
         """Two consecutive 32-channel units in one launch (aliby_nn_conv3x3_pair_bf16): the tensor between them stays in
@@ -243,13 +268,12 @@ class FusedUNet:
         group = "conv3x3_mfma_pair"
         timer = self.eng.timed(group)
         if timer.active:
-            st = self.conv_stats.setdefault(group, [0, 0])
-            st[0] += 2 * (x.numel() + res.numel()) + (2 * x.numel() if out is not None else 4 * head_out.numel()) + (x.numel() // 2 if pool else 0)
-            st[1] += 2 * 2 * 9 * 32 * 32 * n * H * W
+            self._book(group, 2 * (x.numel() + res.numel()) + (2 * x.numel() if out is not None else 4 * head_out.numel())
+                       + (x.numel() // 2 if pool else 0), 2 * 2 * 9 * 32 * 32 * n * H * W)
         hd = self.out
         with timer:
             _lib.check(self.lib.aliby_nn_conv3x3_pair_bf16(
-                self.h, _ptr(x), _ptr(self._pack(ua)), _ptr(self._pack(ub)), _ptr(out) if out is not None else 0, _ptr(ua.scale), _ptr(sa),
+                self.h, _ptr(x), _ptr(self._packed(ua)), _ptr(self._packed(ub)), _ptr(out) if out is not None else 0, _ptr(ua.scale), _ptr(sa),
                 self._sps(sa), _ptr(bias_a), _ptr(ub.scale), _ptr(sb), self._sps(sb), _ptr(bias_b), _ptr(res), n, H, W,
                 _ptr(pooled) if pooled is not None else 0,
                 _ptr(hd.scale) if head_out is not None else 0, _ptr(hd.shift) if head_out is not None else 0,
@@ -262,21 +286,16 @@ class FusedUNet:
         the raw bf16 copy of the tiles is written to HBM.  Same bits as first_conv -> _unit_proj."""
         n, cin, H, W = tiles.shape
         u, proj = d["u"], d["proj"]
-        wpk1 = self._pack(u[1])
-        if proj.wpk is None:
-            proj.wpk = torch.empty(32 * 16, dtype=torch.bfloat16, device="cuda")
-            _lib.check(self.lib.aliby_nn_pack_conv1x1_bf16(self.h, _ptr(proj.w32), 32, proj.w32.shape[1], 16, _ptr(proj.wpk), _stream_ptr()))
+        wpk1, pwpk = self._packed(u[1]), self._packed_proj(proj, 32, 16)
         out = self._new(n, 32, H, W)
         group = "conv3x3_mfma_first_pair"
         timer = self.eng.timed(group)
         if timer.active:
-            st = self.conv_stats.setdefault(group, [0, 0])
-            st[0] += 4 * tiles.numel() + 2 * out.numel()
-            st[1] += 2 * (9 * cin + 9 * 32 + cin) * 32 * n * H * W
+            self._book(group, 4 * tiles.numel() + 2 * out.numel(), 2 * (9 * cin + 9 * 32 + cin) * 32 * n * H * W)
         with timer:
             _lib.check(self.lib.aliby_nn_first_pair_bf16(
                 self.h, _ptr(tiles), n, cin, H, W, _ptr(u[0].scale), _ptr(u[0].shift), _ptr(self.first_w), _ptr(wpk1), _ptr(u[1].scale),
-                _ptr(d["shift1_b0"]), _ptr(d["pb1"]), _ptr(proj.wpk), _ptr(out), _stream_ptr()))
+                _ptr(d["shift1_b0"]), _ptr(d["pb1"]), _ptr(pwpk), _ptr(out), _stream_ptr()))
         return out
 
     def _unit_head(self, x, unit, shift, bias, res, y):
@@ -284,23 +303,15 @@ class FusedUNet:
         is written from the accumulators and the unit's own bf16 output — which nothing else reads — is not written."""
         n, cin, H, W = x.shape
         cout = unit.w32.shape[0]
-        if unit.wpk is None:
-            unit.wpk = {}
-        key = (0, cin, 0, cout)
-        if key not in unit.wpk:
-            pk = torch.empty(cout * cin * 9, dtype=torch.bfloat16, device="cuda")
-            _lib.check(self.lib.aliby_nn_pack_conv3x3_bf16(self.h, _ptr(unit.w32), cout, cin, cin, _ptr(pk), _stream_ptr()))
-            unit.wpk[key] = pk
+        wpk = self._packed(unit)
         sh = unit.shift if shift is None else shift
         group = "conv3x3_mfma_head"  # its own timing group: fewer bytes and more epilogue arithmetic than the plain unit
         timer = self.eng.timed(group)
         if timer.active:
-            st = self.conv_stats.setdefault(group, [0, 0])
-            st[0] += 2 * (x.numel() + res.numel()) + 4 * y.numel()
-            st[1] += 2 * (9 * cin + y.shape[1]) * cout * n * H * W
+            self._book(group, 2 * (x.numel() + res.numel()) + 4 * y.numel(), 2 * (9 * cin + y.shape[1]) * cout * n * H * W)
         with timer:
             _lib.check(self.lib.aliby_nn_conv3x3_head_bf16(
-                self.h, _ptr(x), _ptr(unit.wpk[key]), 0, _ptr(unit.scale), _ptr(sh), self._sps(sh), _ptr(bias), _ptr(res), 0, n, H, W,
+                self.h, _ptr(x), _ptr(wpk), 0, _ptr(unit.scale), _ptr(sh), self._sps(sh), _ptr(bias), _ptr(res), 0, n, H, W,
                 cin, cout, _ptr(self.out.scale), _ptr(self.out.shift), _ptr(self.out_w), _ptr(self.out.bias), self.out_w.shape[0], _ptr(y),
                 _stream_ptr()))
 
@@ -309,65 +320,37 @@ class FusedUNet:
         block's 1x1 projection of its raw input is a few extra k-steps, its output never touches HBM."""
         n, cin, H, W = x.shape
         cout = unit.w32.shape[0]
-        pc_pad = 16 if cin == 32 else 32
-        if unit.wpk is None:
-            unit.wpk = {}
-        key = (0, cin, 0, cout)
-        if key not in unit.wpk:
-            pk = torch.empty(cout * cin * 9, dtype=torch.bfloat16, device="cuda")
-            _lib.check(self.lib.aliby_nn_pack_conv3x3_bf16(self.h, _ptr(unit.w32), cout, cin, cin, _ptr(pk), _stream_ptr()))
-            unit.wpk[key] = pk
-        if proj.wpk is None:
-            proj.wpk = torch.empty(cout * pc_pad, dtype=torch.bfloat16, device="cuda")
-            _lib.check(self.lib.aliby_nn_pack_conv1x1_bf16(self.h, _ptr(proj.w32), cout, proj.w32.shape[1], pc_pad, _ptr(proj.wpk), _stream_ptr()))
+        wpk, pwpk = self._packed(unit), self._packed_proj(proj, cout, 16 if cin == 32 else 32)
         sh = unit.shift if shift is None else shift
         out = self._new(n, cout, H, W)
         group = "conv3x3_mfma"
         timer = self.eng.timed(group)
         if timer.active:
-            st = self.conv_stats.setdefault(group, [0, 0])
-            st[0] += 2 * (x.numel() + out.numel() + x_in.numel())
-            st[1] += 2 * (9 * cin + x_in.shape[1]) * cout * n * H * W
+            self._book(group, 2 * (x.numel() + out.numel() + x_in.numel()), 2 * (9 * cin + x_in.shape[1]) * cout * n * H * W)
         with timer:
             _lib.check(self.lib.aliby_nn_conv3x3_proj_bf16(
-                self.h, _ptr(x), _ptr(unit.wpk[key]), _ptr(out), _ptr(unit.scale), _ptr(sh), self._sps(sh), _ptr(bias), n, H, W, cin, cout,
-                _ptr(x_in), _ptr(proj.wpk), x_in.shape[1], _stream_ptr()))
+                self.h, _ptr(x), _ptr(wpk), _ptr(out), _ptr(unit.scale), _ptr(sh), self._sps(sh), _ptr(bias), n, H, W, cin, cout,
+                _ptr(x_in), _ptr(pwpk), x_in.shape[1], _stream_ptr()))
         return out
 
-    def _launch_deep(self, x, unit, out, shift, bias, res, res_up, in_up):
-        """One launch of the K-loop kernel (aliby_nn_conv3x3_deep_bf16): fp32 accumulation over the whole 9 * CIN reduction."""
+    def _launch_kloop(self, entry, group, x, unit, out, shift, bias, res, res_up, in_up=True):
+        """One launch of a K-loop kernel: fp32 accumulation over the whole 9 * CIN reduction.  Bound below as `_launch_deep`
+        (aliby_nn_conv3x3_deep_bf16) and as `_launch_kloop64` (aliby_nn_conv3x3_kloop64_bf16: the up path's 128 -> 64 convolution
+        through the upsample, booked with the other 64-channel launches)."""
         n, cin, cout = x.shape[0], x.shape[1], out.shape[1]
         H, W = out.shape[2], out.shape[3]
         sh = unit.shift if shift is None else shift
-        group = "conv3x3_mfma_deep"
         timer = self.eng.timed(group)
         if timer.active:  # algorithmic bytes: input + residual read once, output written once (no partial sums any more)
-            st = self.conv_stats.setdefault(group, [0, 0])
-            st[0] += 2 * (x.numel() + out.numel() + (res.numel() if res is not None else 0))
-            st[1] += 2 * 9 * cin * cout * n * H * W
+            self._book(group, 2 * (x.numel() + out.numel() + (res.numel() if res is not None else 0)), 2 * 9 * cin * cout * n * H * W)
         with timer:
-            _lib.check(self.lib.aliby_nn_conv3x3_deep_bf16(
-                self.h, _ptr(x), _ptr(self._pack(unit)), _ptr(out), _ptr(unit.scale), _ptr(sh), self._sps(sh),
+            _lib.check(getattr(self.lib, entry)(
+                self.h, _ptr(x), _ptr(self._packed(unit)), _ptr(out), _ptr(unit.scale), _ptr(sh), self._sps(sh),
                 _ptr(bias) if bias is not None else 0, _ptr(res) if res is not None else 0, 1 if res_up else 0, n, H, W, cin, cout,
                 1 if in_up else 0, _stream_ptr()))
 
-    def _launch_kloop64(self, x, unit, out, shift, bias, res, res_up):
-        """One launch of the 64-output-channel K-loop kernel (aliby_nn_conv3x3_kloop64_bf16): the up path's 128 -> 64 convolution
-        through the upsample, fp32 accumulation over the whole reduction.  Booked with the other 64-channel launches."""
-        n, cin, cout = x.shape[0], x.shape[1], out.shape[1]
-        H, W = out.shape[2], out.shape[3]
-        sh = unit.shift if shift is None else shift
-        group = "conv3x3_mfma"
-        timer = self.eng.timed(group)
-        if timer.active:  # algorithmic bytes: half-resolution input + skip read once, output written once
-            st = self.conv_stats.setdefault(group, [0, 0])
-            st[0] += 2 * (x.numel() + out.numel() + (res.numel() if res is not None else 0))
-            st[1] += 2 * 9 * cin * cout * n * H * W
-        with timer:
-            _lib.check(self.lib.aliby_nn_conv3x3_kloop64_bf16(
-                self.h, _ptr(x), _ptr(self._pack(unit)), _ptr(out), _ptr(unit.scale), _ptr(sh), self._sps(sh),
-                _ptr(bias) if bias is not None else 0, _ptr(res) if res is not None else 0, 1 if res_up else 0, n, H, W, cin, cout,
-                1, _stream_ptr()))
+    _launch_deep = partialmethod(_launch_kloop, "aliby_nn_conv3x3_deep_bf16", "conv3x3_mfma_deep")
+    _launch_kloop64 = partialmethod(_launch_kloop, "aliby_nn_conv3x3_kloop64_bf16", "conv3x3_mfma")
 
     def _launch_unit(self, x, unit, kslice, nslice, out, shift, bias, res, res_up, in_up, pooled):
         n, ctot, cout_tot = x.shape[0], x.shape[1], out.shape[1]
@@ -378,14 +361,7 @@ class FusedUNet:
         if (cin, cout, bool(in_up)) == _KLOOP64:
             assert (ctot, cout_tot) == (cin, cout), "the K-loop kernel takes whole tensors"
             return self._launch_kloop64(x, unit, out, shift, bias, res, res_up)
-        if unit.wpk is None:
-            unit.wpk = {}
-        key = (k0, k1, n0, n1)
-        if key not in unit.wpk:
-            w = unit.w32[n0:n1, k0:k1].contiguous()
-            pk = torch.empty(cout * cin * 9, dtype=torch.bfloat16, device="cuda")
-            _lib.check(self.lib.aliby_nn_pack_conv3x3_bf16(self.h, _ptr(w), cout, w.shape[1], cin, _ptr(pk), _stream_ptr()))
-            unit.wpk[key] = pk
+        wpk = self._packed(unit, kslice, nslice)
         sh = unit.shift if shift is None else shift
         sh = sh[..., k0:k1]
         scale = unit.scale[k0:k1]
@@ -395,13 +371,11 @@ class FusedUNet:
         timer = self.eng.timed(group)
         if timer.active:  # algorithmic bytes / flops of exactly the launches that are bracketed with events
             px_out = n * H * W
-            st = self.conv_stats.setdefault(group, [0, 0])
-            st[0] += 2 * (x.numel() * cin // ctot + px_out * cout + (res.numel() * cout // cout_tot if res is not None else 0)
-                          + (px_out // 4 * cout if pooled is not None else 0))
-            st[1] += 2 * 9 * cin * cout * px_out
+            self._book(group, 2 * (x.numel() * cin // ctot + px_out * cout + (res.numel() * cout // cout_tot if res is not None else 0)
+                                   + (px_out // 4 * cout if pooled is not None else 0)), 2 * 9 * cin * cout * px_out)
         with timer:
             _lib.check(self.lib.aliby_nn_conv3x3_bf16(
-                self.h, _ptr(x), _ptr(unit.wpk[key]), _ptr(out), _ptr(scale), _ptr(sh), self._sps(sh),
+                self.h, _ptr(x), _ptr(wpk), _ptr(out), _ptr(scale), _ptr(sh), self._sps(sh),
                 _ptr(bias[n0:n1]) if bias is not None else 0, _ptr(res) if res is not None else 0, 1 if res_up else 0, n, H, W, cin, cout,
                 1 if in_up else 0, ctot, k0, cout_tot, n0, _ptr(pooled) if pooled is not None else 0, _stream_ptr()))
 
@@ -417,24 +391,19 @@ class FusedUNet:
     def _down_mfma(self, i, d, x_raw, x_act, x1=None):
         """Residual down block on the MFMA unit: 4 launches, no pointwise passes (x1 given: the first two units already ran)."""
         u = d["u"]
-        if x1 is not None:
-            pool = i + 1 < len(self.down) and u[3].w32.shape[0] <= 128
-            if self.fused_pair and tuple(u[2].w32.shape[:2]) == (32, 32) and tuple(u[3].w32.shape[:2]) == (32, 32):
-                return self._pair(x1, u[2], u[3], None, None, u[2].bias, u[3].bias, x1, pool=pool)
-            c2 = self._unit(x1, u[2], bias=u[2].bias)
-            return self._unit(c2, u[3], bias=u[3].bias, res=x1, pool=pool)
-        fuse_proj = (u[1].w32.shape[1], u[1].w32.shape[0]) in ((32, 32), (64, 64))  # projection rides in conv1's launch
-        p = None if fuse_proj else self._proj(x_raw, d["proj"])
-        if i == 0:  # 2 -> 32 channels: K = 18 is too thin for the matrix cores; c0 comes from the first-layer kernel (or
-            c0 = x_act if self._first_c0 else self._conv(x_act, u[0])  # MIOpen), its bias rides in the next shift
-            sh1 = d["shift1_b0"]
-        else:
-            c0 = self._unit(x_raw, u[0], bias=u[0].bias)
-            sh1 = None
-        if fuse_proj:
-            x1 = self._unit_proj(c0, u[1], sh1, d["pb1"], x_raw, d["proj"])
-        else:
-            x1 = self._unit(c0, u[1], shift=sh1, bias=d["pb1"], res=p)
+        if x1 is None:
+            fuse_proj = (u[1].w32.shape[1], u[1].w32.shape[0]) in ((32, 32), (64, 64))  # projection rides in conv1's launch
+            p = None if fuse_proj else self._proj(x_raw, d["proj"])
+            if i == 0:  # 2 -> 32 channels: K = 18 is too thin for the matrix cores; c0 comes from the first-layer kernel (or
+                c0 = x_act if self._first_c0 else self._conv(x_act, u[0])  # MIOpen), its bias rides in the next shift
+                sh1 = d["shift1_b0"]
+            else:
+                c0 = self._unit(x_raw, u[0], bias=u[0].bias)
+                sh1 = None
+            if fuse_proj:
+                x1 = self._unit_proj(c0, u[1], sh1, d["pb1"], x_raw, d["proj"])
+            else:
+                x1 = self._unit(c0, u[1], shift=sh1, bias=d["pb1"], res=p)
         pool = i + 1 < len(self.down) and u[3].w32.shape[0] <= 128
         if self.fused_pair and tuple(u[2].w32.shape[:2]) == (32, 32) and tuple(u[3].w32.shape[:2]) == (32, 32):
             return self._pair(x1, u[2], u[3], None, None, u[2].bias, u[3].bias, x1, pool=pool)
@@ -537,7 +506,8 @@ class FusedUNet:
             sh = [self._style_shift(k) for k in u[1:]]  # [N,C] views of the batched style projection
             _, a1 = self._fused(c0, skip, act=u[1], shift=sh[0], bias=u[0].bias)
             c1 = self._conv(a1, u[1])
-            x1, a2 = self._fused_up_sum(p_low, c1, up, u[2], sh[1], d["pb1"])
+            # A sets the output shape, so the (possibly low-resolution) projection is operand B, read through the upsample
+            x1, a2 = self._fused(c1, p_low, want_sum=True, act=u[2], shift=sh[1], upB=up, bias=d["pb1"])
             c2 = self._conv(a2, u[2])
             _, a3 = self._fused(c2, act=u[3], shift=sh[2], bias=u[2].bias)
             c3 = self._conv(a3, u[3])
@@ -553,18 +523,3 @@ class FusedUNet:
             _lib.check(self.lib.aliby_nn_nhwc_to_nchw_f32(self.h, _ptr(yb), n, H, W, yb.shape[1], yb.shape[1], _ptr(self.out.bias),
                                                           _ptr(y), _stream_ptr()))
         return y, style
-
-    def _fused_up_sum(self, p_low, c1, up, unit, shift, bias):
-        """x1 = upsample?(p_low) + c1 ; a2 = relu(bn(x1) + style shift).  A must be the full-resolution operand
-        for the output shape, so the (possibly low-res) projection goes in slot B."""
-        n, c, H, W = c1.shape
-        S, T = self._new(n, c, H, W), self._new(n, c, H, W)
-        timer = self.eng.timed("fused_pointwise")
-        if timer.active:
-            self.bytes_moved += 2 * (c1.numel() + p_low.numel() + 2 * c1.numel())
-        with timer:
-          _lib.check(self.lib.aliby_nn_fused_act_bf16(
-            self.h, _ptr(c1), _ptr(p_low), _ptr(S), _ptr(T), _ptr(bias), _ptr(unit.scale), _ptr(shift), n, H, W, c, 0,
-            1 if up else 0, 1, self._sps(shift),
-            _stream_ptr()))
-        return S, T

@@ -247,6 +247,12 @@ int aliby_nn_conv3x3_kloop64_bf16(aliby_ctx* ctx, const void* in, const void* wp
                                   const float* shift, int shift_per_sample, const float* bias, const void* res, int res_up,
                                   int N, int H, int W, int CIN, int COUT, int in_up, void* stream);
 
+/* The limits of the two K-loop units above, for a caller that routes by them: limits[0] = output positions per tile of
+ * aliby_nn_conv3x3_deep_bf16 (its minimum image with a per-sample shift is (H + 1) * (W + 2) >= limits[0] + 2 * (W + 2) + 2),
+ * limits[1] = its widest map, limits[2] and limits[3] = the same two figures of aliby_nn_conv3x3_kloop64_bf16.  Needs no
+ * device and no context. */
+int aliby_nn_conv3x3_kloop_limits(int limits[4]);
+
 /* The same unit on v_mfma_f32_16x16x32_bf16 (the shape the chip holds a higher clock on: nn_conv_deep.hip).  Same arguments and
  * meaning; `wpk16` is packed by aliby_nn_pack_conv3x3_deep16_bf16 (w_oihw float32 [COUT, CIN, 3, 3], COUT a multiple of 32, CIN
  * of 64 -> COUT * CIN * 9 bf16).  Accumulates 32 input channels per instruction: agrees with aliby_nn_conv3x3_deep_bf16 to fp32

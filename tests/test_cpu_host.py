@@ -38,6 +38,20 @@ def test_library_exports_every_declared_symbol():
     assert handle.aliby_abi_version() == 1
 
 
+def test_kloop_limits_are_the_figures_the_network_routing_follows():
+    """aliby_nn_conv3x3_kloop_limits: (DC_RUN, DC_WMAX, U_RUN, U_WMAX) of csrc/nn_conv_deep.hip, which FusedUNet routes by.  Needs
+    no device.  A window of RUN + 2 rows + 2 positions: RUN + 2 = 226 and 450 are the figures today's routing follows, so a
+    kernel change that moves them edits this test knowingly."""
+    from aliby_amd import _lib
+
+    limits = (ctypes.c_int * 4)()
+    assert _lib.load().aliby_nn_conv3x3_kloop_limits(limits) == _lib.OK
+    limits = list(limits)
+    assert all(isinstance(v, int) and v > 0 for v in limits), limits
+    assert limits[2] == 2 * limits[0]
+    assert limits[0] + 2 == 226 and limits[2] + 2 == 450
+
+
 def test_no_gpu_fails_loudly():
     import torch
 

@@ -260,6 +260,44 @@ def test_fused_unet_matches_module_forward(engine):
     assert torch.equal(ya, yd)
 
 
+@pytest.mark.parametrize("n,h,w", [(2, 32, 32), (8, 224, 224)])
+def test_fused_unet_weight_caches_do_not_leak_between_routes(engine, n, h, w):
+    """One FusedUNet keeps every packed weight it has made (FusedUNet._packed, _packed_proj) while its route switches are flipped
+    one after the other; after each flip it gives exactly the bits of a fresh instance built with that switch, so no packing made
+    under one route is read under another.  (2, 32, 32): level 3 is a 4 x 4 map, below one tile window of the K-loop kernels, so
+    the K/N-slice launches and the unpacked forms run; (8, 224, 224): N % 8 == 0, the packed forms at W = 112, 56, 28 and both
+    K-loop kernels run.  The switches whose two routes are the same arithmetic also give the bits of the default run."""
+    import torch
+    from aliby_amd.segment.fused_unet import FusedUNet
+    from aliby_amd.segment.unet import build_network
+
+    net = build_network(seed=7, device="cuda")
+    g = torch.Generator(device="cpu").manual_seed(3)
+    for m in net.modules():
+        if isinstance(m, torch.nn.BatchNorm2d):
+            m.running_mean.copy_(torch.randn(m.num_features, generator=g) * 0.2)
+            m.running_var.copy_(torch.rand(m.num_features, generator=g) + 0.5)
+            m.weight.data.copy_(torch.rand(m.num_features, generator=g) + 0.5)
+            m.bias.data.copy_(torch.randn(m.num_features, generator=g) * 0.1)
+    x = torch.randn(n, 2, h, w, generator=g).cuda().contiguous()
+    kept = FusedUNet(net, engine)
+    y0, s0 = kept(x)
+    same_bits = ("fused_first", "fused_pair", "fused_head", "pair_head")
+    for flag in same_bits + ("deep_kernel", "kloop64_kernel"):
+        default = getattr(kept, flag)
+        setattr(kept, flag, not default)
+        y, s = kept(x)
+        fresh = FusedUNet(net, engine)
+        setattr(fresh, flag, not default)
+        yf, sf = fresh(x)
+        assert torch.equal(y, yf) and torch.equal(s, sf), flag
+        if flag in same_bits:
+            assert torch.equal(y, y0) and torch.equal(s, s0), flag
+        setattr(kept, flag, default)
+    y, s = kept(x)  # back on the default route, with every other route's packings in the caches
+    assert torch.equal(y, y0) and torch.equal(s, s0)
+
+
 @pytest.mark.parametrize("n,h,w", [(4, 256, 256), (3, 128, 128), (2, 176, 208), (5, 64, 96), (2, 32, 32), (2, 16, 16), (7, 24, 40)])
 def test_fused_unet_at_other_tile_sizes(engine, n, h, w):
     """The network at tile sizes other than cellpose 3's 224 x 224 — `eval(bsize=256)` (cellpose 4's default), small images
