@@ -14,8 +14,9 @@
 // The scratch rule.  A global-form launch borrows ctx->scratch until the stream has passed it, and the next one (or any other
 // user of the context's scratch) may move or overwrite the block: only ONE may be in flight per context.  Launches on one
 // stream are ordered, and a thread has a context of its own (aliby_amd/_lib.py, default_context); what must not happen is two
-// streams of one context running global forms side by side.  The only place that fans per-object launches out over streams,
-// _FanOut in aliby_amd/extraction/families.py, does so when max_h * max_w <= 4096, which keeps every box-sized and area-sized
+// streams of one context running global forms side by side.  Whoever sends per-object launches of one context to several streams
+// (_FanOut in aliby_amd/extraction/families.py, the early colocalisation launch of aliby_amd/runner.py) asks
+// ObjectTable.lds_resident (aliby_amd/extraction/engine.py) first: max_h * max_w <= 4096, which keeps every box-sized and area-sized
 // site in LDS.  It does not by itself keep k_shape_hull there: its working set grows with max_h alone (about 152 max_h bytes), so
 // a box taller than about 646 rows and at most 6 wide passes that test and still sends the hull to the global form.  That is
 // harmless today only because one hull launch (sizeshape or feret) is in flight per evaluation.

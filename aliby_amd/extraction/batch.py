@@ -10,7 +10,7 @@ the device-side core both `process_tree_masks` and bench.py go through: labels [
 from __future__ import annotations
 
 from aliby_amd.extraction import families
-from aliby_amd.extraction.extract import flatten, kv
+from aliby_amd.extraction.extract import column_names, flatten, kv
 
 
 def instructions_of(tree) -> list:
@@ -25,8 +25,4 @@ def extract_batch(eng, labels_dev, planes, tree, cp_measure_kwargs=None, multi=F
         table = eng.object_table(labels_dev)
     instructions = instructions_of(tree)
     matrix, blocks = families.evaluate(eng, labels_dev, table, planes, instructions, cp_measure_kwargs or {}, multi=multi)
-    names = []
-    for inst, (start, keys) in zip(instructions, blocks):
-        branch = "/".join(str(x) for x in inst)
-        names.extend([f"{branch}/{inst[-1]}"] if keys is None else [f"{branch}/{k}" for k in keys])
-    return matrix, names, table
+    return matrix, column_names(instructions, blocks), table

@@ -8,6 +8,7 @@ HIP kernel in libaliby_hip.so reached through ctypes.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass
 
 import numpy as np
@@ -79,6 +80,12 @@ class ObjectTable:
     max_area: int
     max_h: int
     max_w: int
+
+    @property
+    def lds_resident(self) -> bool:
+        """Every object window fits the LDS forms of the box- and area-sized kernels: only then may per-object launches of one context
+        run side by side on several streams (the scratch rule, and what this does not guarantee: aliby_amd/csrc/object_launch.h)."""
+        return self.n_obj > 0 and self.max_h * self.max_w <= 4096
 
 
 class _NoTimer:
@@ -221,6 +228,19 @@ class FeatureEngine:
             launches = self._sample_count.get(name, len(evs)) if self.profile_sample.get(name, 1) > 1 else len(evs)
             out[name] = {"ms_total": timed_ms * launches / max(len(evs), 1), "launches": launches, "timed_launches": len(evs)}
         self._sample_count = {}
+        return out
+
+    # ------------------------------------------------------------------ z-reduction
+    _REDUCED = {_lib.U16: torch.uint16, _lib.F32: torch.float32, _lib.U64: torch.uint64, _lib.F64: torch.float64}
+
+    def reduce_z(self, t: torch.Tensor, op: int, in_dtype: int, out_dtype: int) -> torch.Tensor:
+        """[..., Z, Y, X] -> [..., Y, X]: the reduction `op` (_lib.RED_MAX / RED_ADD / RED_DIV) over Z of contiguous uint16 or
+        float32 planes (`in_dtype`), written as `out_dtype` (U16, F32, or NumPy's own U64 / F64; aliby_reduce_z)."""
+        *lead, Z, Y, X = t.shape
+        out = torch.empty((*lead, Y, X), dtype=self._REDUCED[out_dtype], device=t.device)
+        with self.timed("reduce_z"):
+            _lib.check(self.lib.aliby_reduce_z(self.ctx.handle, _ptr(t), in_dtype, math.prod(lead), Z, Y * X, op, _ptr(out), out_dtype,
+                                               _stream_ptr()))
         return out
 
     # ------------------------------------------------------------------ objects

@@ -122,14 +122,16 @@ class DeviceResults(Sequence):
         return {key: self.matrix[row, start + j : start + j + 1] for j, key in enumerate(keys)}
 
     def column_names(self):
-        names = []
-        for inst, (start, keys) in zip(self.instructions, self.blocks):
-            branch = "/".join(str(x) for x in inst)
-            if keys is None:
-                names.append(f"{branch}/{inst[-1]}")
-            else:
-                names.extend(f"{branch}/{key}" for key in keys)
-        return names
+        return column_names(self.instructions, self.blocks)
+
+
+def column_names(instructions, blocks) -> list:
+    """"<branch>/<key>" of every column of the feature matrix: the branch is the instruction's path, a scalar metric's key its name."""
+    names = []
+    for inst, (start, keys) in zip(instructions, blocks):
+        branch = "/".join(str(x) for x in inst)
+        names.extend(f"{branch}/{key}" for key in ([inst[-1]] if keys is None else keys))
+    return names
 
 
 def _stack_masks(masks):
@@ -316,9 +318,7 @@ def process_tree_masks(tree, masks, pixels, measure_fn, ncores=None, progress_ba
     # recovering objects and instructions from the materialised tuple cost 3 of a position's 18 ms); the caller gets the tuple
     # the reference returns
     lazy = LazyProduct(ind_masks, instructions)
-    extra = {}
-    if cp_measure_kwargs is not None:
-        extra["cp_measure_kwargs"] = cp_measure_kwargs
+    extra = {} if cp_measure_kwargs is None else {"cp_measure_kwargs": cp_measure_kwargs}
     result = measure_fn(lazy, masks, pixels, ncores=ncores, progress_bar=progress_bar, **extra)
     return tuple(lazy), result
 
@@ -342,9 +342,7 @@ def process_tree_masks_overlap(tree, masks, pixels, measure_fn, ncores=None, pro
     tile_stack_mask = [(tile_i, stack_i, int(mask_i)) for (tile_i, stack_i), inv in inverse.items()
                        for mask_i in inv.in_values[inv.in_values > 0]]
     tileid_instructions = tuple(product(tile_stack_mask, instructions))
-    extra = {}
-    if cp_measure_kwargs is not None:
-        extra["cp_measure_kwargs"] = cp_measure_kwargs
+    extra = {} if cp_measure_kwargs is None else {"cp_measure_kwargs": cp_measure_kwargs}
     result = measure_fn(tileid_instructions, masks, pixels, ncores=ncores, progress_bar=progress_bar, **extra)
     return tileid_instructions, result
 

@@ -5,15 +5,22 @@ Plays the role of the reference's CELL_FUNS / REDUCTION_FUNS registries
 (src/extraction/core/functions/loaders.py:28-79,110-127): names are the cp_measure feature names
 bound at loaders.py:71-77 plus the in-repo cell.py metrics (loaders.py:19-25).  A name that is not
 registered raises KeyError, as `CELL_FUNS[metric]` does (extract.py:147-153).
+
+`evaluate` is `plan` (pure: no engine, table or tensor) followed by one executor for the single-channel and one for the
+channel-pair instructions; tests/test_cpu_feature_dispatch.py replays both on a recording engine.
 """
 
 from __future__ import annotations
+
+import os
+from contextlib import nullcontext
+from dataclasses import dataclass, field, replace
+from typing import Callable
 
 import torch
 
 from aliby_amd import _lib
 from aliby_amd.extraction import features as feat
-from aliby_amd.extraction.engine import _ptr, _stream_ptr
 
 _RED = {"max": _lib.RED_MAX, "add": _lib.RED_ADD, "div": _lib.RED_DIV}
 
@@ -49,161 +56,149 @@ class PlaneCache:
                 raise NotImplementedError(f"reduce_z 'add' over Z={Z} uint16 planes exceeds the exact float32 range (Z <= 256)")
             dt = self.dtype if op == _lib.RED_MAX else _lib.F32
             # (the maximum over z of 8-bit values is still 8-bit: the code U8W stays on the plane for the texture kernel)
-            out = torch.empty((F, C, Y, X), dtype=torch.uint16 if dt != _lib.F32 else torch.float32,
-                              device=self.tensor.device)
-            with self.eng.timed("reduce_z"):
-                _lib.check(
-                    self.eng.lib.aliby_reduce_z(self.eng.ctx.handle, _ptr(self.tensor), _lib.U16 if integer else _lib.F32,
-                                                F * C, Z, Y * X, op, _ptr(out), _lib.U16 if dt != _lib.F32 else _lib.F32,
-                                                _stream_ptr())
-                )
+            out = self.eng.reduce_z(self.tensor, op, _lib.U16 if integer else _lib.F32, _lib.U16 if dt != _lib.F32 else _lib.F32)
         self._cache[red_z] = (out, dt)
         return out, dt
 
 
-def _launch_intensity(eng, labels, table, plane, dt, ch, out, col0, kw):
-    eng.intensity(labels, plane, dt, ch, table, out, col0, edge_measurements=kw.get("edge_measurements", True))
+# The [n_obj, 17] cell.py blocks of one evaluation: every metric of a (plane, channel) comes from ONE launch of k_cell
+# (FeatureEngine.cell_metrics).  Handed to every launcher; the cell.py metrics and nuc_est_conv's median read it.
+class _CellBlocks:
+    def __init__(self, eng, labels, table):
+        self.eng, self.labels, self.table = eng, labels, table
+        self._blocks = {}
+
+    def column(self, plane, dt, ch, metric):
+        key = None if plane is None else (plane.data_ptr(), ch)
+        if key not in self._blocks:
+            self._blocks[key] = self.eng.cell_metrics(self.labels, plane, dt, ch, self.table)
+        return self._blocks[key][:, self.eng.CELL_COLUMNS.index(metric)]
 
 
-def _launch_sizeshape(eng, labels, table, plane, dt, ch, out, col0, kw):
+@dataclass(frozen=True)
+class Family:  # one registered metric
+    # names(kw) -> the keys of its columns, or None for a scalar (one column, named after the metric)
+    names: Callable
+    # launch(eng, labels, table, plane, dt, ch, out, col0, kw, cells) writes out[:, col0:...]; plane / dt / ch are None / 0 / None
+    # for a family without pixels, kw holds keywords of BUILT_KWARGS only (`plan` refuses the rest), `cells` is the evaluation's
+    # _CellBlocks.  None for the channel-pair metrics, which are launched in groups (`Plan.batches`).
+    launch: Callable | None = None
+    needs_pixels: bool = True
+    # launched on the main stream after the fan-out has joined: the cell.py metrics share cached blocks, granularity iterates to a
+    # fixed point and waits on its stream in between, large objects of nuc_conv_3d take the global-scratch form
+    after_join: bool = False
+    # handed the un-reduced [F,C,Z,Y,X] stack instead of one z-reduced plane; valid only under a channel with the reducer key
+    # "None", ALIBY's spelling of "do not reduce" (the reference's reduce_z raises on it, and upstream reaches the function through
+    # its custom loader).  Every other metric under "None" keeps raising "invalid reducer".
+    stack: bool = False
+
+
+def _scalar(kw):
+    return None
+
+
+def _launch_intensity(eng, labels, table, plane, dt, ch, out, col0, kw, cells):
+    eng.intensity(labels, plane, dt, ch, table, out, col0, **kw)
+
+
+def _launch_sizeshape(eng, labels, table, plane, dt, ch, out, col0, kw, cells):
     eng.sizeshape(labels, table, out, col0)
 
 
-def _launch_feret(eng, labels, table, plane, dt, ch, out, col0, kw):
+def _launch_feret(eng, labels, table, plane, dt, ch, out, col0, kw, cells):
     eng.feret(labels, table, out, col0)
 
 
-def _launch_zernike(eng, labels, table, plane, dt, ch, out, col0, kw):
+def _launch_zernike(eng, labels, table, plane, dt, ch, out, col0, kw, cells):
     eng.zernike(labels, None, 0, 0, table, out, col0, weighted=False)
 
 
-def _launch_radial_zernikes(eng, labels, table, plane, dt, ch, out, col0, kw):
+def _launch_radial_zernikes(eng, labels, table, plane, dt, ch, out, col0, kw, cells):
     eng.zernike(labels, plane, dt, ch, table, out, col0, weighted=True)
 
 
-def _launch_texture(eng, labels, table, plane, dt, ch, out, col0, kw):
-    eng.texture(labels, plane, dt, ch, table, out, col0, scale=kw.get("scale", 3), gray_levels=kw.get("gray_levels", 256))
+def _launch_texture(eng, labels, table, plane, dt, ch, out, col0, kw, cells):
+    eng.texture(labels, plane, dt, ch, table, out, col0, **kw)
 
 
-def _launch_radial_distribution(eng, labels, table, plane, dt, ch, out, col0, kw):
-    eng.radial_distribution(labels, plane, dt, ch, table, out, col0, bin_count=kw.get("bin_count", 4),
-                            scaled=kw.get("scaled", True), maximum_radius=kw.get("maximum_radius", 100))
+def _launch_radial_distribution(eng, labels, table, plane, dt, ch, out, col0, kw, cells):
+    eng.radial_distribution(labels, plane, dt, ch, table, out, col0, **kw)
 
 
-def _launch_granularity(eng, labels, table, plane, dt, ch, out, col0, kw, **_):
+def _launch_granularity(eng, labels, table, plane, dt, ch, out, col0, kw, cells):
     if kw.get("image_mask", "frame") != "frame":
         # the reference measures one object at a time on a single-object label image (extract.py:147-153): with the objects as
         # the image mask, every object would get its own background and spectrum images.  Not built.
         raise NotImplementedError("granularity(image_mask='objects') through the extraction tree is not built: the batched "
                                   "kernels share one image-level spectrum per tile (image_mask='frame', CellProfiler's default)")
-    eng.granularity(labels, plane, dt, ch, table, out, col0, **{k: kw[k] for k in _GRANULARITY_KWARGS if k in kw})
-
-
-_GRANULARITY_KWARGS = ("subsample_size", "image_sample_size", "element_size", "granular_spectrum_length", "image_mask", "mask_order")
-
-# name -> {names(kw) -> list[str] | None (scalar), launch, needs_pixels[, cell, stack]}
-MONO = {
-    "intensity": dict(names=lambda kw: feat.intensity_names(kw.get("edge_measurements", True)),
-                      launch=_launch_intensity, needs_pixels=True),
-    "sizeshape": dict(names=lambda kw: feat.sizeshape_names(), launch=_launch_sizeshape, needs_pixels=False),
-    "feret": dict(names=lambda kw: feat.feret_names(), launch=_launch_feret, needs_pixels=False),
-    "zernike": dict(names=lambda kw: feat.zernike_names(), launch=_launch_zernike, needs_pixels=False),
-    "radial_zernikes": dict(names=lambda kw: feat.radial_zernike_names(), launch=_launch_radial_zernikes,
-                            needs_pixels=True),
-}
-MULTI = {name: dict(names=(lambda kw, _n=name: list(feat.COLOC[_n]))) for name in feat.COLOC}
-
-# cell.py metrics (loaders.py:19-25): scalar results, one column each; every metric of a (channel, red_z)
-# comes from ONE launch of k_cell whose 17-column block is cached in `cell_cache`.
-_CELL_MASK_ONLY = ("area", "centroid_x", "centroid_y", "conical_volume", "eccentricity", "spherical_volume", "volume")
-_CELL_PIXELS = ("mean", "median", "std", "total", "total_squared", "max2p5pc", "max5px_median", "moment_of_inertia")
+    eng.granularity(labels, plane, dt, ch, table, out, col0, **kw)
 
 
 def _make_cell_launch(metric):
-    def launch(eng, labels, table, plane, dt, ch, out, col0, kw, cell_cache=None):
-        key = (None if plane is None else (plane.data_ptr(), ch))
-        if cell_cache is None:
-            cell_cache = {}
-        if key not in cell_cache:
-            cell_cache[key] = eng.cell_metrics(labels, plane, dt, ch, table)
-        j = eng.CELL_COLUMNS.index(metric)
-        out[:, col0] = cell_cache[key][:, j]
+    def launch(eng, labels, table, plane, dt, ch, out, col0, kw, cells):
+        out[:, col0] = cells.column(plane, dt, ch, metric)
 
     return launch
 
 
-for _m in _CELL_MASK_ONLY:
-    MONO[_m] = dict(names=lambda kw: None, launch=_make_cell_launch(_m), needs_pixels=False, cell=True)
-for _m in _CELL_PIXELS:
-    MONO[_m] = dict(names=lambda kw: None, launch=_make_cell_launch(_m), needs_pixels=True, cell=True)
-
-
-def _launch_nuc_est_conv(eng, labels, table, plane, dt, ch, out, col0, kw, cell_cache=None):
+def _launch_nuc_est_conv(eng, labels, table, plane, dt, ch, out, col0, kw, cells):
     # custom/localisation.py, with its defaults (an entry of cp_measure_kwargs named after an in-repo function is not looked at).
-    # The median it subtracts is a column of the (plane, channel)'s cell.py block, shared with the metrics above.
+    # The median it subtracts is a column of the (plane, channel)'s cell.py block, shared with the cell.py metrics.
     if plane is None:
         raise Exception("nuc_est_conv needs the pixels of a channel")
-    key = (plane.data_ptr(), ch)
-    if cell_cache is None:
-        cell_cache = {}
-    if key not in cell_cache:
-        cell_cache[key] = eng.cell_metrics(labels, plane, dt, ch, table)
-    eng.nuc_est_conv(labels, plane, dt, ch, table, out, col0, median=cell_cache[key][:, eng.CELL_COLUMNS.index("median")])
+    eng.nuc_est_conv(labels, plane, dt, ch, table, out, col0, median=cells.column(plane, dt, ch, "median"))
 
 
-# An extension of this fork's registry: the reference reaches the function through its custom loader, not load_cellfuns_core.
-MONO["nuc_est_conv"] = dict(names=lambda kw: None, launch=_launch_nuc_est_conv, needs_pixels=True, cell=True)
-
-
-def _launch_nuc_conv_3d(eng, labels, table, stack, dt, ch, out, col0, kw, cell_cache=None):
-    # custom/localisation.py:123-140, with its defaults.  `stack` is the un-reduced [F,C,Z,Y,X] block (see `stack=True` below).
+def _launch_nuc_conv_3d(eng, labels, table, stack, dt, ch, out, col0, kw, cells):
+    # custom/localisation.py:123-140, with its defaults.  `stack` is the un-reduced [F,C,Z,Y,X] block (Family.stack).
     eng.nuc_conv_3d(labels, stack, dt, ch, table, out, col0)
 
 
-# Another extension.  `stack=True`: the metric is handed the un-reduced stack instead of one z-reduced plane, and is valid only
-# under a channel with the reducer key "None", ALIBY's spelling of "do not reduce" (the reference's reduce_z raises on it, and
-# upstream reaches the function through its custom loader).  Every other metric under "None" keeps raising "invalid reducer".
-# `cell=True`: launched on the main stream after the fan-out has joined, since large objects take the global-scratch form.
-MONO["nuc_conv_3d"] = dict(names=lambda kw: None, launch=_launch_nuc_conv_3d, needs_pixels=True, cell=True, stack=True)
-
-
-def _launch_ratio(eng, labels, table, plane, dt, ch, out, col0, kw):
+def _launch_ratio(eng, labels, table, plane, dt, ch, out, col0, kw, cells):
     # cell.ratio needs a [Y, X, 2] image (cell.py:270); the extraction path hands every metric ONE z-reduced plane, so the
     # reference returns NaN for every object here.  The two-channel form is FeatureEngine.cell_ratio / functions.ratio.
     out[:, col0] = float("nan")
 
 
-MONO["ratio"] = dict(names=lambda kw: None, launch=_launch_ratio, needs_pixels=True)
+MONO = {
+    "intensity": Family(lambda kw: feat.intensity_names(kw.get("edge_measurements", True)), _launch_intensity),
+    "sizeshape": Family(lambda kw: feat.sizeshape_names(), _launch_sizeshape, needs_pixels=False),
+    "feret": Family(lambda kw: feat.feret_names(), _launch_feret, needs_pixels=False),
+    "zernike": Family(lambda kw: feat.zernike_names(), _launch_zernike, needs_pixels=False),
+    "radial_zernikes": Family(lambda kw: feat.radial_zernike_names(), _launch_radial_zernikes),
+    "texture": Family(lambda kw: feat.texture_names(kw.get("scale", 3), kw.get("gray_levels", 256)), _launch_texture),
+    "radial_distribution": Family(lambda kw: feat.radial_distribution_names(kw.get("bin_count", 4), kw.get("scaled", True)),
+                                  _launch_radial_distribution),
+    "granularity": Family(lambda kw: feat.granularity_names(kw.get("granular_spectrum_length", 16)), _launch_granularity,
+                          after_join=True),
+    "ratio": Family(_scalar, _launch_ratio),
+    # extensions of this fork's registry: the reference reaches the two functions through its custom loader, not load_cellfuns_core
+    "nuc_est_conv": Family(_scalar, _launch_nuc_est_conv, after_join=True),
+    "nuc_conv_3d": Family(_scalar, _launch_nuc_conv_3d, after_join=True, stack=True),
+}
+# cell.py metrics (loaders.py:19-25): scalar results, one column each
+for _m in ("area", "centroid_x", "centroid_y", "conical_volume", "eccentricity", "spherical_volume", "volume"):
+    MONO[_m] = Family(_scalar, _make_cell_launch(_m), needs_pixels=False, after_join=True)
+for _m in ("mean", "median", "std", "total", "total_squared", "max2p5pc", "max5px_median", "moment_of_inertia"):
+    MONO[_m] = Family(_scalar, _make_cell_launch(_m), after_join=True)
+MULTI = {name: Family(lambda kw, _n=name: list(feat.COLOC[_n])) for name in feat.COLOC}
 
 
 def register_optional(eng_cls):
-    """Families whose kernels are built in later commits register themselves when the engine has them."""
-    if hasattr(eng_cls, "texture"):
-        MONO["texture"] = dict(names=lambda kw: feat.texture_names(kw.get("scale", 3), kw.get("gray_levels", 256)),
-                               launch=_launch_texture, needs_pixels=True)
-    if hasattr(eng_cls, "granularity"):
-        # `cell` = run on the main stream after the fan-out has joined: the call iterates to a fixed point and waits on its
-        # stream in between
-        MONO["granularity"] = dict(names=lambda kw: feat.granularity_names(kw.get("granular_spectrum_length", 16)),
-                                   launch=_launch_granularity, needs_pixels=True, cell=True)
-    if hasattr(eng_cls, "radial_distribution"):
-        MONO["radial_distribution"] = dict(names=lambda kw: feat.radial_distribution_names(kw.get("bin_count", 4), kw.get("scaled", True)),
-                                           launch=_launch_radial_distribution, needs_pixels=True)
+    """Does nothing: every family is registered when this module is imported.  Kept because the benchmark calls it."""
 
 
 class _FanOut:
     """Per-object kernels are one small workgroup per object: latency-bound and far from filling 256 CUs, so
     independent instructions (different channels / families / channel pairs) go to a few side HIP streams and run
     concurrently.  fork(): side streams wait for the main stream; join(): the main stream waits for them.  Only
-    taken when every object window is LDS-resident: a global-scratch launch borrows the context's scratch, so only one may be
-    in flight per context (the rule, and what this condition does and does not guarantee: aliby_amd/csrc/object_launch.h)."""
+    taken when every object window is LDS-resident (ObjectTable.lds_resident): a global-scratch launch borrows the context's
+    scratch, so only one may be in flight per context (the rule, and what this condition does and does not guarantee:
+    aliby_amd/csrc/object_launch.h)."""
 
     def __init__(self, eng, table, out):
-        import os
-
         n = int(os.environ.get("ALIBY_FEATURE_STREAMS", "4"))
-        small = table.n_obj > 0 and table.max_h * table.max_w <= 4096
-        self.enabled = n > 1 and small and out.is_cuda
+        self.enabled = n > 1 and table.lds_resident and out.is_cuda
         self.out = out
         self.k = 0
         if self.enabled:
@@ -222,7 +217,7 @@ class _FanOut:
 
     def next_stream(self):
         if not self.enabled:
-            return _NULL_CTX
+            return nullcontext()
         i = self.k % len(self.streams)
         self.k += 1
         self.used.add(i)
@@ -237,17 +232,6 @@ class _FanOut:
                 ev.record(self.streams[i])
                 main.wait_event(ev)
             self.used.clear()
-
-
-class _NullCtx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
-
-
-_NULL_CTX = _NullCtx()
 
 
 # the functions the reference takes from cp_measure (get_core_measurements / get_correlation_measurements, loaders.py:71-77): only
@@ -265,11 +249,38 @@ BUILT_KWARGS = {
     "costes": ("scale_max",),
 }
 
+LAUNCH, COPY, GROUP = "launch", "copy", "group"
 
-def evaluate(eng, labels, table, planes, instructions, cp_measure_kwargs, multi=False):
-    """Run every instruction over every object; returns (matrix [n_obj, n_cols] on device, blocks)."""
-    register_optional(type(eng))
-    blocks, specs = [], []
+
+@dataclass(frozen=True)
+class Step:
+    """One instruction of a plan: its registry entry, its keywords and its columns [col0, col0 + ncols)."""
+
+    inst: tuple
+    family: Family
+    kw: dict
+    col0: int
+    ncols: int
+    # single-channel plans: LAUNCH on its own; COPY, its columns are in `Plan.copies`; GROUP, a member of `Plan.zernike_groups`
+    role: str = LAUNCH
+
+
+@dataclass(frozen=True)
+class Plan:
+    blocks: list  # per instruction (first column, names | None): the second return value of `evaluate`
+    n_cols: int
+    steps: list
+    # single-channel instructions
+    copies: list = field(default_factory=list)  # (first column, source column, columns), after the join
+    zernike_groups: dict = field(default_factory=dict)  # red_z -> [(channel, first column)]: channels of one plane block, one launch
+    # channel pairs, in launch order
+    prefetch: list = field(default_factory=list)  # (red_z, pair, whether its rank planes are needed) on the main stream
+    batches: dict = field(default_factory=dict)  # (red_z, thr, scale_max) -> [(pair, {metric: first column})]: one launch each
+
+
+def plan(instructions, cp_measure_kwargs, multi=False) -> Plan:
+    """What `evaluate` will do for these instructions, and every refusal that depends on the names and keywords alone."""
+    blocks, steps = [], []
     col = 0
     for inst in instructions:
         metric = inst[-1]
@@ -282,138 +293,137 @@ def evaluate(eng, labels, table, planes, instructions, cp_measure_kwargs, multi=
         unbuilt = sorted(set(kw) - set(BUILT_KWARGS.get(metric, ()))) if metric in CP_MEASURE_NAMES else ()
         if unbuilt:
             raise NotImplementedError(f"cp_measure_kwargs[{metric!r}]: {unbuilt} not built (built: {sorted(BUILT_KWARGS.get(metric, ()))})")
-        if reg[metric].get("stack") and (inst[0] == "None" or inst[1] != "None"):
+        if reg[metric].stack and (inst[0] == "None" or inst[1] != "None"):
             raise Exception(f"{metric} needs the un-reduced stack of a channel: list it under a channel with the reducer key "
                             f"'None', not under {inst[0]!r} / {inst[1]!r}")
-        names = reg[metric]["names"](kw)
+        names = reg[metric].names(kw)
+        ncols = 1 if names is None else len(names)
         blocks.append((col, names))
-        specs.append((inst, reg[metric], kw, col, 1 if names is None else len(names)))
-        col += 1 if names is None else len(names)
-    out = eng.new_output(table.n_obj, col)
-    cache = PlaneCache(eng, planes) if planes is not None else None
+        steps.append(Step(inst, reg[metric], kw, col, ncols))
+        col += ncols
+    return (_plan_multi if multi else _plan_mono)(blocks, col, steps)
 
-    fan = _FanOut(eng, table, out)
-    if multi:
-        # one launch per (pair, red_z): every requested colocalisation metric of that pair together
-        groups = {}
-        for inst, reg, kw, col0, _ in specs:
-            (ch0, ch1), red_ch, red_z, metric = inst[0], inst[1], inst[2], inst[3]
-            if red_ch != "None":
-                raise NotImplementedError(
-                    "channel-combining multi instructions (extract.py:227-235) are not built; "
-                    "the builder only emits red_ch='None' (pipe_builder.py:33-43)"
-                )
-            # kwargs are per feature name, as the reference bakes them into one partial per name (loaders.py:71-77):
-            # manders_fold's thr must not leak into rwc.  The kernel takes one thr per launch, so metrics of a pair whose
-            # thresholds differ go to separate launches (sub-group key = the thr the launch will carry).
-            thr = float(kw.get("thr", 15.0)) if metric in ("manders_fold", "rwc") else None
-            scale_max = float(kw.get("scale_max", 255.0)) if metric == "costes" else None
-            groups.setdefault(((ch0, ch1), red_z), []).append((metric, col0, thr, scale_max))
-        split = {}
-        for key, entries in groups.items():
-            thrs = sorted({t for _, _, t, _ in entries if t is not None})
-            scale_max = next((sm for _, _, _, sm in entries if sm is not None), 255.0)
-            if len(thrs) <= 1:
-                split[(key, 0)] = dict(cols={m: c for m, c, _, _ in entries}, thr=thrs[0] if thrs else 15.0, scale_max=scale_max)
-            else:  # threshold-free metrics ride with the first threshold's launch
-                for k, t in enumerate(thrs):
-                    cols = {m: c for m, c, tt, _ in entries if tt == t or (tt is None and k == 0)}
-                    split[(key, k)] = dict(cols=cols, thr=t, scale_max=scale_max)
-        groups = {(pair_z, k): g for (pair_z, k), g in split.items()}
-        if cache is None:
-            raise Exception("pixels are required for colocalisation instructions")
-        for (((ch0, ch1), red_z), _k), g in groups.items():  # shared inputs first, on the main stream: z-reduction, rank planes
-            plane, dt = cache.get(red_z)
-            if "rwc" in g["cols"]:
-                eng.rank_planes(labels, plane, dt, table, (ch0, ch1))
-        # every pair that shares a z-reduction and its parameters goes into one launch (csrc/feat_coloc.hip, k_coloc_pairs)
-        import os
 
-        batches = {}
-        for (((ch0, ch1), red_z), _k), g in groups.items():
-            batches.setdefault((red_z, g["thr"], g["scale_max"]), []).append(((ch0, ch1), g["cols"]))
-        left = []
-        for (red_z, thr, scale_max), pairs in batches.items():
-            plane, dt = cache.get(red_z)
-            if os.environ.get("ALIBY_COLOC_PAIRS", "1") == "0" or len(pairs) < 2 or not eng.coloc_pairs(
-                    labels, plane, dt, pairs, table, out, thr=thr, scale_max=scale_max):
-                left.extend((pair, red_z, cols, thr, scale_max) for pair, cols in pairs)
-        if left:
-            fan.fork()
-            for (ch0, ch1), red_z, cols, thr, scale_max in left:
-                plane, dt = cache.get(red_z)
-                with fan.next_stream():
-                    eng.coloc(labels, plane, dt, ch0, ch1, table, out, cols, thr=thr, scale_max=scale_max)
-            fan.join()
-        return out, blocks
-
-    # shared, pixel-independent inputs first, on the main stream (each is cached on the object table)
-    for inst, reg, kw, col0, ncols in specs:
-        metric = inst[-1]
-        if inst[0] != "None" and reg["needs_pixels"] and cache is not None and inst[1] in _RED:
-            cache.get(inst[1])
-        if metric in ("zernike", "radial_zernikes") and table.n_obj:
-            eng.mec(labels, table)
-        if metric == "radial_distribution" and table.n_obj:
-            eng.radial_geometry(labels, table, kw.get("bin_count", 4), None if kw.get("scaled", True) else kw.get("maximum_radius", 100))
-    fan.fork()
-    done = {}  # (metric, kwargs) of pixel-independent families already computed -> first column
-    copies, after = [], []
-    zern_groups = {}  # red_z -> [(channel, first column)] of the radial_zernikes instructions
-    sizeshape_col0 = next((c0 for inst, reg, kw, c0, _ in specs if inst[-1] == "sizeshape"), None)
-    cell_cache = {}
-    for spec in specs:
-        inst, reg, kw, col0, ncols = spec
-        ch, red_z, metric = inst[0], inst[1], inst[-1]
-        if reg.get("cell"):
-            after.append(spec)  # cell.py metrics share a cached block: main stream, after the join
-            continue
-        if ch == "None" or not reg["needs_pixels"]:
-            if ch != "None" and cache is not None:
-                cache.get(red_z)  # the reference would still reduce (and raise on a bad reducer)
-            key = (metric, tuple(sorted(kw.items())))
+def _plan_mono(blocks, n_cols, steps) -> Plan:
+    done = {}  # (metric, kwargs) of pixel-independent families already launched -> first column
+    copies, zernike_groups = [], {}
+    sizeshape_col0 = next((s.col0 for s in steps if s.inst[-1] == "sizeshape"), None)
+    for k, s in enumerate(steps):
+        ch, red_z, metric = s.inst[0], s.inst[1], s.inst[-1]
+        role = LAUNCH  # (also what a family that runs after the join keeps)
+        if not s.family.after_join and (ch == "None" or not s.family.needs_pixels):
+            key = (metric, tuple(sorted(s.kw.items())))
             if metric == "feret" and sizeshape_col0 is not None:
                 # the two Feret diameters are columns of the sizeshape block (one hull kernel writes both): copy them
                 ss = feat.sizeshape_names()
-                for j, name in enumerate(feat.feret_names()):
-                    copies.append((col0 + j, sizeshape_col0 + ss.index(name), 1))
+                copies.extend((s.col0 + j, sizeshape_col0 + ss.index(name), 1) for j, name in enumerate(feat.feret_names()))
+                role = COPY
             elif key in done:
                 # e.g. "feret"/"zernike" listed under every channel: same labels, same numbers
-                copies.append((col0, done[key], ncols))
+                copies.append((s.col0, done[key], s.ncols))
+                role = COPY
             else:
-                with fan.next_stream():
-                    reg["launch"](eng, labels, table, None, 0, None, out, col0, kw)
-                done[key] = col0
-        else:
-            if cache is None:
-                raise Exception("pixels are required for this instruction")
-            plane, dt = cache.get(red_z)
-            if metric == "radial_zernikes" and hasattr(eng, "radial_zernikes_multi") and table.n_obj:
-                zern_groups.setdefault(red_z, []).append((ch, col0))  # channels of one plane block share a launch (below)
-                continue
-            with fan.next_stream():
-                reg["launch"](eng, labels, table, plane, dt, ch, out, col0, kw)
-    for red_z, members in zern_groups.items():
+                done[key] = s.col0
+        elif not s.family.after_join and metric == "radial_zernikes":
+            zernike_groups.setdefault(red_z, []).append((ch, s.col0))
+            role = GROUP
+        steps[k] = replace(s, role=role)
+    return Plan(blocks, n_cols, steps, copies=copies, zernike_groups=zernike_groups)
+
+
+def _plan_multi(blocks, n_cols, steps) -> Plan:
+    groups = {}  # (pair, red_z) -> [(metric, first column, thr, scale_max)]: every requested metric of that pair together
+    for s in steps:
+        (ch0, ch1), red_ch, red_z, metric = s.inst[0], s.inst[1], s.inst[2], s.inst[3]
+        if red_ch != "None":
+            raise NotImplementedError("channel-combining multi instructions (extract.py:227-235) are not built; "
+                                      "the builder only emits red_ch='None' (pipe_builder.py:33-43)")
+        # kwargs are per feature name, as the reference bakes them into one partial per name (loaders.py:71-77):
+        # manders_fold's thr must not leak into rwc.  The kernel takes one thr per launch, so metrics of a pair whose
+        # thresholds differ go to separate launches.
+        thr = float(s.kw.get("thr", 15.0)) if metric in ("manders_fold", "rwc") else None
+        scale_max = float(s.kw.get("scale_max", 255.0)) if metric == "costes" else None
+        groups.setdefault(((ch0, ch1), red_z), []).append((metric, s.col0, thr, scale_max))
+    prefetch, batches = [], {}
+    for (pair, red_z), entries in groups.items():
+        thrs = sorted({t for _, _, t, _ in entries if t is not None}) or [15.0]
+        scale_max = next((sm for _, _, _, sm in entries if sm is not None), 255.0)
+        for k, thr in enumerate(thrs):  # threshold-free metrics ride with the first threshold's launch
+            cols = {m: c for m, c, t, _ in entries if t == thr or (t is None and k == 0)}
+            prefetch.append((red_z, pair, "rwc" in cols))
+            # every pair that shares a z-reduction and its parameters goes into one launch (csrc/feat_coloc.hip, k_coloc_pairs)
+            batches.setdefault((red_z, thr, scale_max), []).append((pair, cols))
+    return Plan(blocks, n_cols, steps, prefetch=prefetch, batches=batches)
+
+
+def evaluate(eng, labels, table, planes, instructions, cp_measure_kwargs, multi=False):
+    """Run every instruction over every object; returns (matrix [n_obj, n_cols] on device, blocks)."""
+    p = plan(instructions, cp_measure_kwargs, multi)
+    out = eng.new_output(table.n_obj, p.n_cols)
+    cache = PlaneCache(eng, planes) if planes is not None else None
+    (_run_multi if multi else _run_mono)(eng, labels, table, cache, out, _FanOut(eng, table, out), p)
+    return out, p.blocks
+
+
+def _run_multi(eng, labels, table, cache, out, fan, p):
+    if cache is None:
+        raise Exception("pixels are required for colocalisation instructions")
+    for red_z, pair, ranks in p.prefetch:  # shared inputs first, on the main stream: z-reduction, rank planes
         plane, dt = cache.get(red_z)
-        with fan.next_stream():
-            eng.radial_zernikes_multi(labels, plane, dt, [c for c, _ in members], table, out, [c0 for _, c0 in members])
-    fan.join()
-    for col0, src, ncols in copies:
-        out[:, col0 : col0 + ncols] = out[:, src : src + ncols]
-    for inst, reg, kw, col0, ncols in after:
-        ch, red_z = inst[0], inst[1]
-        extra = {"cell_cache": cell_cache}
-        if reg.get("stack"):
-            if cache is None:
-                raise Exception("pixels are required for this instruction")
-            reg["launch"](eng, labels, table, cache.tensor, cache.dtype, ch, out, col0, kw, **extra)
-        elif ch == "None" or not reg["needs_pixels"]:
-            if ch != "None" and cache is not None:
-                cache.get(red_z)
-            reg["launch"](eng, labels, table, None, 0, None, out, col0, kw, **extra)
-        else:
-            if cache is None:
-                raise Exception("pixels are required for this instruction")
+        if ranks:
+            eng.rank_planes(labels, plane, dt, table, pair)
+    left = []  # what goes pair by pair: single pairs, and what coloc_pairs declines
+    for (red_z, thr, scale_max), pairs in p.batches.items():
+        plane, dt = cache.get(red_z)
+        if len(pairs) < 2 or not eng.coloc_pairs(labels, plane, dt, pairs, table, out, thr=thr, scale_max=scale_max):
+            left.extend((pair, plane, dt, cols, thr, scale_max) for pair, cols in pairs)
+    if left:
+        fan.fork()
+        for (ch0, ch1), plane, dt, cols, thr, scale_max in left:
+            with fan.next_stream():
+                eng.coloc(labels, plane, dt, ch0, ch1, table, out, cols, thr=thr, scale_max=scale_max)
+        fan.join()
+
+
+def _inputs(step, cache):  # -> (pixels, dtype code, channel) that the step's launcher is handed
+    ch, red_z = step.inst[0], step.inst[1]
+    if ch == "None" or not step.family.needs_pixels:
+        if ch != "None" and cache is not None:
+            cache.get(red_z)  # the reference would still reduce (and raise on a bad reducer)
+        return None, 0, None
+    if cache is None:
+        raise Exception("pixels are required for this instruction")
+    return (cache.tensor, cache.dtype, ch) if step.family.stack else (*cache.get(red_z), ch)
+
+
+def _run_mono(eng, labels, table, cache, out, fan, p):
+    # shared inputs first, on the main stream (the pixel-independent ones are cached on the object table)
+    for s in p.steps:
+        ch, red_z, metric = s.inst[0], s.inst[1], s.inst[-1]
+        if ch != "None" and s.family.needs_pixels and cache is not None and red_z in _RED:
+            cache.get(red_z)
+        if metric in ("zernike", "radial_zernikes") and table.n_obj:
+            eng.mec(labels, table)
+        if metric == "radial_distribution" and table.n_obj:
+            eng.radial_geometry(labels, table, s.kw.get("bin_count", 4), None if s.kw.get("scaled", True) else s.kw.get("maximum_radius", 100))
+    cells = _CellBlocks(eng, labels, table)
+    group = table.n_obj > 0  # without objects the Zernike channels are not grouped: each launches on its own
+    fan.fork()
+    for s in p.steps:
+        if s.family.after_join:
+            continue
+        plane, dt, ch = _inputs(s, cache)
+        if s.role == LAUNCH or (s.role == GROUP and not group):
+            with fan.next_stream():
+                s.family.launch(eng, labels, table, plane, dt, ch, out, s.col0, s.kw, cells)
+    if group:
+        for red_z, members in p.zernike_groups.items():
             plane, dt = cache.get(red_z)
-            reg["launch"](eng, labels, table, plane, dt, ch, out, col0, kw, **extra)
-    return out, blocks
+            with fan.next_stream():
+                eng.radial_zernikes_multi(labels, plane, dt, [c for c, _ in members], table, out, [c0 for _, c0 in members])
+    fan.join()
+    for col0, src, ncols in p.copies:
+        out[:, col0 : col0 + ncols] = out[:, src : src + ncols]
+    for s in p.steps:
+        if s.family.after_join:
+            s.family.launch(eng, labels, table, *_inputs(s, cache), out, s.col0, s.kw, cells)

@@ -115,7 +115,6 @@ def reduce_z(trap_image, fun, axis: int = 0):
     np.divide) with NumPy's result dtypes — uint16 input: uint16 / uint64 / float64; float32 input: float32 — and the
     reference's error for anything that is not a ufunc (distributors.py:20-24).  A 2-D image comes back as it is."""
     from aliby_amd import _lib
-    from aliby_amd.extraction.engine import _ptr, _stream_ptr
 
     if isinstance(fun, np.ufunc):
         op = _UFUNCS.get(fun.__name__)
@@ -130,13 +129,8 @@ def reduce_z(trap_image, fun, axis: int = 0):
         a = a.astype(np.uint16 if a.dtype in (np.uint8, np.bool_) else np.float32)
     moved = np.ascontiguousarray(np.moveaxis(a, axis, 0))  # [Z, ...]
     Z, rest = moved.shape[0], moved.shape[1:]
-    eng = FeatureEngine()
     dev = torch.from_numpy(moved).cuda()
     u16 = moved.dtype == np.uint16
     in_dt = _lib.U16 if u16 else _lib.F32
-    out_dt, t_dt = ((in_dt, dev.dtype) if op == 0 else (_lib.F32, torch.float32) if not u16
-                    else (_lib.U64, torch.uint64) if op == 1 else (_lib.F64, torch.float64))
-    out = torch.empty(rest, dtype=t_dt, device="cuda")
-    _lib.check(eng.lib.aliby_reduce_z(eng.ctx.handle, _ptr(dev), in_dt, 1, Z, int(np.prod(rest, dtype=np.int64)), op, _ptr(out), out_dt,
-                                      _stream_ptr()))
-    return out.cpu().numpy()
+    out_dt = in_dt if op == 0 else _lib.F32 if not u16 else _lib.U64 if op == 1 else _lib.F64
+    return FeatureEngine().reduce_z(dev.reshape(Z, 1, int(np.prod(rest, dtype=np.int64))), op, in_dt, out_dt).reshape(rest).cpu().numpy()

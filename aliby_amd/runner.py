@@ -432,11 +432,12 @@ class BatchRunner:
         # extractmulti_<obj> right behind extract_<obj> (the builder's order, pipe_builder.py:60-75) reads the same masks and
         # pixels: its launches (rank planes + one colocalisation launch for all pairs, ~3 ms alone on the device) go out FIRST,
         # on a stream of their own, and run beside the per-channel families instead of after them; the step itself then finds
-        # its result here.  Only LDS-resident object windows (the large-object variants share the context's scratch block).
+        # its result here.  Only LDS-resident object windows (ObjectTable.lds_resident: the large-object variants share the context's
+        # scratch block).
         steps = list(batch[0].pipeline["steps"])
         partner = "extractmulti_" + name[len("extract_"):] if name.startswith("extract_") else None
-        if (not multi and self._side_multi and self.measure is None and partner is not None and table.n_obj > 0
-                and table.max_h * table.max_w <= 4096 and steps.index(name) + 1 < len(steps) and steps[steps.index(name) + 1] == partner):
+        if (not multi and self._side_multi and self.measure is None and partner is not None and table.lds_resident
+                and steps.index(name) + 1 < len(steps) and steps[steps.index(name) + 1] == partner):
             if self._multi_stream is None:
                 self._multi_stream = torch.cuda.Stream()
             side, main = self._multi_stream, torch.cuda.current_stream()

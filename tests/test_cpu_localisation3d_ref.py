@@ -103,8 +103,8 @@ def test_metric_is_registered():
     from aliby_amd.extraction import functions
 
     reg = families.MONO["nuc_conv_3d"]
-    assert reg["names"]({}) is None and reg["needs_pixels"] and reg["cell"] and reg["stack"]
-    assert [m for m, r in families.MONO.items() if r.get("stack")] == ["nuc_conv_3d"]
+    assert reg.names({}) is None and reg.needs_pixels and reg.after_join and reg.stack
+    assert [m for m, r in families.MONO.items() if r.stack] == ["nuc_conv_3d"]
     assert callable(FeatureEngine.nuc_conv_3d) and callable(functions.nuc_conv_3d)
 
 

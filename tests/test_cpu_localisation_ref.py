@@ -85,7 +85,7 @@ def test_family_is_registered():
     from aliby_amd.extraction import functions
 
     reg = families.MONO["nuc_est_conv"]
-    assert reg["names"]({}) is None and reg["needs_pixels"] and reg["cell"]
+    assert reg.names({}) is None and reg.needs_pixels and reg.after_join
     assert callable(FeatureEngine.nuc_est_conv) and callable(functions.nuc_est_conv)
 
 
