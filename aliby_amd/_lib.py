@@ -153,6 +153,7 @@ _SIGNATURES = {
     "aliby_features_nuc_est_conv": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, C.c_double, C.c_double, C.c_double,
                                          _vp, _i, _i, _vp]),
     "aliby_features_nuc_conv_3d": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, C.c_double, C.c_double, _vp, _i, _i, _vp]),
+    "aliby_features_neighbors": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _i, _vp]),
     "aliby_features_cell": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "aliby_features_coloc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i,
                                   C.c_double, C.c_double, _vp, _vp, _vp]),

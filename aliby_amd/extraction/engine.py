@@ -560,6 +560,27 @@ class FeatureEngine:
         table._mec = mec
         return mec
 
+    def neighbors(self, labels, table: ObjectTable, out, col0, distance=None):
+        """Columns col0..col0+6 of out [n_obj, .]: the `neighbors` family (features.neighbors_names(distance);
+        aliby_features_neighbors) — CellProfiler's MeasureObjectNeighbors with the objects as their own neighbours: the number of
+        neighbours within `distance` pixels, the share of the outline in contact with them, the two closest objects by centre, and the
+        angle between them.  distance=None: adjacent objects (d = 1); else an integer in 1..64 (ValueError otherwise).  PARITY
+        UNPINNED, and the angle is atan2(|v1 x v2|, v1 . v2) where CellProfiler takes an arccos: the definition, and what is not built
+        ("Expand until adjacent", a second object set), are in include/aliby_hip.h.  Uses no context scratch."""
+        d = feat.neighbors_distance(distance)
+        F, Y, X = labels.shape
+        if table.n_obj == 0:
+            return 7
+        offsets_dev = getattr(table, "_offsets_dev", None)
+        if offsets_dev is None:
+            offsets_dev = table._offsets_dev = torch.from_numpy(np.ascontiguousarray(table.offsets, dtype=np.int32)).to(labels.device)
+        centres = torch.empty((table.n_obj, 2), dtype=torch.float64, device=labels.device)
+        with self.timed("neighbors"):
+            _lib.check(self.lib.aliby_features_neighbors(
+                self.ctx.handle, _ptr(labels), F, Y, X, _ptr(table.dev), table.n_obj, table.max_h, table.max_w, _ptr(offsets_dev),
+                int(np.diff(table.offsets).max()), d, _ptr(centres), _ptr(out), out.stride(0), col0, _stream_ptr()))
+        return 7
+
     def zernike(self, labels, planes, dtype, channel, table: ObjectTable, out, col0, weighted: bool):
         F, Y, X = labels.shape
         Cn = planes.shape[1] if planes is not None else 0

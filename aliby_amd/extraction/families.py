@@ -109,6 +109,11 @@ def _launch_feret(eng, labels, table, plane, dt, ch, out, col0, kw, cells):
     eng.feret(labels, table, out, col0)
 
 
+def _launch_neighbors(eng, labels, table, plane, dt, ch, out, col0, kw, cells):
+    # (`plan` has refused every keyword but `distance`: the "expand" method and a second object set are not built)
+    eng.neighbors(labels, table, out, col0, **kw)
+
+
 def _launch_zernike(eng, labels, table, plane, dt, ch, out, col0, kw, cells):
     eng.zernike(labels, None, 0, 0, table, out, col0, weighted=False)
 
@@ -175,6 +180,9 @@ MONO = {
     # extensions of this fork's registry: the reference reaches the two functions through its custom loader, not load_cellfuns_core
     "nuc_est_conv": Family(_scalar, _launch_nuc_est_conv, after_join=True),
     "nuc_conv_3d": Family(_scalar, _launch_nuc_conv_3d, after_join=True, stack=True),
+    # cp_measure's multi-mask measurement of that name (CellProfiler's MeasureObjectNeighbors), with the objects as their own
+    # neighbours; the reference's loader does not bind it.  Parity unpinned (features.neighbors_names)
+    "neighbors": Family(lambda kw: feat.neighbors_names(kw.get("distance")), _launch_neighbors, needs_pixels=False),
 }
 # cell.py metrics (loaders.py:19-25): scalar results, one column each
 for _m in ("area", "centroid_x", "centroid_y", "conical_volume", "eccentricity", "spherical_volume", "volume"):
@@ -234,10 +242,11 @@ class _FanOut:
             self.used.clear()
 
 
-# the functions the reference takes from cp_measure (get_core_measurements / get_correlation_measurements, loaders.py:71-77): only
-# their entries of cp_measure_kwargs are ever looked at there; an entry named after one of the in-repo functions is ignored
+# the cp_measure functions: those the reference takes from it (get_core_measurements / get_correlation_measurements,
+# loaders.py:71-77), and "neighbors", a cp_measure function the reference does not bind and this registry adds.  Only their entries
+# of cp_measure_kwargs are ever looked at; an entry named after one of the in-repo functions is ignored
 CP_MEASURE_NAMES = ("intensity", "sizeshape", "zernike", "feret", "texture", "radial_distribution", "radial_zernikes", "granularity",
-                    "pearson", "manders_fold", "rwc", "costes")
+                    "pearson", "manders_fold", "rwc", "costes", "neighbors")
 # per-feature keywords (cp_measure_kwargs / cp_measure_feature_kwargs of the builder) that the kernels implement
 BUILT_KWARGS = {
     "intensity": ("edge_measurements",),
@@ -247,6 +256,7 @@ BUILT_KWARGS = {
     "manders_fold": ("thr",),
     "rwc": ("thr",),
     "costes": ("scale_max",),
+    "neighbors": ("distance",),
 }
 
 LAUNCH, COPY, GROUP = "launch", "copy", "group"

@@ -10,6 +10,8 @@ identity 4 + 6*S + 5*I + 10*P = 632 quoted at examples/01:156-158 is reproduced 
 
 from __future__ import annotations
 
+import numbers
+
 INTENSITY_CORE = [
     "Intensity_IntegratedIntensity",
     "Intensity_MeanIntensity",
@@ -141,6 +143,31 @@ def radial_zernike_names() -> list[str]:
     return out
 
 
+NEIGHBORS_MAX_DISTANCE = 64  # bounds the per-pixel scan of csrc/feat_neighbors.hip; not a structural limit
+
+
+def neighbors_distance(distance=None) -> int:
+    """The pixel distance d of the `neighbors` family: None -> 1 (CellProfiler's "Adjacent"), else an integer in 1..64.  Anything
+    else is a ValueError.  Needs no device."""
+    if distance is None:
+        return 1
+    if isinstance(distance, bool) or not isinstance(distance, numbers.Integral) or not 1 <= int(distance) <= NEIGHBORS_MAX_DISTANCE:
+        raise ValueError(f"neighbors: distance must be None or an integer in 1..{NEIGHBORS_MAX_DISTANCE}, got {distance!r}")
+    return int(distance)
+
+
+def neighbors_names(distance=None) -> list[str]:
+    """Columns of the `neighbors` family (csrc/feat_neighbors.hip): CellProfiler's MeasureObjectNeighbors with the objects as their own
+    neighbours, which cp_measure carries among its multi-mask measurements.  The suffix is "Adjacent" for distance=None (d = 1),
+    else str(d).  PARITY UNPINNED: the definition (include/aliby_hip.h, tests/neighbors_ref.py) is recalled from CellProfiler 4 and
+    centrosome, neither of which can be run beside this package.  AngleBetweenNeighbors is atan2(|v1 x v2|, v1 . v2), not
+    CellProfiler's arccos of the normalised dot product: the same angle, well-conditioned near 0 and 180 degrees (deliberate).
+    Not built: "Expand until adjacent", neighbours from a second object set, distances above 64."""
+    s = "Adjacent" if distance is None else str(neighbors_distance(distance))
+    return [f"Neighbors_{n}_{s}" for n in ("NumberOfNeighbors", "PercentTouching", "FirstClosestObjectNumber", "FirstClosestDistance",
+                                           "SecondClosestObjectNumber", "SecondClosestDistance", "AngleBetweenNeighbors")]
+
+
 COLOC = {
     "pearson": ["Correlation_Pearson", "Correlation_Slope"],
     "manders_fold": ["Correlation_Manders_1", "Correlation_Manders_2"],
@@ -164,6 +191,8 @@ def family_names(family: str, **kw) -> list[str]:
         return radial_distribution_names(kw.get("bin_count", 4), kw.get("scaled", True))
     if family == "radial_zernikes":
         return radial_zernike_names()
+    if family == "neighbors":
+        return neighbors_names(kw.get("distance"))
     if family in COLOC:
         return list(COLOC[family])
     raise KeyError(family)

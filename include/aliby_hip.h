@@ -486,6 +486,30 @@ int aliby_features_nuc_est_conv(aliby_ctx* ctx, const uint16_t* labels, const vo
 int aliby_features_nuc_conv_3d(aliby_ctx* ctx, const uint16_t* labels, const void* stack, int dtype, int F, int C, int Z, int Y,
                                int X, int channel, const aliby_object* table_dev, int n_obj, int max_h, int max_w, int max_area,
                                double pixel_size, double z_spacing, double* out, int ld, int col0, void* stream);
+/* "neighbors": CellProfiler's MeasureObjectNeighbors with the objects as their own neighbours (among cp_measure's multi-mask
+ * measurements; not bound by the reference's loader).  PARITY UNPINNED: recalled from CellProfiler 4's measureobjectneighbors.py and
+ * centrosome's outline / strel_disk, neither of which can be run beside this library (tests/neighbors_ref.py restates it).
+ * Per tile [Y,X] (labels 1..n, 0 = background), object L, integer distance d in 1..64: S = the offsets with
+ * dy^2 + dx^2 <= d^2 (strel_disk(d)), T = those with dy^2 + dx^2 <= d^2 + d (strel_disk(d + 0.5)); offsets that leave the frame are
+ * dropped; the outline of L = its pixels on the frame's first / last row or column or with an 8-neighbour of another value.
+ * out[row * ld + col0 + k], k = 0..6:
+ *   0 NumberOfNeighbors: distinct labels not in {0, L} at q + o, q a pixel of L, o in S
+ *   1 PercentTouching: double(t) / double(p) * 100; p = outline pixels, t = those with a label not in {0, L} at q + o, o in T
+ *   2, 3 FirstClosestObjectNumber, FirstClosestDistance; 4, 5 SecondClosest...: centres (sum y / area, sum x / area) from exact
+ *     64-bit sums and one float64 division each; candidates = the other present labels of the tile, ranked by dy dy + dx dx in
+ *     float64, ties to the lower label; distance = sqrt(key).  No first candidate: 2-3 are 0; no second: 4-6 are 0.
+ *   6 AngleBetweenNeighbors: atan2(|v1 x v2|, v1 . v2) 180 / pi for the vectors from L's centre to the two centres, NaN when one
+ *     is zero (CellProfiler: arccos of the normalised dot product — the same angle, ill-conditioned near 0 and 180 degrees; the
+ *     departure is deliberate).
+ * A label of 1..n without pixels: NaN in all seven, never a neighbour or a candidate.  A label above its tile's table count (a
+ * wrong max_labels hint) is not counted.  Not built: "Expand until adjacent", neighbours from a second object set.
+ * offsets_dev [dev, F + 1]: the table's row offsets (row offsets[tile] + l - 1 is label l); max_count: the largest tile's rows;
+ * centres_dev [dev, n_obj x 2 float64]: workspace, holds the centres (y, x) afterwards.  Two launches on `stream`; ctx scratch is
+ * not used, so the call may run beside other launches of the context.  n_obj == 0 launches nothing.  distance outside 1..64 is
+ * ALIBY_ERR_INVALID (the cap bounds the per-pixel scan).  Kernels: csrc/feat_neighbors.hip. */
+int aliby_features_neighbors(aliby_ctx* ctx, const uint16_t* labels, int F, int Y, int X, const aliby_object* table_dev, int n_obj,
+                             int max_h, int max_w, const int32_t* offsets_dev, int max_count, int distance, double* centres_dev,
+                             double* out, int ld, int col0, void* stream);
 /* trap.imBackground / trap.background_max5 (src/extraction/core/functions/trap.py:6-43): per tile, over the pixels of
  * `channel` under NO mask (labels == 0): out[f*2] = their median (numpy.median), out[f*2+1] = the mean of the five largest
  * (of all of them when fewer); NaN for a tile without background. */
