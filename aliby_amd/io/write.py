@@ -7,8 +7,9 @@ Both files are encoded by libaliby_hip.so (csrc/host_writers.hip: `aliby_parquet
 formats, read back by pyarrow / numpy like the reference's — because the reference's two library calls are what a position
 costs once the kernels are fast: ~15 CPU-ms for a thousand-column parquet through pyarrow, ~5.5 ms for a label image through
 numpy + zlib, against ~2 ms of device time per FOV.  The native calls run with the interpreter lock released, so the
-position-batched runner's writer THREADS encode files side by side (no writer processes, no Arrow IPC hop).  Tables or arrays
-the native encoders do not cover (null values, nested / object dtypes) go through pyarrow / numpy as before.
+position-batched runner's writer THREADS encode files side by side; that is the runner's only write path (the pyarrow writer
+processes it had before these encoders are gone).  Tables or arrays the native encoders do not cover (null values,
+nested / object dtypes) go through pyarrow / numpy as before, on the same threads; `ALIBY_NATIVE_WRITERS=0` sends everything there.
 """
 
 from __future__ import annotations

@@ -488,18 +488,22 @@ def test_dense_layout_cache_keeps_renamed_columns_apart():
 def test_run_positions_keeps_shared_steps_between_calls_and_leaves_the_collector_as_it_found_it(tmp_path):
     """Host-only stand-in steps (no GPU): a step object without per-position state is built once for the process, not once per
     call or per position (aliby_amd/runner.py _SharedSteps); `release_pinned()` drops it; while a call runs the cycle collector is
-    off (the launch thread collects by hand), afterwards it is back on, nothing stays frozen, and a failing step restores it too."""
+    off (the launch thread collects by hand), afterwards it is back on, nothing stays frozen, and a failing step restores it too.
+    The same for the thread switch interval: at most the default `switch_interval=2e-4` inside the steps, the
+    caller's value after a call that returned and after one that raised.  `writer_processes=` is no argument any more."""
     import gc
+    import sys
 
     from aliby_amd import runner
 
-    made, seen = [], []
+    made, seen, intervals = [], [], []
 
     class FakeTiler:
         def __init__(self, k):
             self.k = k
 
         def run_tp(self, tp):
+            intervals.append(sys.getswitchinterval())
             return {"drift": {}, "pixels": np.full((1, 1, 1, 4, 4), self.k, np.uint16)}
 
     def init(step_name, parameters, other=None):
@@ -509,6 +513,7 @@ def test_run_positions_keeps_shared_steps_between_calls_and_leaves_the_collector
 
         def embed(pixels):
             seen.append(gc.isenabled())
+            intervals.append(sys.getswitchinterval())
             if parameters.get("fail"):
                 raise RuntimeError("boom")
             return np.arange(6, dtype=np.float64).reshape(2, 3) + float(pixels.flat[0])
@@ -519,21 +524,34 @@ def test_run_positions_keeps_shared_steps_between_calls_and_leaves_the_collector
         return [{"steps": {"tile": {"k": i}, "nahual_embed_x": {"address": "ipc://unused", **extra}},
                  "passed_data": {"nahual_embed_x": [("pixels", "tile")]}} for i in range(n)]
 
-    runner.release_pinned()
-    assert gc.isenabled() and gc.get_freeze_count() == 0
-    for call in range(2):
-        got = runner.run_positions(pipes(3), [f"c{call}_{i}" for i in range(3)], tmp_path / "out", init_step_fn=init, batch_size=2)
-        assert [g[0].num_rows for g in got] == [2, 2, 2]
+    before = sys.getswitchinterval()
+    sys.setswitchinterval(0.0123)  # (a value nothing else sets: what every call below must put back)
+    mine = sys.getswitchinterval()
+    try:
+        assert abs(mine - 0.0123) < 1e-6
+        runner.release_pinned()
         assert gc.isenabled() and gc.get_freeze_count() == 0
-    assert made.count("nahual_embed_x") == 1 and made.count("tile") == 6  # the embedder: once; tilers hold an image each
-    assert seen and not any(seen)  # the steps ran with the collector off
-    runner.release_pinned()
-    runner.run_positions(pipes(1), ["again"], tmp_path / "out", init_step_fn=init, batch_size=2)
-    assert made.count("nahual_embed_x") == 2
-    with pytest.raises(RuntimeError, match="boom"):
-        runner.run_positions(pipes(1, fail=True), ["bad"], tmp_path / "out", init_step_fn=init, batch_size=2)
-    assert gc.isenabled() and gc.get_freeze_count() == 0
-    runner.release_pinned()
+        for call in range(2):
+            got = runner.run_positions(pipes(3), [f"c{call}_{i}" for i in range(3)], tmp_path / "out", init_step_fn=init, batch_size=2)
+            assert [g[0].num_rows for g in got] == [2, 2, 2]
+            assert gc.isenabled() and gc.get_freeze_count() == 0
+            assert sys.getswitchinterval() == mine
+        assert made.count("nahual_embed_x") == 1 and made.count("tile") == 6  # the embedder: once; tilers hold an image each
+        assert seen and not any(seen)  # the steps ran with the collector off
+        assert len(intervals) == 12 and max(intervals) <= 2e-4  # ... and with the lowered switch interval, tilers and embedder
+        runner.release_pinned()
+        runner.run_positions(pipes(1), ["again"], tmp_path / "out", init_step_fn=init, batch_size=2)
+        assert made.count("nahual_embed_x") == 2
+        with pytest.raises(RuntimeError, match="boom"):
+            runner.run_positions(pipes(1, fail=True), ["bad"], tmp_path / "out", init_step_fn=init, batch_size=2)
+        assert gc.isenabled() and gc.get_freeze_count() == 0
+        assert sys.getswitchinterval() == mine
+        assert max(intervals) <= 2e-4  # (the failing step included)
+        with pytest.raises(TypeError):  # the writer processes are gone, and so is their argument: not accepted and ignored
+            runner.run_positions(pipes(1), ["procs"], tmp_path / "out", init_step_fn=init, batch_size=2, writer_processes=2)
+        runner.release_pinned()
+    finally:
+        sys.setswitchinterval(before)
 
 
 def test_usable_cores_divides_the_share_among_local_ranks(monkeypatch):
