@@ -24,6 +24,7 @@ U8W = 4  # uint8 / bool pixels in uint16 storage: texture's grey level is the va
 U64, F64 = 2, 3  # aliby_reduce_z output dtypes (NumPy's result types for uint16 add / divide)
 RED_MAX, RED_ADD, RED_DIV = 0, 1, 2
 CROP_CLIP, CROP_8BIT, CROP_STD = 1, 2, 4  # stages of aliby_crop_tiles_u16 (ALIBY_CROP_*)
+CONV_ALTERNATE, CONV_ASCENDING, CONV_DESCENDING = 0, 1, 2  # modes of aliby_nn_conv_order (ALIBY_CONV_*)
 
 
 class AlibyHipError(RuntimeError):
@@ -104,6 +105,7 @@ _SIGNATURES = {
     "aliby_debug_conv_deep_trace": (_i, [_vp, _vp]),
     "aliby_track_stitch": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp]),
     "aliby_debug_conv_trace": (_i, [_vp, _vp]),
+    "aliby_nn_conv_order": (_i, [_vp, _i]),
     "aliby_features_coloc_pairs": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _i, C.c_double, C.c_double, _vp, _vp, _vp]),
     "aliby_trap_gauss1d": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp]),
     "aliby_trap_warp": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _i, C.c_double, _vp]),

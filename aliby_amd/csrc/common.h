@@ -18,6 +18,9 @@ struct aliby_ctx {
   // small device scratch owned by the context (per-tile counters etc.)
   void* scratch;
   size_t scratch_bytes;
+  // tile order of the persistent convolution launches (conv_launch.h): ALIBY_CONV_* mode, and the launches counted so far
+  int conv_order;
+  unsigned conv_launches;
 };
 
 void aliby_set_error(const char* fmt, ...);

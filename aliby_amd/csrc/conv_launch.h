@@ -1,12 +1,12 @@
 // conv_launch.h — the launch front end of the network's persistent convolution kernels (nn_conv.hip: k_conv3x3, k_conv3x3_dma,
 // k_conv_pair32, k_conv_first_pair; nn_conv_deep.hip: k_conv3x3_deep, k_conv3x3_deep16, k_conv3x3_deep_ls, k_conv3x3_kloop64).
-// Host side only; the counterpart of the per-object feature kernels is object_launch.h.
+// The counterpart of the per-object feature kernels is object_launch.h.
 //
-// Every such kernel takes one argument struct with `ntiles` and loops over the tiles itself: the grid is 8 XCDs x `nslots`
-// workgroups, never more than the tiles need.  A site states how many workgroups an XCD holds (the kernel's resident workgroups
-// per CU x 32 CUs) as `cap`; the caps stay with the sites, they follow from each kernel's LDS and registers.  The working sets
-// are dynamic LDS, so hipFuncAttributeMaxDynamicSharedMemorySize is raised once per process and kernel, at the kernel's own
-// first launch.
+// Every such kernel takes one argument struct with `ntiles` and `order` and loops over the tiles itself (tile_walk, the one
+// device function here): the grid is 8 XCDs x `nslots` workgroups, never more than the tiles need.  A site states how many
+// workgroups an XCD holds (the kernel's resident workgroups per CU x 32 CUs) as `cap`; the caps stay with the sites, they follow
+// from each kernel's LDS and registers.  The working sets are dynamic LDS, so hipFuncAttributeMaxDynamicSharedMemorySize is
+// raised once per process and kernel, at the kernel's own first launch.
 #pragma once
 #include "common.h"
 #include <limits.h>
@@ -34,9 +34,38 @@ int conv_tiles(Args& a) {
   return ALIBY_OK;
 }
 
+// The tiles of this workgroup.  Workgroup b lives on XCD b % 8 and is slot b / 8 of it; XCD x owns the contiguous eighth
+// [x * per_xcd, (x + 1) * per_xcd) of the tile list, so that neighbouring tiles (shared halos) meet in the same L2, and its
+// slots share the eighth with a stride of nslots.  order 0 walks the eighth upwards; order 1 walks the mirror image, from its
+// last tile down: the same tiles per XCD and the same count per slot, so the only difference is WHEN a tile runs.  A launch
+// that walks against its producer starts on the part of the tensor that the producer wrote last, which is the part the
+// Infinity Cache still holds.  The k-th tile of the workgroup, k < count, is first + k * step.
+struct TileWalk {
+  int first, step, count;
+};
+__device__ __forceinline__ TileWalk tile_walk(int ntiles, int order) {
+  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nslots = gridDim.x >> 3;
+  const int per_xcd = (ntiles + 7) >> 3;
+  const int lo = xcd * per_xcd, hi = min(ntiles, lo + per_xcd);
+  TileWalk w;
+  w.count = lo + slot < hi ? (hi - lo - slot + nslots - 1) / nslots : 0;
+  w.first = order ? hi - 1 - slot : lo + slot;
+  w.step = order ? -nslots : nslots;
+  return w;
+}
+
+// The direction of the next persistent launch on `ctx`: pinned, or (the default) opposite to the previous one.  A launch with
+// phase stamps switched on (the debug-trace entry points) walks upwards: the stamps are those of workgroup 0's first tiles.
+inline int next_order(aliby_ctx* ctx, bool traced) {
+  if (traced || ctx->conv_order == ALIBY_CONV_ASCENDING) return 0;
+  if (ctx->conv_order == ALIBY_CONV_DESCENDING) return 1;
+  return (int)(ctx->conv_launches++ & 1u);
+}
+
 // One persistent launch: 8 XCDs x at most `cap` slots of THREADS threads with `lds_bytes` of dynamic LDS.
 template <auto Kernel, int THREADS, class Args>
-int launch(Args& a, int lds_bytes, int cap, hipStream_t stream) {
+int launch(aliby_ctx* ctx, Args& a, int lds_bytes, int cap, hipStream_t stream) {
+  a.order = next_order(ctx, a.trace != nullptr);
   static bool attr_done = false;
   if (!attr_done) {
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));

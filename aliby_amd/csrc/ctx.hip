@@ -69,6 +69,8 @@ int aliby_ctx_create(int device, aliby_ctx** out) {
   snprintf(c->name, sizeof(c->name), "%s (%s)", p.name, p.gcnArchName);
   c->scratch = nullptr;
   c->scratch_bytes = 0;
+  c->conv_order = ALIBY_CONV_ALTERNATE;
+  c->conv_launches = 0;
   *out = c;
   return ALIBY_OK;
 }
@@ -90,6 +92,14 @@ int aliby_device_info(aliby_ctx* ctx, int* cu_count, int* lds_bytes, size_t* hbm
     strncpy(name, ctx->name, (size_t)name_len - 1);
     name[name_len - 1] = 0;
   }
+  return ALIBY_OK;
+}
+
+int aliby_nn_conv_order(aliby_ctx* ctx, int mode) {
+  ARG_CHECK(ctx != nullptr, "ctx is NULL");
+  ARG_CHECK(mode == ALIBY_CONV_ALTERNATE || mode == ALIBY_CONV_ASCENDING || mode == ALIBY_CONV_DESCENDING, "conv_order: unknown mode");
+  ctx->conv_order = mode;
+  ctx->conv_launches = 0;  // alternate: the next launch walks upwards
   return ALIBY_OK;
 }
 

@@ -81,7 +81,8 @@ struct ConvArgs {
   int N, H, W;
   int G;               // packed launches: images laid side by side per tile row (G * W = 224); 1 otherwise
   int tiles_x, tiles_y, ntiles;
-  const uint4* pin;    // fused 1x1 projection: raw input [N, H, W, pcs*8] bf16 (NULL: none)
+  int order;           // direction of the tile walk (tile_walk), set by launch<>
+  const uint4* pin;   // fused 1x1 projection: raw input [N, H, W, pcs*8] bf16 (NULL: none)
   const uint4* pwpk;   // its packed weights ([cout block][k-step][lane]); the projection's bias rides in `bias`
   int pcs;             // 16-byte units per projection input pixel
   // fused output head (the network's last unit): y[n, o, p] = hbias[o] + sum_c hw[o, c] * bf16(relu(hscale[c] * OUT[n, p, c] + hshift[c]))
@@ -349,14 +350,11 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(ConvArgs a) {
   for (int k = 0; k < 4; ++k) sc[k] = f32x2_t{a.scale[pl * 8 + 2 * k], a.scale[pl * 8 + 2 * k + 1]};
 
   const int IH = UP ? a.H >> 1 : a.H, IW = UP ? a.W >> 1 : a.W;
-  // XCD-aware persistent schedule: workgroup b lives on XCD b%8; each XCD walks one contiguous eighth of
-  // the tile list so that neighbouring tiles (shared halos) meet in the same L2.
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nslots = gridDim.x >> 3;
-  const int per_xcd = (a.ntiles + 7) >> 3;
-  const int t_end = min(a.ntiles, (xcd + 1) * per_xcd);
+  // XCD-aware persistent schedule (tile_walk): each XCD walks one contiguous eighth of the tile list
+  const TileWalk walk = tile_walk(a.ntiles, a.order);
 
-  int stamp_tile = 0;
-  for (int tile = xcd * per_xcd + slot; tile < t_end; tile += nslots, ++stamp_tile) {
+  for (int stamp_tile = 0; stamp_tile < walk.count; ++stamp_tile) {
+    const int tile = walk.first + stamp_tile * walk.step;
     CONV_STAMP(0);
     const int tx = tile % a.tiles_x, tyn = tile / a.tiles_x;
     const int ty = tyn % a.tiles_y, n = tyn / a.tiles_y;
@@ -589,9 +587,7 @@ __global__ __launch_bounds__(256, (DmaCfg<CIN, COUT, UP, PACK>::WAVES_PER_SIMD))
   for (int k = 0; k < 4; ++k) sc[k] = f32x2_t{a.scale[pl * 8 + 2 * k], a.scale[pl * 8 + 2 * k + 1]};
 
   const int IH = UP ? a.H >> 1 : a.H, IW = UP ? a.W >> 1 : a.W;
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nslots = gridDim.x >> 3;
-  const int per_xcd = (a.ntiles + 7) >> 3;
-  const int t_end = min(a.ntiles, (xcd + 1) * per_xcd);
+  const TileWalk walk = tile_walk(a.ntiles, a.order);
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
 
   auto issue_dma = [&](int tile) {
@@ -627,9 +623,9 @@ __global__ __launch_bounds__(256, (DmaCfg<CIN, COUT, UP, PACK>::WAVES_PER_SIMD))
     }
   };
 
-  int tile = xcd * per_xcd + slot, stamp_tile = 0;
-  if (tile < t_end) issue_dma(tile);
-  for (; tile < t_end; tile += nslots, ++stamp_tile) {
+  if (walk.count > 0) issue_dma(walk.first);
+  for (int stamp_tile = 0; stamp_tile < walk.count; ++stamp_tile) {
+    const int tile = walk.first + stamp_tile * walk.step;
     CONV_STAMP(0);
     const int tx = tile % a.tiles_x, tyn = tile / a.tiles_x;
     const int ty = tyn % a.tiles_y, n = tyn / a.tiles_y;
@@ -715,7 +711,7 @@ __global__ __launch_bounds__(256, (DmaCfg<CIN, COUT, UP, PACK>::WAVES_PER_SIMD))
       f32x16_t acc[R];
       conv_seed<R>(acc, b4, rr, a.res != nullptr);
       __builtin_amdgcn_sched_barrier(0);
-      if (pass == 0 && tile + nslots < t_end) issue_dma(tile + nslots);  // R is free: everyone passed the barrier after the prologue
+      if (pass == 0 && stamp_tile + 1 < walk.count) issue_dma(tile + walk.step);  // R is free: everyone passed the barrier after the prologue
       if (pass + 1 < PASSES && a.res) load_res(pass + 1);                   // consumed after this pass's MFMA loop
       __builtin_amdgcn_sched_barrier(0);
       if (pass == 0) CONV_STAMP(4);
@@ -772,10 +768,8 @@ __global__ __launch_bounds__(512, 1) void k_conv_pair32(ConvArgs a) {
   const int px = lane & 31, hh = lane >> 5;
   const int c0 = hh * 16;
 
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nslots = gridDim.x >> 3;
-  const int per_xcd = (a.ntiles + 7) >> 3;
-  const int t_begin = xcd * per_xcd + slot, t_end = min(a.ntiles, (xcd + 1) * per_xcd);
-  const int my_tiles = t_begin < t_end ? (t_end - t_begin + nslots - 1) / nslots : 0;  // the same for both roles
+  const TileWalk walk = tile_walk(a.ntiles, a.order);
+  const int my_tiles = walk.count;  // the same for both roles
 
   if (!consumer) {
     // =============================================================== producers: window -> unit A -> B's planes
@@ -809,9 +803,9 @@ __global__ __launch_bounds__(512, 1) void k_conv_pair32(ConvArgs a) {
         v[u] = inN[(unsigned)((cy * a.W + cx) * a.cs + pl)];
       }
     };
-    if (my_tiles > 0) request(t_begin);
+    if (my_tiles > 0) request(walk.first);
     for (int it = 0; it < my_tiles; ++it) {
-      const int tile = t_begin + it * nslots;
+      const int tile = walk.first + it * walk.step;
       const int tx = tile % a.tiles_x, tyn = tile / a.tiles_x;
       const int ty = tyn % a.tiles_y, n = tyn / a.tiles_y;
       const int y0 = ty * TH, x0 = tx * TWO;
@@ -833,7 +827,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_pair32(ConvArgs a) {
         ldsIn[pl * PLANE_IN + pix0 + u * PIX_PER_IT] = o;
       }
       __syncthreads();  // S1: the window is complete
-      if (it + 1 < my_tiles) request(tile + nslots);
+      if (it + 1 < my_tiles) request(tile + walk.step);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int pass = 0; pass < PASSES; ++pass) {
@@ -905,7 +899,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_pair32(ConvArgs a) {
     // (measured and NOT adopted, round 3: requesting a pass's residual rows one pass ahead instead of right before they seed the
     // accumulators — 8.03 against 7.75 ms per step for the down-block pair: the consumers are not what the launch waits for)
     for (int it = 0; it < my_tiles; ++it) {
-      const int tile = t_begin + it * nslots;
+      const int tile = walk.first + it * walk.step;
       const int tx = tile % a.tiles_x, tyn = tile / a.tiles_x;
       const int ty = tyn % a.tiles_y, n = tyn / a.tiles_y;
       const int y0 = ty * TH, x0 = tx * TWO;
@@ -995,10 +989,8 @@ __global__ __launch_bounds__(512, 1) void k_conv_first_pair(ConvArgs a) {
   const int px = lane & 31, hh = lane >> 5;
   const int c0 = hh * 16;
 
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nslots = gridDim.x >> 3;
-  const int per_xcd = (a.ntiles + 7) >> 3;
-  const int t_begin = xcd * per_xcd + slot, t_end = min(a.ntiles, (xcd + 1) * per_xcd);
-  const int my_tiles = t_begin < t_end ? (t_end - t_begin + nslots - 1) / nslots : 0;
+  const TileWalk walk = tile_walk(a.ntiles, a.order);
+  const int my_tiles = walk.count;  // the same for both roles
   const size_t plane = (size_t)a.H * a.W;
 
   if (!consumer) {
@@ -1061,10 +1053,10 @@ __global__ __launch_bounds__(512, 1) void k_conv_first_pair(ConvArgs a) {
         v[u] = a.fx[((size_t)n * a.fcin + cc) * plane + (size_t)cy * a.W + cx];
       }
     };
-    if (my_tiles > 0) request(t_begin);
+    if (my_tiles > 0) request(walk.first);
     unsigned short* const P0h = reinterpret_cast<unsigned short*>(P0);
     for (int it = 0; it < my_tiles; ++it) {
-      const int tile = t_begin + it * nslots;
+      const int tile = walk.first + it * walk.step;
       const int tx = tile % a.tiles_x, tyn = tile / a.tiles_x;
       const int ty = tyn % a.tiles_y;
       const int y0 = ty * TH, x0 = tx * TWO;
@@ -1091,7 +1083,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_first_pair(ConvArgs a) {
         for (int i = tid; i < cfg::RAWP_WORDS; i += 256) rawPh[2 * i + 1] = 0;
       }
       __syncthreads();  // S1: the window is complete
-      if (it + 1 < my_tiles) request(tile + nslots);
+      if (it + 1 < my_tiles) request(tile + walk.step);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int pass = 0; pass < PASSES; ++pass) {
@@ -1148,7 +1140,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_first_pair(ConvArgs a) {
     __syncthreads();  // the producers' first tile: its S1 ...
     __syncthreads();  // ... and S2
     for (int it = 0; it < my_tiles; ++it) {
-      const int tile = t_begin + it * nslots;
+      const int tile = walk.first + it * walk.step;
       const int tx = tile % a.tiles_x, tyn = tile / a.tiles_x;
       const int ty = tyn % a.tiles_y, n = tyn / a.tiles_y;
       const int y0 = ty * TH, x0 = tx * TWO;
@@ -1233,28 +1225,28 @@ __global__ void k_pack_conv3x3(const float* w, int cout, int cin_src, int cin, i
 unsigned long long* g_conv_trace = nullptr;
 
 template <int CIN, int COUT, bool UP, bool PACK = false>
-int launch_conv_dma(ConvArgs& a, hipStream_t stream) {
+int launch_conv_dma(aliby_ctx* ctx, ConvArgs& a, hipStream_t stream) {
   using cfg = DmaCfg<CIN, COUT, UP, PACK>;
   if (const int rc = conv_tiles<cfg, PACK>(a)) return rc;
   const int cap = 32 * cfg::WAVES_PER_SIMD;  // workgroups per XCD: 32 CUs x (1 or 2) resident workgroups
-  return launch<k_conv3x3_dma<CIN, COUT, UP, PACK>, 256>(a, cfg::LDS_BYTES, cap, stream);
+  return launch<k_conv3x3_dma<CIN, COUT, UP, PACK>, 256>(ctx, a, cfg::LDS_BYTES, cap, stream);
 }
 
 template <int CIN, int COUT, bool UP, bool TALL, bool PACK = false>
-int launch_conv_reg(ConvArgs& a, hipStream_t stream) {
+int launch_conv_reg(aliby_ctx* ctx, ConvArgs& a, hipStream_t stream) {
   using cfg = ConvCfg<CIN, COUT, TALL, PACK>;
   if (const int rc = conv_tiles<cfg, PACK>(a)) return rc;
   constexpr int PKV = PACK ? 0 : (!UP && CIN == 32 && COUT == 32) ? 1 : ((!UP && CIN == 64 && COUT == 64) ? 2 : 0);  // projection input: 16 / 32 channels
   constexpr int P_BYTES = PKV ? 2 * PKV * ((cfg::TH * cfg::TW) | 1) * 16 : 0;
   constexpr int CAP = 64;  // 2 workgroups per CU, 32 CUs per XCD
   if (!a.pin && !a.hout) {
-    if (!a.pool) return launch<k_conv3x3<CIN, COUT, UP, false, 0, TALL, PACK>, 256>(a, cfg::LDS_BYTES, CAP, stream);
-    return launch<k_conv3x3<CIN, COUT, UP, true, 0, TALL, PACK>, 256>(a, cfg::LDS_BYTES, CAP, stream);
+    if (!a.pool) return launch<k_conv3x3<CIN, COUT, UP, false, 0, TALL, PACK>, 256>(ctx, a, cfg::LDS_BYTES, CAP, stream);
+    return launch<k_conv3x3<CIN, COUT, UP, true, 0, TALL, PACK>, 256>(ctx, a, cfg::LDS_BYTES, CAP, stream);
   }
   if (a.pin) {
     if constexpr (PKV > 0) {
       ARG_CHECK(!a.pool && a.pcs >= 1 && a.pcs <= 2 * PKV, "conv3x3: fused projection: unsupported input width");
-      return launch<k_conv3x3<CIN, COUT, UP, false, PKV, TALL>, 256>(a, cfg::LDS_BYTES + P_BYTES, CAP, stream);
+      return launch<k_conv3x3<CIN, COUT, UP, false, PKV, TALL>, 256>(ctx, a, cfg::LDS_BYTES + P_BYTES, CAP, stream);
     } else {
       aliby_set_error("conv3x3: fused projection is built for (32,32) and (64,64) without upsampling only");
       return ALIBY_ERR_UNSUPPORTED;
@@ -1262,7 +1254,7 @@ int launch_conv_reg(ConvArgs& a, hipStream_t stream) {
   }
   if constexpr (COUT == 32 && CIN == 32 && !UP && !PACK) {  // a.hout: the output head in the epilogue
     ARG_CHECK(!a.pool && a.hO >= 1 && a.hO <= 3, "conv3x3: fused head: 1..3 output channels, no pooled output");
-    return launch<k_conv3x3<CIN, COUT, UP, false, 0, TALL, false, true>, 256>(a, cfg::LDS_BYTES, CAP, stream);
+    return launch<k_conv3x3<CIN, COUT, UP, false, 0, TALL, false, true>, 256>(ctx, a, cfg::LDS_BYTES, CAP, stream);
   } else {
     aliby_set_error("conv3x3: the fused output head is built for the (32,32) unit only");
     return ALIBY_ERR_UNSUPPORTED;
@@ -1270,7 +1262,7 @@ int launch_conv_reg(ConvArgs& a, hipStream_t stream) {
 }
 
 template <int CIN, int COUT, bool UP>
-int launch_conv(ConvArgs& a, hipStream_t stream) {
+int launch_conv(aliby_ctx* ctx, ConvArgs& a, hipStream_t stream) {
   // measured per shape (scripts/bench_conv.py): the DMA pipeline wins where the raw window is small (upsampled
   // input); ALIBY_CONV_DMA=0/1 forces one variant for A/B runs
   static const bool use_dma = env_int("ALIBY_CONV_DMA", UP) != 0;
@@ -1278,9 +1270,9 @@ int launch_conv(ConvArgs& a, hipStream_t stream) {
     if constexpr (UP && COUT >= 64) {
       static const int pack_up = env_int("ALIBY_CONV_PACK", 7);  // bit 2: upsampled shapes
       if ((pack_up & 4) && (a.W == 56 || a.W == 112) && a.N % (224 / a.W) == 0 && a.H % DmaCfg<CIN, COUT, UP, true>::TH == 0)
-        return launch_conv_dma<CIN, COUT, UP, true>(a, stream);
+        return launch_conv_dma<CIN, COUT, UP, true>(ctx, a, stream);
     }
-    return launch_conv_dma<CIN, COUT, UP>(a, stream);
+    return launch_conv_dma<CIN, COUT, UP>(ctx, a, stream);
   }
   // a taller tile where it divides the image and fits two workgroups per CU (measured: 64->128 at 56 rows +10 %,
   // 32->32 at 224 rows +3..7 %: the fixed per-tile latency chain is amortised over twice the pixels)
@@ -1292,13 +1284,13 @@ int launch_conv(ConvArgs& a, hipStream_t stream) {
         a.H % ConvCfg<CIN, COUT, false, true>::TH == 0) {
       if constexpr (CIN == 64 && COUT == 64) {
         static const bool tall64 = env_int("ALIBY_CONV_TALL64", 1) != 0;
-        if (tall64 && a.H % ConvCfg<CIN, COUT, true, true>::TH == 0) return launch_conv_reg<CIN, COUT, UP, true, true>(a, stream);
+        if (tall64 && a.H % ConvCfg<CIN, COUT, true, true>::TH == 0) return launch_conv_reg<CIN, COUT, UP, true, true>(ctx, a, stream);
       }
-      return launch_conv_reg<CIN, COUT, UP, false, true>(a, stream);
+      return launch_conv_reg<CIN, COUT, UP, false, true>(ctx, a, stream);
     }
   }
-  if (CAN_TALL && !a.pin && a.H % (2 * ConvCfg<CIN, COUT, false>::TH) == 0) return launch_conv_reg<CIN, COUT, UP, CAN_TALL>(a, stream);
-  return launch_conv_reg<CIN, COUT, UP, false>(a, stream);
+  if (CAN_TALL && !a.pin && a.H % (2 * ConvCfg<CIN, COUT, false>::TH) == 0) return launch_conv_reg<CIN, COUT, UP, CAN_TALL>(ctx, a, stream);
+  return launch_conv_reg<CIN, COUT, UP, false>(ctx, a, stream);
 }
 
 }  // namespace
@@ -1350,12 +1342,12 @@ static int conv3x3_entry(aliby_ctx* ctx, const void* in, const void* wpk, void* 
   a.cs = in_channels / 8;
   a.coff = in_channel0 / 8;
   a.N = N; a.H = H; a.W = W;
-  if (CIN == 32 && COUT == 32 && !in_up) return launch_conv<32, 32, false>(a, stream);
-  if (CIN == 64 && COUT == 32 && in_up) return launch_conv<64, 32, true>(a, stream);
-  if (CIN == 64 && COUT == 64 && !in_up) return launch_conv<64, 64, false>(a, stream);
-  if (CIN == 64 && COUT == 64 && in_up) return launch_conv<64, 64, true>(a, stream);
-  if (CIN == 64 && COUT == 128) return in_up ? launch_conv<64, 128, true>(a, stream) : launch_conv<64, 128, false>(a, stream);
-  if (CIN == 32 && COUT == 64 && !in_up) return launch_conv<32, 64, false>(a, stream);
+  if (CIN == 32 && COUT == 32 && !in_up) return launch_conv<32, 32, false>(ctx, a, stream);
+  if (CIN == 64 && COUT == 32 && in_up) return launch_conv<64, 32, true>(ctx, a, stream);
+  if (CIN == 64 && COUT == 64 && !in_up) return launch_conv<64, 64, false>(ctx, a, stream);
+  if (CIN == 64 && COUT == 64 && in_up) return launch_conv<64, 64, true>(ctx, a, stream);
+  if (CIN == 64 && COUT == 128) return in_up ? launch_conv<64, 128, true>(ctx, a, stream) : launch_conv<64, 128, false>(ctx, a, stream);
+  if (CIN == 32 && COUT == 64 && !in_up) return launch_conv<32, 64, false>(ctx, a, stream);
   aliby_set_error("conv3x3: unsupported (CIN=%d, COUT=%d, upsample=%d) combination", CIN, COUT, in_up);
   return ALIBY_ERR_UNSUPPORTED;
 }
@@ -1424,9 +1416,9 @@ extern "C" int aliby_nn_conv3x3_pair_bf16(aliby_ctx* ctx, const void* in, const 
   ARG_CHECK(nt < INT_MAX, "conv3x3_pair: too many tiles");
   a.ntiles = (int)nt;
   constexpr int CAP = 32;  // one 8-wave workgroup per CU, 32 CUs per XCD
-  if (!head_out && !pool_out) return launch<k_conv_pair32<false, false>, 512>(a, PairCfg::LDS_BYTES, CAP, stream);
-  if (!head_out) return launch<k_conv_pair32<true, false>, 512>(a, PairCfg::LDS_BYTES, CAP, stream);
-  return launch<k_conv_pair32<false, true>, 512>(a, PairCfg::LDS_BYTES, CAP, stream);
+  if (!head_out && !pool_out) return launch<k_conv_pair32<false, false>, 512>(ctx, a, PairCfg::LDS_BYTES, CAP, stream);
+  if (!head_out) return launch<k_conv_pair32<true, false>, 512>(ctx, a, PairCfg::LDS_BYTES, CAP, stream);
+  return launch<k_conv_pair32<false, true>, 512>(ctx, a, PairCfg::LDS_BYTES, CAP, stream);
 }
 
 extern "C" int aliby_nn_first_pair_bf16(aliby_ctx* ctx, const float* tiles, int N, int Cin, int H, int W, const float* scale0,
@@ -1448,7 +1440,7 @@ extern "C" int aliby_nn_first_pair_bf16(aliby_ctx* ctx, const float* tiles, int 
   const long long nt = (long long)N * a.tiles_x * a.tiles_y;
   ARG_CHECK(nt < INT_MAX, "first_pair: too many tiles");
   a.ntiles = (int)nt;
-  return launch<k_conv_first_pair, 512>(a, FirstPairCfg::LDS_BYTES, 32, stream);  // one 8-wave workgroup per CU, 32 CUs per XCD
+  return launch<k_conv_first_pair, 512>(ctx, a, FirstPairCfg::LDS_BYTES, 32, stream);  // one 8-wave workgroup per CU, 32 CUs per XCD
 }
 
 extern "C" int aliby_nn_out_head_bf16(aliby_ctx* ctx, const void* x, const float* scale, const float* shift, const float* w,

@@ -78,6 +78,7 @@ struct DeepArgs {
   int LW, HP;          // W + 2, H + 1
   int q_begin, q_end;  // flat output positions [q_begin, q_end) of the tall image
   int nruns, nhalf, ntiles;
+  int order;           // direction of the tile walk (tile_walk), set by launch<>
   int stagger;         // the second workgroup of every CU starts this many x 64 x 64 cycles late (see the kernel)
   unsigned long long* trace;  // diagnostics: shader-clock stamps of workgroup 0's first tiles (NULL in production)
 };
@@ -221,14 +222,12 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep(DeepArgs a) {
   const int cs = CIN / 8;
   int* const goff = reinterpret_cast<int*>(lds + 8 * DC_PLANE) + tid;  // goff[it * 256]: this thread's input offsets of the tile
 
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nslots = gridDim.x >> 3;
-  const int per_xcd = (a.ntiles + 7) >> 3;
-  const int t_end = min(a.ntiles, (xcd + 1) * per_xcd);
-  if (slot >= (nslots >> 1))
+  const TileWalk walk = tile_walk(a.ntiles, a.order);
+  if ((blockIdx.x >> 3) >= (gridDim.x >> 4))  // the upper half of every XCD's slots
     for (int i = 0; i < a.stagger; ++i) __builtin_amdgcn_s_sleep(64);
 
-  int stamp_tile = 0;
-  for (int tile = xcd * per_xcd + slot; tile < t_end; tile += nslots, ++stamp_tile) {
+  for (int stamp_tile = 0; stamp_tile < walk.count; ++stamp_tile) {
+    const int tile = walk.first + stamp_tile * walk.step;
     DC_STAMP(0);
     const int half = tile % a.nhalf, run = tile / a.nhalf;
     const int q0 = a.q_begin + run * DC_RUN;
@@ -365,11 +364,10 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_kloop64(DeepArgs a) {
   const int cs = CIN / 8;
   int* const goff = reinterpret_cast<int*>(lds + 4 * U_PLANE) + tid;  // goff[it * 256]: this thread's input offsets of the tile
 
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nslots = gridDim.x >> 3;
-  const int per_xcd = (a.ntiles + 7) >> 3;
-  const int t_end = min(a.ntiles, (xcd + 1) * per_xcd);
+  const TileWalk walk = tile_walk(a.ntiles, a.order);
 
-  for (int tile = xcd * per_xcd + slot; tile < t_end; tile += nslots) {
+  for (int ti = 0; ti < walk.count; ++ti) {
+    const int tile = walk.first + ti * walk.step;
     const int q0 = a.q_begin + tile * U_RUN;
     const int p_first = q0 - LW - 1;  // flat index of window position 0
     unsigned inside = 0, later = 0;
@@ -493,11 +491,10 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep16(DeepArgs a) {
   const int cs = CIN / 8;
   int* const goff = reinterpret_cast<int*>(lds + 8 * DC_PLANE16) + tid;
 
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nslots = gridDim.x >> 3;
-  const int per_xcd = (a.ntiles + 7) >> 3;
-  const int t_end = min(a.ntiles, (xcd + 1) * per_xcd);
+  const TileWalk walk = tile_walk(a.ntiles, a.order);
 
-  for (int tile = xcd * per_xcd + slot; tile < t_end; tile += nslots) {
+  for (int ti = 0; ti < walk.count; ++ti) {
+    const int tile = walk.first + ti * walk.step;
     const int half = tile % a.nhalf, run = tile / a.nhalf;
     const int q0 = a.q_begin + run * DC_RUN;
     const int p_first = q0 - LW - 1;
@@ -693,10 +690,8 @@ __global__ __launch_bounds__(256 + DL_LT, 1) void k_conv3x3_deep_ls(DeepArgs a) 
   const int LW = a.LW, HP = a.HP;
   const int WIN = DC_RUN + 2 * LW + 2;
   const int cs = CIN / 8;
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nslots = gridDim.x >> 3;
-  const int per_xcd = (a.ntiles + 7) >> 3;
-  const int t_begin = xcd * per_xcd + slot, t_end = min(a.ntiles, (xcd + 1) * per_xcd);
-  const int my_tiles = t_begin < t_end ? (t_end - t_begin + nslots - 1) / nslots : 0;
+  const TileWalk walk = tile_walk(a.ntiles, a.order);
+  const int my_tiles = walk.count;
   const int G = my_tiles * S;  // slices this workgroup goes through: one barrier each, for every wave
 
   if (wave >= 4) {
@@ -746,11 +741,11 @@ __global__ __launch_bounds__(256 + DL_LT, 1) void k_conv3x3_deep_ls(DeepArgs a) 
     };
     // slice g of the workgroup = (tile g / S, slice g % S); prepared one barrier ahead of its MFMAs
     if (G > 0) {
-      tile_offsets(t_begin);
+      tile_offsets(walk.first);
       issue_dma(0);
       activate(0, planes0);
       if (G > 1) {
-        if (S == 1) tile_offsets(t_begin + nslots);
+        if (S == 1) tile_offsets(walk.first + walk.step);
         issue_dma(1 % S);
       }
     }
@@ -761,7 +756,7 @@ __global__ __launch_bounds__(256 + DL_LT, 1) void k_conv3x3_deep_ls(DeepArgs a) 
         activate(s1, planes0 + ((g + 1) & 1) * 8 * DC_PLANE);  // (its offsets / masks are the ones its DMA was issued with)
         if (g + 2 < G) {
           const int s2 = (g + 2) % S;
-          if (s2 == 0) tile_offsets(t_begin + ((g + 2) / S) * nslots);
+          if (s2 == 0) tile_offsets(walk.first + ((g + 2) / S) * walk.step);
           issue_dma(s2);
         }
       }
@@ -775,7 +770,7 @@ __global__ __launch_bounds__(256 + DL_LT, 1) void k_conv3x3_deep_ls(DeepArgs a) 
   const int row_off[3] = {0, LW, 2 * LW};
   int g = 0;
   for (int ti = 0; ti < my_tiles; ++ti) {
-    const int tile = t_begin + ti * nslots;
+    const int tile = walk.first + ti * walk.step;
     const int half = tile % a.nhalf, run = tile / a.nhalf;
     const int q0 = a.q_begin + run * DC_RUN;
     const int c0 = half * 128 + cb * 32 + hh * 16;
@@ -914,9 +909,9 @@ static int deep_entry(aliby_ctx* ctx, const void* in, const void* wpk, void* out
   auto go = [&](auto cin, auto up) {
     constexpr int C = decltype(cin)::value;
     constexpr bool U = decltype(up)::value;
-    if (m16) return launch<k_conv3x3_deep16<C, U>, 256>(a, DC16_LDS_BYTES, 64, stream);
-    if (ls) return launch<k_conv3x3_deep_ls<C, U>, 256 + DL_LT>(a, DL_LDS_BYTES, 32, stream);
-    return launch<k_conv3x3_deep<C, U>, 256>(a, DC_LDS_BYTES, slots, stream);
+    if (m16) return launch<k_conv3x3_deep16<C, U>, 256>(ctx, a, DC16_LDS_BYTES, 64, stream);
+    if (ls) return launch<k_conv3x3_deep_ls<C, U>, 256 + DL_LT>(ctx, a, DL_LDS_BYTES, 32, stream);
+    return launch<k_conv3x3_deep<C, U>, 256>(ctx, a, DC_LDS_BYTES, slots, stream);
   };
   auto by_up = [&](auto cin) { return in_up ? go(cin, std::true_type{}) : go(cin, std::false_type{}); };
   if (CIN == 64) return by_up(std::integral_constant<int, 64>{});
@@ -976,7 +971,7 @@ extern "C" int aliby_nn_conv3x3_kloop64_bf16(aliby_ctx* ctx, const void* in, con
   DeepArgs a;
   if (const int rc = deep_args(a, ctx, in, wpk, out, scale, shift, shift_per_sample, bias, res, res_up, N, H, W, CIN, COUT, U_RUN, 1))
     return rc;
-  return launch<k_conv3x3_kloop64<128, true>, 256>(a, U_LDS_BYTES, 64, stream);  // 2 workgroups per CU, 32 CUs per XCD
+  return launch<k_conv3x3_kloop64<128, true>, 256>(ctx, a, U_LDS_BYTES, 64, stream);  // 2 workgroups per CU, 32 CUs per XCD
 }
 
 extern "C" int aliby_nn_conv3x3_kloop_limits(int limits[4]) {

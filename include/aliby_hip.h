@@ -274,6 +274,13 @@ int aliby_nn_maxpool2_bf16(aliby_ctx* ctx, const void* in, void* out, int N, int
  * (uint64: 0 tile start, 1 loads issued, 2 after barrier, 3 prologue done, 4 after barrier, 5 MFMA done,
  * 6 stores issued).  NULL switches it off (the default). */
 int aliby_debug_conv_trace(aliby_ctx* ctx, void* stamps_dev);
+/* Tile order of the persistent convolution launches (every aliby_nn_conv3x3* / _pair / aliby_nn_first_pair entry) on `ctx`.  Each
+ * XCD walks its eighth of a launch's tiles upwards (ALIBY_CONV_ASCENDING), from its end downwards (ALIBY_CONV_DESCENDING), or
+ * (ALIBY_CONV_ALTERNATE, a new context's mode) in the direction opposite to the context's previous launch, so that a launch
+ * starts on what its producer wrote last and the Infinity Cache still holds.  Setting a mode restarts the alternation at
+ * ascending.  The order changes when a tile is computed, never its bits; launches with phase stamps on walk upwards. */
+enum { ALIBY_CONV_ALTERNATE = 0, ALIBY_CONV_ASCENDING = 1, ALIBY_CONV_DESCENDING = 2 };
+int aliby_nn_conv_order(aliby_ctx* ctx, int mode);
 /* The same unit (segment/dispatch.py:208-215) with the residual block's 1x1 projection fused in (cellpose `resdown`: x = proj(x_in) + conv1(conv0(x_in))):
  *   OUT = conv3x3( relu(scale*IN + shift) ) + bias + proj_w . PROJ_IN[n,y,x,:]
  * PROJ_IN is the block's RAW input [N,H,W,proj_channels] bf16 (no activation; the projection's BatchNorm is folded into
