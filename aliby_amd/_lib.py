@@ -169,6 +169,7 @@ _SIGNATURES = {
                                     C.c_double, C.c_double, _vp]),
     "aliby_texture3d_lds_voxels": (_i, []),
     "aliby_features_texture3d": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _i, _vp]),
+    "aliby_features_neighbors3d": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _vp]),
     "aliby_parquet_write": (_i, [C.c_char_p, _vp, _i, _vp, _i, _vp, _vp, _i]),
     "aliby_npz_write": (_i, [C.c_char_p, _vp, _i, _i]),
     "aliby_host_codecs": (_i, [C.POINTER(_i), C.POINTER(_i)]),

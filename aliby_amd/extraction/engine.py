@@ -503,6 +503,29 @@ class FeatureEngine:
                 F, Cn, Z, Y, X, channel, _ptr(offsets), scale, gray_levels, _ptr(out), out.stride(0), 0, _stream_ptr()))
         return out
 
+    def neighbors3d(self, volume: torch.Tensor, counts, distance=None) -> torch.Tensor:
+        """Volume labels uint16 [F,Z,Y,X] (1..counts[f] per stack) -> float64 [sum counts, 7] (features.neighbors3d_names(distance);
+        aliby_features_neighbors3d): the `neighbors` family on volumes — the number of objects within `distance` voxels, the share of
+        the plane-by-plane outline in contact with them, the two closest objects of the stack by centre, and the angle between them.
+        Rows in (stack, label) order.  distance=None: adjacent objects (d = 1); else an integer in 1..16 (ValueError otherwise; the cap
+        bounds the per-voxel scan, it is not a structural limit).  A label of 1..counts[f] without voxels gets a row of NaN; values
+        above counts[f] touch but are neither counted nor measured.  Voxel spacing is not used.  PARITY UNPINNED, and the angle is
+        atan2(|v1 x v2|, v1 . v2) where CellProfiler takes an arccos: the definition, and what is not built ("Expand until adjacent", a
+        second object set, physical-unit balls), are in include/aliby_hip.h.  The object table is built in the context's scratch: a
+        main-stream call.  Bitwise independent of run and batch."""
+        d = feat.neighbors3d_distance(distance)
+        F, Z, Y, X = self._volume_labels("neighbors3d", volume)
+        offsets = self._volume_offsets("neighbors3d", F, counts)
+        rows = int(offsets[-1])
+        out = self.new_output(rows, 7)
+        if rows == 0:
+            return out  # stacks without any object: an empty block (the C entry refuses a NULL output)
+        centres = torch.empty((rows, 3), dtype=torch.float64, device=volume.device)
+        with self.timed("neighbors3d"):
+            _lib.check(self.lib.aliby_features_neighbors3d(self.ctx.handle, _ptr(volume.contiguous()), F, Z, Y, X, _ptr(offsets), d, _ptr(centres),
+                                                           _ptr(out), out.stride(0), 0, _stream_ptr()))
+        return out
+
     def relabel_sequential(self, labels: torch.Tensor) -> np.ndarray:
         F, Y, X = labels.shape
         n = np.zeros(F, np.int32)

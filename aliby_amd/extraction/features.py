@@ -245,3 +245,28 @@ def texture3d_names(scale: int = 3, gray_levels: int = 256) -> list[str]:
     named as the 2-D `texture_names` names its 4 (mahotas' (13, 13) result on a 3-D array).  Which direction a block index stands
     for is the kernel's table (the header of feat_texture3d.hip); that order and parity with cp_measure are unpinned."""
     return [f"{h}_{scale}_{d:02d}_{gray_levels}" for d in range(13) for h in HARALICK]
+
+
+NEIGHBORS3D_MAX_DISTANCE = 16  # bounds the per-voxel scan of csrc/feat_neighbors3d.hip (about 19 k offsets at 16); not a structural limit
+
+
+def neighbors3d_distance(distance=None) -> int:
+    """The voxel distance d of `FeatureEngine.neighbors3d`: None -> 1 (CellProfiler's "Adjacent"), else an integer in 1..16.  Anything
+    else is a ValueError.  Needs no device."""
+    if distance is None:
+        return 1
+    if isinstance(distance, bool) or not isinstance(distance, numbers.Integral) or not 1 <= int(distance) <= NEIGHBORS3D_MAX_DISTANCE:
+        raise ValueError(f"neighbors3d: distance must be None or an integer in 1..{NEIGHBORS3D_MAX_DISTANCE}, got {distance!r}")
+    return int(distance)
+
+
+def neighbors3d_names(distance=None) -> list[str]:
+    """Columns of `FeatureEngine.neighbors3d` (csrc/feat_neighbors3d.hip): the seven of `neighbors_names`, on volume labels.  The
+    suffix is "Adjacent" for distance=None (d = 1), else str(d).  PARITY UNPINNED: the definition (include/aliby_hip.h,
+    tests/neighbors3d_ref.py) is recalled from CellProfiler 4 and centrosome, neither of which can be run beside this package.
+    AngleBetweenNeighbors is atan2(|v1 x v2|, v1 . v2), not CellProfiler's arccos of the normalised dot product: the same angle,
+    well-conditioned near 0 and 180 degrees (deliberate).  Not built: "Expand until adjacent", neighbours from a second object set,
+    physical-unit (anisotropic) balls, distances above 16."""
+    s = "Adjacent" if distance is None else str(neighbors3d_distance(distance))
+    return [f"Neighbors_{n}_{s}" for n in ("NumberOfNeighbors", "PercentTouching", "FirstClosestObjectNumber", "FirstClosestDistance",
+                                           "SecondClosestObjectNumber", "SecondClosestDistance", "AngleBetweenNeighbors")]

@@ -676,6 +676,41 @@ int aliby_texture3d_lds_voxels(void);
 int aliby_features_texture3d(aliby_ctx* ctx, const uint16_t* labels, const void* pixels, int dtype, int F, int C, int Z, int Y, int X,
                              int channel, const int32_t* offsets_host, int scale, int gray_levels, double* out, int ld, int col0,
                              void* stream);
+/* "neighbors3d": the `neighbors` family (aliby_features_neighbors: CellProfiler's MeasureObjectNeighbors with the objects as their
+ * own neighbours) on the same labelled stacks.  PARITY UNPINNED: recalled from CellProfiler 4's measureobjectneighbors.py and
+ * centrosome's outline / strel_disk, neither of which can be run beside this library (tests/neighbors3d_ref.py restates it).
+ * Per stack [Z,Y,X] (labels 1..n, 0 = background), object L, integer distance d in 1..16: S = the offsets with
+ * dz^2 + dy^2 + dx^2 <= d^2 (skimage.morphology.ball(d); the 6-neighbour cross for d = 1), T = those with
+ * dz^2 + dy^2 + dx^2 <= d^2 + d (the integer-offset form of radius d + 0.5; the 18-neighbourhood for d = 1); offsets that leave the
+ * volume are dropped (no wrap, no padding value).  The outline of L is taken plane by plane, as CellProfiler outlines a volume: its
+ * voxels on the first / last row or column of their plane or with one of the 8 in-plane neighbours of another value (0 included);
+ * the first and last planes are no borders, and the voxels above and below do not make an outline voxel.
+ * out[row * ld + col0 + k], k = 0..6, row = offsets_host[f] + L - 1:
+ *   0 NumberOfNeighbors: distinct labels v not in {0, L}, v <= n, at q + o, q a voxel of L, o in S
+ *   1 PercentTouching: double(t) / double(p) * 100; p = outline voxels, t = those with a non-zero value other than L at q + o, o in
+ *     T (a value above n counts here, as in 2-D)
+ *   2, 3 FirstClosestObjectNumber, FirstClosestDistance; 4, 5 SecondClosest...: centres (sum z, sum y, sum x) / count from exact
+ *     64-bit sums and one float64 division each; candidates = the other present labels of the stack, ranked by
+ *     (dz dz + dy dy) + dx dx in float64 (every operation rounded on its own), ties to the lower label; distance = sqrt(key).  No
+ *     first candidate: 2-3 are 0; no second: 4-6 are 0.
+ *   6 AngleBetweenNeighbors: atan2(|v1 x v2|, v1 . v2) 180 / pi with the 3-D cross product, for the vectors from L's centre to the
+ *     two centres, NaN when one is zero (the deliberate departure from CellProfiler's arccos, as in 2-D).
+ * A label of 1..n without voxels: NaN in all seven, never a neighbour or a candidate.  Labels above n are not measured and not
+ * counted in column 0.  Voxel spacing is not used.  On a stack of one plane every column is aliby_features_neighbors'.
+ * Not built: "Expand until adjacent", neighbours from a second object set, physical-unit (anisotropic) balls.
+ * Worked example, a stack [4, 6, 8] (z, y, x) at d = 1: A = 1 on z 0..1, y 1..2, x 1..2; B = 2 on z 0..1, y 1..2, x 3..4 (a face
+ * shared with A); C = 3 on z 2..3, y 3..4, x 3..4 (it meets B along one edge, across planes: offset (1, 1, 0), in T, not in S).
+ *   NumberOfNeighbors 1, 1, 0; PercentTouching 50, 62.5, 25 (every voxel is an outline voxel: 8 each; A's four at x = 2 reach B;
+ *   B's four at x = 3 reach A, and of its two at (z 1, y 2), which reach C, (x 4) is a fifth; C's two at (z 2, y 3) reach B).
+ *   Centres A (0.5, 1.5, 1.5), B (0.5, 1.5, 3.5), C (2.5, 3.5, 3.5): A -> 2 at 2, 3 at sqrt(12); B -> 1 at 2, 3 at sqrt(8);
+ *   C -> 2 at sqrt(8), 1 at sqrt(12); angles atan2(sqrt(32), 4), 90 and atan2(sqrt(32), 8) degrees.
+ * centres_dev [dev, offsets_host[F] x 3 float64]: workspace, holds the centres (z, y, x) afterwards.  The object table is built in
+ * the context's scratch, so this is a main-stream call: one in flight per context (the scratch rule, csrc/object_launch.h); it
+ * waits for `stream` before it returns.  offsets_host[F] == 0 launches nothing.  distance outside 1..16 is ALIBY_ERR_INVALID (the
+ * cap bounds the per-voxel scan: a ball of radius 16.5 is about 19 k offsets; it is not a structural limit).  Results are bitwise
+ * independent of the run, of the other stacks of the call and of the batch.  Kernels: csrc/feat_neighbors3d.hip. */
+int aliby_features_neighbors3d(aliby_ctx* ctx, const uint16_t* labels, int F, int Z, int Y, int X, const int32_t* offsets_host,
+                               int distance, double* centres_dev, double* out, int ld, int col0, void* stream);
 
 /* ---- a17: the step API's files, encoded natively (host code, no GPU work) ------------------ */
 /* profiles/<name>.parquet — pyarrow.parquet.write_table(profiles, path, compression="zstd")
