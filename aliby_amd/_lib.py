@@ -164,6 +164,8 @@ _SIGNATURES = {
     "aliby_features_sizeshape3d": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
     "aliby_surface3d_table": (_i, [_vp, _vp]),
     "aliby_features_surface3d": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
+    "aliby_intensity3d_detail_lds_voxels": (_i, []),
+    "aliby_features_intensity3d_detail": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp]),
     "aliby_coloc3d_lds_voxels": (_i, []),
     "aliby_features_coloc3d": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i,
                                     C.c_double, C.c_double, _vp]),

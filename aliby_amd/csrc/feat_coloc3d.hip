@@ -8,9 +8,9 @@
 // shared with feat_texture3d.hip.
 //   1. k_volume_table: voxel count and bounding box per (stack, label), one read of the labels.
 //   2. k_coloc3d: one workgroup of 256 lanes per (object, pair).  The object's voxels of both channels are gathered from its
-//      bounding box in raster order (z, y, x) by order-preserving compaction into two float lists, then each list is copied,
-//      sorted (bitonic) and reduced to its distinct values in place: the dense rank of a value is its index among them (binary
-//      search), so no rank is ever stored, in LDS or in HBM.  16 bytes per voxel: lists up to C3_LDS_VOXELS live in LDS (128 KiB),
+//      bounding box in raster order (z, y, x) by order-preserving compaction (volume_gather, volume_table.h) into two float lists,
+//      then each list is copied, sorted (bitonic) and reduced to its distinct values in place: the dense rank of a value is its index
+//      among them (binary search), so no rank is ever stored, in LDS or in HBM.  16 bytes per voxel: lists up to C3_LDS_VOXELS live in LDS (128 KiB),
 //      longer ones in global scratch (template parameter GLOBAL, same code).
 // Reproducibility: the workgroup size is fixed and the lane of a voxel, the sort and every reduction tree depend on the object's
 // own voxel list only, never on the other objects of the launch, the batch or which of the two forms ran: results are bitwise
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(C3_BLOCK) void k_coloc3d(C3Args a) {
   float* sv = fv + cap;
   float* d1 = sv + cap;
   float* d2 = d1 + cap;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int tid = threadIdx.x;
   const int ch0 = a.pairs[2 * blockIdx.y], ch1 = a.pairs[2 * blockIdx.y + 1];
   const size_t vol = (size_t)a.v.Z * a.v.Y * a.v.X;
 
@@ -112,41 +112,12 @@ __global__ __launch_bounds__(C3_BLOCK) void k_coloc3d(C3Args a) {
     const T* p0 = reinterpret_cast<const T*>(a.pixels) + ((size_t)f * a.C + ch0) * vol;
     const T* p1 = reinterpret_cast<const T*>(a.pixels) + ((size_t)f * a.C + ch1) * vol;
     const VolumeBox box = volume_box(a.v.bmin, a.v.bmax, row);
-    const unsigned nbox = box.nbox;
 
-    // ---- gather (raster order): C3_PER_LANE consecutive voxels of the box per lane and round -----------------------------
+    // ---- gather (raster order): C3_PER_LANE consecutive voxels of the box per lane and round (volume_gather) -------------
     __syncthreads();  // the previous object's lists are done with
-    int base = 0;
-    for (unsigned i0 = 0; i0 < nbox; i0 += C3_BLOCK * C3_PER_LANE) {
-      size_t idx[C3_PER_LANE];
-      unsigned in = 0;
-#pragma unroll
-      for (int k = 0; k < C3_PER_LANE; ++k) {
-        const unsigned i = i0 + (unsigned)tid * C3_PER_LANE + k;
-        idx[k] = 0;
-        if (i < nbox) {
-          idx[k] = box.index(i, a.v.Y, a.v.X);
-          if (lab[idx[k]] == L) in |= 1u << k;
-        }
-      }
-      const int c = __popc(in);
-      int incl = c;  // inclusive scan of the lanes' counts inside the wave
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(incl, o, 64); if (lane >= o) incl += v; }
-      __syncthreads();
-      if (lane == 63) wsum[wid] = incl;
-      __syncthreads();
-      int off = 0, tot = 0;
-      for (int i = 0; i < C3_BLOCK / 64; ++i) { const int s = wsum[i]; if (i < wid) off += s; tot += s; }
-      int pos = base + off + incl - c;
-      base += tot;
-#pragma unroll
-      for (int k = 0; k < C3_PER_LANE; ++k) {
-        if (!(in & (1u << k))) continue;
-        if (pos < cap) { fv[pos] = px_load<T>(p0, idx[k]); sv[pos] = px_load<T>(p1, idx[k]); }  // (pos < count <= cap: a guard, not a path)
-        ++pos;
-      }
-    }
+    const int base = volume_gather<C3_BLOCK, C3_PER_LANE>(lab, L, box, a.v.Y, a.v.X, wsum, [&](int pos, unsigned, size_t idx) {
+      if (pos < cap) { fv[pos] = px_load<T>(p0, idx); sv[pos] = px_load<T>(p1, idx); }  // (pos < count <= cap: a guard, not a path)
+    });
     __syncthreads();
     const int N = min(base, cap);
 

@@ -1,4 +1,5 @@
-// volume_table.h — the front end of the per-object kernels on volume labels [F, Z, Y, X] (feat_coloc3d.hip, feat_texture3d.hip):
+// volume_table.h — the front end of the per-object kernels on volume labels [F, Z, Y, X] (feat_coloc3d.hip, feat_texture3d.hip,
+// feat_intensity3d_detail.hip; feat_neighbors3d.hip takes the table and the plan):
 // the object table (k_volume_table: voxel count and bounding box per (stack, label), one read of the labels), the host's plan
 // around it (volume_plan), the arguments and the prologue every such kernel opens with, and the launch of a <dtype, GLOBAL> kernel.
 // (The index decode of k_volume_table and the entries' shape check are volume_pass.h, shared with the whole-stack kernels.)
@@ -93,6 +94,48 @@ __device__ __forceinline__ VolumeBox volume_box(const unsigned* bmin, const unsi
   b.d = bmax[(size_t)row * 3] - b.z0 + 1; b.h = bmax[(size_t)row * 3 + 1] - b.y0 + 1; b.w = bmax[(size_t)row * 3 + 2] - b.x0 + 1;
   b.nbox = b.d * b.h * b.w;
   return b;
+}
+
+// The gather of the kernels that keep an object's voxel LIST (feat_coloc3d.hip, feat_intensity3d_detail.hip): the voxels of label L
+// inside its box in raster order (z, y, x), by order-preserving compaction, PER_LANE consecutive voxels of the box per lane and round.
+// visit(pos, i, idx) once per voxel of the object: pos = its rank in the list, i = its index in the box, idx = its index in the
+// stack.  Returns the number of voxels to every lane.  All BLOCK lanes call it; wsum = LDS int[BLOCK / 64]; a barrier
+// lies before the first visit, none after the last.  The lane of a voxel depends on the object's own box only.
+template <int BLOCK, int PER_LANE, class Visit>
+__device__ __forceinline__ int volume_gather(const uint16_t* lab, uint16_t L, const VolumeBox& box, int Y, int X, int* wsum, Visit visit) {
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  int base = 0;
+  for (unsigned i0 = 0; i0 < box.nbox; i0 += BLOCK * PER_LANE) {
+    size_t idx[PER_LANE];
+    unsigned in = 0;
+#pragma unroll
+    for (int k = 0; k < PER_LANE; ++k) {
+      const unsigned i = i0 + (unsigned)tid * PER_LANE + k;
+      idx[k] = 0;
+      if (i < box.nbox) {
+        idx[k] = box.index(i, Y, X);
+        if (lab[idx[k]] == L) in |= 1u << k;
+      }
+    }
+    const int c = __popc(in);
+    int incl = c;  // inclusive scan of the lanes' counts inside the wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(incl, o, 64); if (lane >= o) incl += v; }
+    __syncthreads();
+    if (lane == 63) wsum[wid] = incl;
+    __syncthreads();
+    int off = 0, tot = 0;
+    for (int i = 0; i < BLOCK / 64; ++i) { const int s = wsum[i]; if (i < wid) off += s; tot += s; }
+    int pos = base + off + incl - c;
+    base += tot;
+#pragma unroll
+    for (int k = 0; k < PER_LANE; ++k) {
+      if (!(in & (1u << k))) continue;
+      visit(pos, i0 + (unsigned)tid * PER_LANE + k, idx[k]);
+      ++pos;
+    }
+  }
+  return base;
 }
 
 struct VolumePlan {

@@ -393,6 +393,38 @@ class FeatureEngine:
                                                            _stream_ptr()))
         return out
 
+    @property
+    def intensity3d_detail_lds_voxels(self) -> int:
+        """Largest object, in voxels, that `intensity3d_detail` measures from LDS; larger ones go through global scratch (same results)."""
+        return int(self.lib.aliby_intensity3d_detail_lds_voxels())
+
+    def intensity3d_detail(self, volume: torch.Tensor, pixels: torch.Tensor, channel: int, counts, edge_measurements: bool = True) -> torch.Tensor:
+        """Volume labels uint16 [F,Z,Y,X] (1..counts[f] per stack), pixels uint16 or float32 [F,C,Z,Y,X] -> float64 [sum counts, 13]
+        (8 with edge_measurements=False; features.intensity3d_detail_names(edge_measurements); aliby_features_intensity3d_detail): the
+        columns of the 2-D `intensity` family that `intensity3d` lacks, over each object's voxels in raster order (z, y, x) — the five
+        edge statistics (edge voxel: one of the six face neighbours inside the volume carries another value), MassDisplacement, the
+        quartiles, median and MAD (CellProfiler's interpolation rule, float64), and the position of the maximum (ties to the last
+        voxel in raster order).  torch.cat([intensity3d(...), intensity3d_detail(...)], 1) is the whole 2-D column set plus Volume and
+        Location_Center_*.  Rows in (stack, label) order.  A label of 1..counts[f] without voxels gets a row of NaN (the edge columns
+        too, where the 2-D family writes 0); an object with voxels but no edge voxel gets 0 in the edge columns; labels above counts[f]
+        are not measured, but count as another value next to an object.  NaN pixels give unspecified results.  Objects above
+        `intensity3d_detail_lds_voxels` voxels are measured in the context's scratch, where the object table is built too: a
+        main-stream call, one in flight per context (the scratch rule, csrc/object_launch.h).  Bitwise independent of run and batch."""
+        F, Cn, Z, Y, X, offsets = self._volume_inputs("intensity3d_detail", volume, pixels, counts)
+        if isinstance(channel, bool) or not isinstance(channel, (int, np.integer)):
+            raise TypeError(f"channel must be an integer, got {channel!r}")
+        names = feat.intensity3d_detail_names(edge_measurements)  # (refuses a flag that is not a bool)
+        if not 0 <= int(channel) < Cn:
+            raise ValueError(f"channel {int(channel)} out of range for {Cn} channels")
+        out = self.new_output(int(offsets[-1]), len(names))
+        if int(offsets[-1]) == 0:
+            return out  # stacks without any object: an empty block
+        with self.timed("intensity3d_detail"):
+            _lib.check(self.lib.aliby_features_intensity3d_detail(
+                self.ctx.handle, _ptr(volume.contiguous()), _ptr(pixels.contiguous()), _lib.U16 if pixels.dtype == torch.uint16 else _lib.F32,
+                F, Cn, Z, Y, X, int(channel), _ptr(offsets), int(edge_measurements), _ptr(out), out.stride(0), 0, _stream_ptr()))
+        return out
+
     @staticmethod
     def _spacing3d(spacing) -> np.ndarray:
         sp = np.ascontiguousarray(np.asarray(spacing, np.float64).reshape(3))

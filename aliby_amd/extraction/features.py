@@ -206,6 +206,18 @@ def intensity3d_names() -> list[str]:
             "Location_Center_X", "Location_Center_Y", "Location_Center_Z"]
 
 
+def intensity3d_detail_names(edge_measurements: bool = True) -> list[str]:
+    """Columns of `FeatureEngine.intensity3d_detail` (csrc/feat_intensity3d_detail.hip): `intensity_names(edge_measurements)` without
+    the columns `intensity3d` already gives, in that order: the five edge statistics (only with the flag), MassDisplacement, the
+    quartiles, median and MAD, and the position of the maximum.  13 columns, or 8.  torch.cat([intensity3d, intensity3d_detail], 1)
+    is then the 2-D family's whole column set plus Volume and Location_Center_*.  Parity with cp_measure on volumes is unpinned, like
+    the other 3-D families."""
+    if not isinstance(edge_measurements, bool):
+        raise TypeError(f"edge_measurements must be a bool, got {edge_measurements!r}")
+    given = set(intensity3d_names())
+    return [name for name in intensity_names(edge_measurements) if name not in given]
+
+
 def sizeshape3d_names(surface_area: bool = False) -> list[str]:
     """Size and shape of volume labels (csrc/feat_sizeshape3d.hip), named after CellProfiler's 3-D MeasureObjectSizeShape (the
     names cp_measure's `sizeshape` uses for 3-D input; parity with it is unpinned, like intensity3d).  19 columns; with

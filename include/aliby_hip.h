@@ -626,6 +626,34 @@ int aliby_labels_apply_lut(aliby_ctx* ctx, const uint16_t* labels_in, int T, int
  * Center_X/Y/Z.  Exact integer sums: run-to-run deterministic. */
 int aliby_features_intensity3d(aliby_ctx* ctx, const uint16_t* labels, const uint16_t* pixels, int F, int C, int Z, int Y,
                                int X, int channel, const int32_t* offsets_host, double* out, int ld, int col0, void* stream);
+/* The columns of the 2-D intensity family (aliby_features_intensity) that aliby_features_intensity3d does not give, over the same
+ * labelled stacks: labels uint16 [F,Z,Y,X], pixels [F,C,Z,Y,X] of dtype ALIBY_U16 or ALIBY_F32, one channel per call.  The 2-D
+ * definitions, applied to the voxels of object (f, label) = row offsets_host[f] + label - 1 in raster order (z, y, x); parity with
+ * cp_measure on volumes is unpinned.  13 columns at out[row * ld + col0 ..] with edge = 1, the last 8 of them with edge = 0:
+ *   0-4 IntegratedIntensityEdge, MeanIntensityEdge, StdIntensityEdge (population), MinIntensityEdge, MaxIntensityEdge over the edge
+ *     voxels.  A voxel of the object is an edge voxel iff at least one of its six face neighbours INSIDE the volume carries another
+ *     value: 0, another label, or a label above n_f (skimage find_boundaries, connectivity 1, mode "inner", on the 3-D labels;
+ *     neighbours outside the volume do not count: the border is replicated).  An object with voxels but no edge voxel (it fills its
+ *     stack) gets 0.0 in all five, as in 2-D.
+ *   5 MassDisplacement: sqrt((dx dx + dy dy) + dz dz), d = Location_Center - Location_CenterMassIntensity in voxel indices, both
+ *     centres as aliby_features_intensity3d computes them (sums, one rounded division each); NaN when the integrated intensity is 0.
+ *   6, 7, 9 LowerQuartileIntensity, MedianIntensity, UpperQuartileIntensity: with the object's n values v sorted ascending and
+ *     p = 1/4, 1/2, 3/4: q = n p, i = floor(q), f = q - i; v[i] (1 - f) + v[i + 1] f if i < n - 1, else v[i]; float64 arithmetic
+ *     (CellProfiler's rule: n = 2 takes v[1] at 3/4).
+ *   8 MADIntensity: the same rule at p = 1/2 on the sorted |v - median|, the difference taken in float64.
+ *   10-12 Location_MaxIntensity_X, _Y, _Z: the voxel of the maximum; ties go to the LAST in raster order.
+ * ALIBY_U16: every sum is an exact 64-bit integer (the edge variance from n sum v^2 - (sum v)^2 in 128 bits), and the order
+ * statistics are exact.  ALIBY_F32: float64 sums in a tree that depends on the object's own voxels only, the edge deviation in a second
+ * pass about the mean; NaN pixels give unspecified results.  A label of 1..n_f without voxels gets NaN in every column (the volume
+ * families' convention; in the edge columns the 2-D family writes 0).  Labels above n_f are not measured.  Objects of up to
+ * aliby_intensity3d_detail_lds_voxels() voxels are measured from LDS, larger ones from global scratch, by the same code: results are
+ * bitwise independent of the run, of the other objects of the call and of the batch.  The object table and the larger objects' lists
+ * live in the context's scratch, so this is a main-stream call: one in flight per context (the scratch rule, csrc/object_launch.h);
+ * it waits for `stream` before it returns.  offsets_host[F] == 0 launches nothing.  Kernel: csrc/feat_intensity3d_detail.hip. */
+int aliby_intensity3d_detail_lds_voxels(void);
+int aliby_features_intensity3d_detail(aliby_ctx* ctx, const uint16_t* labels, const void* pixels, int dtype, int F, int C, int Z, int Y,
+                                      int X, int channel, const int32_t* offsets_host, int edge, double* out, int ld, int col0,
+                                      void* stream);
 /* Per-object size and shape over the same labelled stacks (uint16 [F,Z,Y,X], object (f, label) = row offsets_host[f] + label - 1).
  * 19 columns at out[row * ld + col0 ..]: Volume, BoundingBoxMinimum_X/Y/Z, BoundingBoxMaximum_X/Y/Z (exclusive),
  * BoundingBoxVolume, Center_X/Y/Z (voxel indices: bit-identical to intensity3d's), Extent, EquivalentDiameter, EulerNumber
