@@ -41,6 +41,7 @@
 // Everything but sqrt and atan2 is integer or a single rounded float64 operation: a row carries the same bits whatever the batch,
 // the workgroup size and the stream.
 #include "common.h"
+#include "neighbors_stats.h"
 
 typedef unsigned short u16;
 
@@ -54,13 +55,19 @@ struct NeighborsArgs {
   const int32_t* offsets;  // [F + 1], device
   int max_count;           // the largest tile's rows: what the bitmap was sized from
   int d;
-  double* centres;  // [n_obj, 2]
+  double* centres;  // [n_obj, 2] (y, x)
   double* out;
   int ld, col0;
+  __device__ __forceinline__ int rows() const { return n_obj; }
+  __device__ __forceinline__ bool stack_rows(int row, int& lo, int& hi) const {  // k_neighbors_closest: a row's stack is its tile
+    const int tile = tab[row].tile;
+    if (tile < 0 || tile >= F) return false;
+    lo = max(offsets[tile], 0); hi = min(offsets[tile + 1], n_obj);
+    return true;
+  }
 };
 
 __global__ __launch_bounds__(256) void k_neighbors_scan(NeighborsArgs a) {
-  extern __shared__ __align__(16) unsigned int bitmap[];
   __shared__ int red_i[8];
   __shared__ long long red_l[8];
   const int oi = blockIdx.x, tid = threadIdx.x;
@@ -70,16 +77,14 @@ __global__ __launch_bounds__(256) void k_neighbors_scan(NeighborsArgs a) {
   // the box, clipped to the frame (a table made from these labels never needs it)
   const int y0 = max(o.y0, 0), y1 = min(o.y1, a.Y), x0 = max(o.x0, 0), x1 = min(o.x1, a.X);
   if (o.area <= 0 || o.tile < 0 || o.tile >= a.F || y0 >= y1 || x0 >= x1) {
-    if (tid == 0) out[0] = out[1] = ctr[0] = ctr[1] = NAN;
+    if (tid == 0) neighbors_absent<2>(out, ctr);
     return;
   }
   const int Y = a.Y, X = a.X, h = y1 - y0, w = x1 - x0;
   const u16* lab = a.labels + (size_t)o.tile * Y * X;
   const int L = o.label;
-  const int nt = max(0, min(a.offsets[o.tile + 1] - a.offsets[o.tile], a.max_count));  // labels with a bit: 1..nt
-  const int words = (nt >> 5) + 1;
-  for (int k = tid; k < words; k += blockDim.x) bitmap[k] = 0u;
-  __syncthreads();
+  const NeighborsBitmap<0> bm{max(0, min(a.offsets[o.tile + 1] - a.offsets[o.tile], a.max_count))};
+  bm.clear();
 
   const int d = a.d, s2 = d * d, t2 = s2 + d;
   int n = 0, outline = 0, touching = 0, last_set = 0;
@@ -103,94 +108,17 @@ __global__ __launch_bounds__(256) void k_neighbors_scan(NeighborsArgs a) {
         if (dy >= -1 && dy <= 1 && dx >= -1 && dx <= 1) edge = true;  // (the 3 x 3 square lies inside T for every d >= 1)
         if (v == 0) continue;
         touch = true;
-        if (dd <= rs && v <= nt && v != last_set) {
-          const unsigned int bit = 1u << (v & 31);
-          // (a stale read only costs a redundant atomic)
-          if (!(reinterpret_cast<volatile unsigned int*>(bitmap)[v >> 5] & bit)) atomicOr(&bitmap[v >> 5], bit);
-          last_set = v;
-        }
+        bm.mark(dd <= rs, v, last_set);
       }
     }
     outline += edge;
     touching += edge && touch;
   }
   __syncthreads();
-  int cnt = 0;
-  for (int k = tid; k < words; k += blockDim.x) cnt += __popc(bitmap[k]);
-  cnt = block_sum_i32(cnt, red_i);
-  n = block_sum_i32(n, red_i);
-  outline = block_sum_i32(outline, red_i);
-  touching = block_sum_i32(touching, red_i);
-  sy = block_sum_i64(sy, red_l);
-  sx = block_sum_i64(sx, red_l);
-  if (tid == 0) {
-    if (n == 0) {  // (a row whose area the labels do not bear out: absent)
-      out[0] = out[1] = ctr[0] = ctr[1] = NAN;
-    } else {
-      out[0] = (double)cnt;
-      out[1] = (double)touching / (double)outline * 100.0;
-      ctr[0] = (double)sy / (double)n;
-      ctr[1] = (double)sx / (double)n;
-    }
-  }
-}
-
-// (key, label) pairs: lower key first, then lower label
-__device__ __forceinline__ bool nb_less(double ka, int la, double kb, int lb) { return ka < kb || (ka == kb && la < lb); }
-
-__global__ __launch_bounds__(256) void k_neighbors_closest(NeighborsArgs a) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int oi = blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE;  // wave-uniform
-  if (oi >= a.n_obj) return;
-  double* out = a.out + (size_t)oi * a.ld + a.col0 + 2;
-  const int tile = a.tab[oi].tile;
-  const double cy = a.centres[2 * (size_t)oi], cx = a.centres[2 * (size_t)oi + 1];
-  if (cy != cy || tile < 0 || tile >= a.F) {  // absent (k_neighbors_scan wrote a NaN centre)
-    if (lane < 5) out[lane] = NAN;
-    return;
-  }
-  const int lo = max(a.offsets[tile], 0), hi = min(a.offsets[tile + 1], a.n_obj);  // row lo + l - 1 is label l
-  double k1 = INFINITY, k2 = INFINITY;
-  int l1 = INT_MAX, l2 = INT_MAX;  // (INT_MAX: no candidate)
-  for (int j = lo + lane; j < hi; j += WAVE) {
-    if (j == oi) continue;
-    const double py = a.centres[2 * (size_t)j], px = a.centres[2 * (size_t)j + 1];
-    if (py != py) continue;
-    const double dy = py - cy, dx = px - cx, key = dy * dy + dx * dx;
-    const int l = j - lo + 1;
-    if (nb_less(key, l, k1, l1)) {
-      k2 = k1; l2 = l1; k1 = key; l1 = l;
-    } else if (nb_less(key, l, k2, l2)) {
-      k2 = key; l2 = l;
-    }
-  }
-#pragma unroll
-  for (int m = 1; m < WAVE; m <<= 1) {  // the lanes of a group hold the best two of the group's rows; groups double
-    const double p1 = __shfl_xor(k1, m, WAVE), p2 = __shfl_xor(k2, m, WAVE);
-    const int q1 = __shfl_xor(l1, m, WAVE), q2 = __shfl_xor(l2, m, WAVE);
-    if (nb_less(p1, q1, k1, l1)) {
-      const bool mine = nb_less(k1, l1, p2, q2);
-      k2 = mine ? k1 : p2; l2 = mine ? l1 : q2;
-      k1 = p1; l1 = q1;
-    } else if (nb_less(p1, q1, k2, l2)) {
-      k2 = p1; l2 = q1;
-    }
-  }
-  if (lane == 0) {
-    const bool has1 = l1 != INT_MAX, has2 = l2 != INT_MAX;
-    out[0] = has1 ? (double)l1 : 0.0;
-    out[1] = has1 ? sqrt(k1) : 0.0;
-    out[2] = has2 ? (double)l2 : 0.0;
-    out[3] = has2 ? sqrt(k2) : 0.0;
-    double angle = 0.0;
-    if (has2) {
-      const size_t r1 = (size_t)(lo + l1 - 1), r2 = (size_t)(lo + l2 - 1);
-      const double v1y = a.centres[2 * r1] - cy, v1x = a.centres[2 * r1 + 1] - cx;
-      const double v2y = a.centres[2 * r2] - cy, v2x = a.centres[2 * r2 + 1] - cx;
-      angle = (k1 == 0.0 || k2 == 0.0) ? (double)NAN : atan2(fabs(v1x * v2y - v1y * v2x), v1x * v2x + v1y * v2y) * (180.0 / M_PI);
-    }
-    out[4] = angle;
-  }
+  const int cnt = block_sum_i32(bm.popcount(), red_i);
+  n = block_sum_i32(n, red_i); outline = block_sum_i32(outline, red_i); touching = block_sum_i32(touching, red_i);
+  sy = block_sum_i64(sy, red_l); sx = block_sum_i64(sx, red_l);
+  if (tid == 0) neighbors_scan_write(out, ctr, cnt, n, outline, touching, sy, sx);
 }
 
 extern "C" int aliby_features_neighbors(aliby_ctx* ctx, const uint16_t* labels, int F, int Y, int X, const aliby_object* table_dev,
@@ -208,11 +136,9 @@ extern "C" int aliby_features_neighbors(aliby_ctx* ctx, const uint16_t* labels, 
   a.labels = labels; a.F = F; a.Y = Y; a.X = X; a.tab = table_dev; a.n_obj = n_obj; a.offsets = offsets_dev;
   a.max_count = max_count; a.d = distance; a.centres = centres_dev; a.out = out; a.ld = ld; a.col0 = col0;
   hipStream_t s = as_stream(stream);
-  const size_t lds = (((size_t)(max_count >> 5) + 1) * sizeof(unsigned int) + 15) & ~(size_t)15;  // <= 8 KiB
-  hipLaunchKernelGGL(k_neighbors_scan, dim3(n_obj), dim3(aliby_pick_block((long long)max_h * max_w)), lds, s, a);
+  hipLaunchKernelGGL(k_neighbors_scan, dim3(n_obj), dim3(aliby_pick_block((long long)max_h * max_w)), neighbors_bitmap_bytes(max_count), s, a);
   KERNEL_CHECK();
-  const int rows_per_block = 256 / WAVE;
-  hipLaunchKernelGGL(k_neighbors_closest, dim3((n_obj + rows_per_block - 1) / rows_per_block), dim3(256), 0, s, a);
+  neighbors_closest_launch<2>(a, n_obj, s);
   KERNEL_CHECK();
   return ALIBY_OK;
 }

@@ -38,14 +38,15 @@
 //      bit per label of the stack (atomicOr on 32-bit words; at most 8 KiB, sized by the largest stack of the call), behind the 2-D
 //      kernel's two filters: the last label set, and a test of the bit before the atomic.  Then: popcount of the bitmap, integer
 //      block reductions of p, t, the count and the three coordinate sums, columns 0-1 and the centre into centres_dev [rows, 3].
-//   3. k_neighbors3d_closest: one wave per row.  The lanes stride over the centres of the row's own stack (a NaN centre = absent),
-//      each keeps its two best (key, label) pairs, and a butterfly merges them under the order "lower key, then lower label": a
-//      total order on distinct labels, so the result does not depend on which lane saw which row.  Columns 2-6.
+//   3. k_neighbors_closest<3> (neighbors_stats.h, the 2-D family's kernel): one wave per row.  The lanes stride over the centres of
+//      the row's own stack (a NaN centre = absent), each keeps its two best (key, label) pairs, and a butterfly merges them under the
+//      order "lower key, then lower label": a total order on distinct labels, so the result is the same whichever lane saw a row.  Columns 2-6.
 // The object table lives in the context's scratch, so this is a main-stream family: one such call in flight per context (the
 // scratch rule, object_launch.h); the entry waits for its stream before it returns.
 // Everything but sqrt and atan2 is integer or a single rounded float64 operation, and the workgroup size is fixed: a row carries
 // the same bits whatever the batch, the other stacks of the call, the grid and the stream.
 #include "common.h"
+#include "neighbors_stats.h"
 #include "volume_table.h"
 
 typedef unsigned short u16;
@@ -62,6 +63,12 @@ struct N3Args {
   double* centres;  // [rows, 3] (z, y, x)
   double* out;
   int ld, col0;
+  __device__ __forceinline__ int rows() const { return v.n_items; }
+  __device__ __forceinline__ bool stack_rows(int row, int& lo, int& hi) const {  // k_neighbors_closest: found in the offsets
+    const int f = volume_stack_of(v.offsets, v.F, row);
+    lo = max(v.offsets[f], 0); hi = min(v.offsets[f + 1], v.n_items);
+    return true;
+  }
 };
 
 // the largest w >= 0 with w * w <= r, for 0 <= r <= 16^2 + 16 (exact: float sqrt is within one of it)
@@ -73,14 +80,13 @@ __device__ __forceinline__ int n3_isqrt(int r) {
 }
 
 __global__ __launch_bounds__(N3_BLOCK) void k_neighbors3d_scan(N3Args a) {
-  extern __shared__ __align__(16) unsigned int bitmap[];
   __shared__ int red_i[8];
   __shared__ long long red_l[8];
   const int row = blockIdx.x, tid = threadIdx.x;
   double* out = a.out + (size_t)row * a.ld + a.col0;
   double* ctr = a.centres + 3 * (size_t)row;
   if (a.v.count[row] == 0) {  // a label without voxels
-    if (tid == 0) out[0] = out[1] = ctr[0] = ctr[1] = ctr[2] = NAN;
+    if (tid == 0) neighbors_absent<3>(out, ctr);
     return;
   }
   const int Z = a.v.Z, Y = a.v.Y, X = a.v.X;
@@ -88,10 +94,8 @@ __global__ __launch_bounds__(N3_BLOCK) void k_neighbors3d_scan(N3Args a) {
   const int L = row - a.v.offsets[f] + 1;
   const u16* lab = a.v.labels + (size_t)f * Z * Y * X;
   const VolumeBox box = volume_box(a.v.bmin, a.v.bmax, row);
-  const int nt = max(0, min(a.v.offsets[f + 1] - a.v.offsets[f], a.max_count));  // labels with a bit: 1..nt
-  const int words = (nt >> 5) + 1;
-  for (int k = tid; k < words; k += N3_BLOCK) bitmap[k] = 0u;
-  __syncthreads();
+  const NeighborsBitmap<N3_BLOCK> bm{max(0, min(a.v.offsets[f + 1] - a.v.offsets[f], a.max_count))};
+  bm.clear();
 
   const int d = a.d, s2 = d * d, t2 = s2 + d;
   int n = 0, outline = 0, touching = 0, last_set = 0;
@@ -123,12 +127,7 @@ __global__ __launch_bounds__(N3_BLOCK) void k_neighbors3d_scan(N3Args a) {
           if (near_y && dx >= -1 && dx <= 1) edge = true;  // (the in-plane 3 x 3 square lies inside T for every d >= 1)
           if (v == 0) continue;
           touch = true;
-          if (dx * dx <= rs && v <= nt && v != last_set) {
-            const unsigned int bit = 1u << (v & 31);
-            // (a stale read only costs a redundant atomic)
-            if (!(reinterpret_cast<volatile unsigned int*>(bitmap)[v >> 5] & bit)) atomicOr(&bitmap[v >> 5], bit);
-            last_set = v;
-          }
+          bm.mark(dx * dx <= rs, v, last_set);
         }
       }
     }
@@ -136,89 +135,10 @@ __global__ __launch_bounds__(N3_BLOCK) void k_neighbors3d_scan(N3Args a) {
     touching += edge && touch;
   }
   __syncthreads();
-  int cnt = 0;
-  for (int k = tid; k < words; k += N3_BLOCK) cnt += __popc(bitmap[k]);
-  cnt = block_sum_i32(cnt, red_i);
-  n = block_sum_i32(n, red_i);
-  outline = block_sum_i32(outline, red_i);
-  touching = block_sum_i32(touching, red_i);
-  sz = block_sum_i64(sz, red_l);
-  sy = block_sum_i64(sy, red_l);
-  sx = block_sum_i64(sx, red_l);
-  if (tid == 0) {
-    if (n == 0) {  // (a row whose count the labels do not bear out: absent)
-      out[0] = out[1] = ctr[0] = ctr[1] = ctr[2] = NAN;
-    } else {
-      out[0] = (double)cnt;
-      out[1] = (double)touching / (double)outline * 100.0;
-      ctr[0] = (double)sz / (double)n;
-      ctr[1] = (double)sy / (double)n;
-      ctr[2] = (double)sx / (double)n;
-    }
-  }
-}
-
-// (key, label) pairs: lower key first, then lower label
-__device__ __forceinline__ bool n3_less(double ka, int la, double kb, int lb) { return ka < kb || (ka == kb && la < lb); }
-
-__global__ __launch_bounds__(N3_BLOCK) void k_neighbors3d_closest(N3Args a) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int row = blockIdx.x * (N3_BLOCK / WAVE) + threadIdx.x / WAVE;  // wave-uniform
-  const int n_rows = a.v.n_items;
-  if (row >= n_rows) return;
-  double* out = a.out + (size_t)row * a.ld + a.col0 + 2;
-  const double cz = a.centres[3 * (size_t)row], cy = a.centres[3 * (size_t)row + 1], cx = a.centres[3 * (size_t)row + 2];
-  if (cz != cz) {  // absent (k_neighbors3d_scan wrote a NaN centre)
-    if (lane < 5) out[lane] = NAN;
-    return;
-  }
-  const int f = volume_stack_of(a.v.offsets, a.v.F, row);
-  const int lo = max(a.v.offsets[f], 0), hi = min(a.v.offsets[f + 1], n_rows);  // row lo + l - 1 is label l
-  double k1 = INFINITY, k2 = INFINITY;
-  int l1 = INT_MAX, l2 = INT_MAX;  // (INT_MAX: no candidate)
-  for (int j = lo + lane; j < hi; j += WAVE) {
-    if (j == row) continue;
-    const double pz = a.centres[3 * (size_t)j], py = a.centres[3 * (size_t)j + 1], px = a.centres[3 * (size_t)j + 2];
-    if (pz != pz) continue;
-    const double dz = pz - cz, dy = py - cy, dx = px - cx, key = (dz * dz + dy * dy) + dx * dx;
-    const int l = j - lo + 1;
-    if (n3_less(key, l, k1, l1)) {
-      k2 = k1; l2 = l1; k1 = key; l1 = l;
-    } else if (n3_less(key, l, k2, l2)) {
-      k2 = key; l2 = l;
-    }
-  }
-#pragma unroll
-  for (int m = 1; m < WAVE; m <<= 1) {  // the lanes of a group hold the best two of the group's rows; groups double
-    const double p1 = __shfl_xor(k1, m, WAVE), p2 = __shfl_xor(k2, m, WAVE);
-    const int q1 = __shfl_xor(l1, m, WAVE), q2 = __shfl_xor(l2, m, WAVE);
-    if (n3_less(p1, q1, k1, l1)) {
-      const bool mine = n3_less(k1, l1, p2, q2);
-      k2 = mine ? k1 : p2; l2 = mine ? l1 : q2;
-      k1 = p1; l1 = q1;
-    } else if (n3_less(p1, q1, k2, l2)) {
-      k2 = p1; l2 = q1;
-    }
-  }
-  if (lane == 0) {
-    const bool has1 = l1 != INT_MAX, has2 = l2 != INT_MAX;
-    out[0] = has1 ? (double)l1 : 0.0;
-    out[1] = has1 ? sqrt(k1) : 0.0;
-    out[2] = has2 ? (double)l2 : 0.0;
-    out[3] = has2 ? sqrt(k2) : 0.0;
-    double angle = 0.0;
-    if (has2) {
-      const double* c1 = a.centres + 3 * (size_t)(lo + l1 - 1);
-      const double* c2 = a.centres + 3 * (size_t)(lo + l2 - 1);
-      const double v1z = c1[0] - cz, v1y = c1[1] - cy, v1x = c1[2] - cx;
-      const double v2z = c2[0] - cz, v2y = c2[1] - cy, v2x = c2[2] - cx;
-      // the cross product on the axes (z, y, x); with both dz = 0 only its z component is left: the 2-D family's
-      const double wz = v1x * v2y - v1y * v2x, wy = v1z * v2x - v1x * v2z, wx = v1y * v2z - v1z * v2y;
-      angle = (k1 == 0.0 || k2 == 0.0) ? (double)NAN
-                                       : atan2(sqrt((wx * wx + wy * wy) + wz * wz), (v1z * v2z + v1y * v2y) + v1x * v2x) * (180.0 / M_PI);
-    }
-    out[4] = angle;
-  }
+  const int cnt = block_sum_i32(bm.popcount(), red_i);
+  n = block_sum_i32(n, red_i); outline = block_sum_i32(outline, red_i); touching = block_sum_i32(touching, red_i);
+  sz = block_sum_i64(sz, red_l); sy = block_sum_i64(sy, red_l); sx = block_sum_i64(sx, red_l);
+  if (tid == 0) neighbors_scan_write(out, ctr, cnt, n, outline, touching, sz, sy, sx);
 }
 
 }  // namespace
@@ -244,11 +164,9 @@ extern "C" int aliby_features_neighbors3d(aliby_ctx* ctx, const uint16_t* labels
   a.v = plan.args; a.d = distance; a.centres = centres_dev; a.out = out; a.ld = ld; a.col0 = col0;
   a.max_count = 0;
   for (int f = 0; f < F; ++f) a.max_count = std::max(a.max_count, offsets_host[f + 1] - offsets_host[f]);  // <= 65535 (volume_offsets_ok)
-  const size_t lds = (((size_t)(a.max_count >> 5) + 1) * sizeof(unsigned int) + 15) & ~(size_t)15;  // <= 8 KiB
-  hipLaunchKernelGGL(k_neighbors3d_scan, dim3(n), dim3(N3_BLOCK), lds, s, a);
+  hipLaunchKernelGGL(k_neighbors3d_scan, dim3(n), dim3(N3_BLOCK), neighbors_bitmap_bytes(a.max_count), s, a);
   KERNEL_CHECK();
-  const int rows_per_block = N3_BLOCK / WAVE;
-  hipLaunchKernelGGL(k_neighbors3d_closest, dim3((n + rows_per_block - 1) / rows_per_block), dim3(N3_BLOCK), 0, s, a);
+  neighbors_closest_launch<3>(a, n, s);
   KERNEL_CHECK();
   // the table and the offsets live in ctx scratch: they must be consumed before the host reuses it
   return aliby_wait_stream(s);

@@ -372,6 +372,35 @@ class FeatureEngine:
             raise ValueError(f"{who} takes tensors on the device")
         return F, int(pixels.shape[1]), Z, Y, X, FeatureEngine._volume_offsets(who, F, counts)
 
+    @staticmethod
+    def _integer(name: str, v) -> int:
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"{name} must be an integer, got {v!r}")
+        return int(v)
+
+    @staticmethod
+    def _channel(channel, Cn: int) -> int:
+        channel = FeatureEngine._integer("channel", channel)
+        if not 0 <= channel < Cn:
+            raise ValueError(f"channel {channel} out of range for {Cn} channels")
+        return channel
+
+    @staticmethod
+    def _pixel_code(pixels: torch.Tensor) -> int:
+        """dtype code of the pixels of a volume method (uint16 or float32: _volume_inputs)."""
+        return _lib.U16 if pixels.dtype == torch.uint16 else _lib.F32
+
+    def _volume_block(self, rows: int, cols: int, *launches) -> torch.Tensor:
+        """The result of a volume method: a NaN block [rows, cols], handed to call(out) of every (profile group, call) of `launches`
+        in turn.  Stacks without any object: the empty block and no launch (found by tests/fuzz/fuzz_volume.py — the C entries refuse
+        a NULL output)."""
+        out = self.new_output(rows, cols)
+        if rows:
+            for name, call in launches:
+                with self.timed(name):
+                    _lib.check(call(out))
+        return out
+
     def intensity3d(self, volume: torch.Tensor, pixels: torch.Tensor, channel: int, counts) -> torch.Tensor:
         """Volume labels uint16 [F,Z,Y,X] (1..counts[f] per stack), pixels uint16 [F,C,Z,Y,X] -> float64 [sum counts, 12]
         (features.intensity3d_names(); aliby_features_intensity3d).  Rows in (stack, label) order.  A label of 1..counts[f]
@@ -380,18 +409,10 @@ class FeatureEngine:
         F, Cn, Z, Y, X, offsets = self._volume_inputs("intensity3d", volume, pixels, counts)
         if pixels.dtype != torch.uint16:
             raise TypeError(f"intensity3d: pixels must be uint16 (the family has no float form), got {pixels.dtype}")
-        if isinstance(channel, bool) or not isinstance(channel, (int, np.integer)):
-            raise TypeError(f"channel must be an integer, got {channel!r}")
-        if not 0 <= int(channel) < Cn:
-            raise ValueError(f"channel {int(channel)} out of range for {Cn} channels")
-        out = self.new_output(int(offsets[-1]), 12)
-        if int(offsets[-1]) == 0:
-            return out  # stacks without any object: an empty block (found by tests/fuzz/fuzz_volume.py — the C entry refuses a NULL output)
-        with self.timed("intensity3d"):
-            _lib.check(self.lib.aliby_features_intensity3d(self.ctx.handle, _ptr(volume.contiguous()), _ptr(pixels.contiguous()), F, Cn, Z, Y,
-                                                           X, int(channel), _ptr(offsets), _ptr(out), out.stride(0) if out.numel() else 12, 0,
-                                                           _stream_ptr()))
-        return out
+        channel = self._channel(channel, Cn)
+        return self._volume_block(int(offsets[-1]), 12, ("intensity3d", lambda out: self.lib.aliby_features_intensity3d(
+            self.ctx.handle, _ptr(volume.contiguous()), _ptr(pixels.contiguous()), F, Cn, Z, Y, X, channel, _ptr(offsets), _ptr(out), out.stride(0), 0,
+            _stream_ptr())))
 
     @property
     def intensity3d_detail_lds_voxels(self) -> int:
@@ -411,19 +432,11 @@ class FeatureEngine:
         `intensity3d_detail_lds_voxels` voxels are measured in the context's scratch, where the object table is built too: a
         main-stream call, one in flight per context (the scratch rule, csrc/object_launch.h).  Bitwise independent of run and batch."""
         F, Cn, Z, Y, X, offsets = self._volume_inputs("intensity3d_detail", volume, pixels, counts)
-        if isinstance(channel, bool) or not isinstance(channel, (int, np.integer)):
-            raise TypeError(f"channel must be an integer, got {channel!r}")
-        names = feat.intensity3d_detail_names(edge_measurements)  # (refuses a flag that is not a bool)
-        if not 0 <= int(channel) < Cn:
-            raise ValueError(f"channel {int(channel)} out of range for {Cn} channels")
-        out = self.new_output(int(offsets[-1]), len(names))
-        if int(offsets[-1]) == 0:
-            return out  # stacks without any object: an empty block
-        with self.timed("intensity3d_detail"):
-            _lib.check(self.lib.aliby_features_intensity3d_detail(
-                self.ctx.handle, _ptr(volume.contiguous()), _ptr(pixels.contiguous()), _lib.U16 if pixels.dtype == torch.uint16 else _lib.F32,
-                F, Cn, Z, Y, X, int(channel), _ptr(offsets), int(edge_measurements), _ptr(out), out.stride(0), 0, _stream_ptr()))
-        return out
+        names = feat.intensity3d_detail_names(edge_measurements)  # (refuses a flag that is not a bool, before the channel's range)
+        channel = self._channel(channel, Cn)
+        return self._volume_block(int(offsets[-1]), len(names), ("intensity3d_detail", lambda out: self.lib.aliby_features_intensity3d_detail(
+            self.ctx.handle, _ptr(volume.contiguous()), _ptr(pixels.contiguous()), self._pixel_code(pixels), F, Cn, Z, Y, X, channel, _ptr(offsets),
+            int(edge_measurements), _ptr(out), out.stride(0), 0, _stream_ptr())))
 
     @staticmethod
     def _spacing3d(spacing) -> np.ndarray:
@@ -461,18 +474,15 @@ class FeatureEngine:
         if surface_area:
             self._surface3d_shape(Z, Y, X)
         offsets = self._volume_offsets("sizeshape3d", F, counts)
-        out = self.new_output(int(offsets[-1]), 20 if surface_area else 19)
-        if int(offsets[-1]) == 0:
-            return out  # stacks without any object: an empty block
         volume = volume.contiguous()
-        with self.timed("sizeshape3d"):
-            _lib.check(self.lib.aliby_features_sizeshape3d(self.ctx.handle, _ptr(volume), F, Z, Y, X, _ptr(offsets), _ptr(sp), _ptr(out),
-                                                           out.stride(0), 0, _stream_ptr()))
+
+        def launch(fn, col0):
+            return lambda out: fn(self.ctx.handle, _ptr(volume), F, Z, Y, X, _ptr(offsets), _ptr(sp), _ptr(out), out.stride(0), col0, _stream_ptr())
+
+        launches = [("sizeshape3d", launch(self.lib.aliby_features_sizeshape3d, 0))]
         if surface_area:
-            with self.timed("surface3d"):
-                _lib.check(self.lib.aliby_features_surface3d(self.ctx.handle, _ptr(volume), F, Z, Y, X, _ptr(offsets), _ptr(sp), _ptr(out),
-                                                             out.stride(0), 19, _stream_ptr()))
-        return out
+            launches.append(("surface3d", launch(self.lib.aliby_features_surface3d, 19)))
+        return self._volume_block(int(offsets[-1]), 20 if surface_area else 19, *launches)
 
     @property
     def coloc3d_lds_voxels(self) -> int:
@@ -495,17 +505,11 @@ class FeatureEngine:
         thr, scale_max = float(thr), float(scale_max)
         if not (np.isfinite(thr) and np.isfinite(scale_max) and scale_max > 0):
             raise ValueError(f"thr must be finite and scale_max positive and finite, got {thr!r}, {scale_max!r}")
-        stride = 2 * len(metrics)
-        out = self.new_output(int(offsets[-1]), len(names))
-        if int(offsets[-1]) == 0:
-            return out  # stacks without any object: an empty block
         col = {m: 2 * k for k, m in enumerate(metrics)}
-        with self.timed("coloc3d"):
-            _lib.check(self.lib.aliby_features_coloc3d(
-                self.ctx.handle, _ptr(volume.contiguous()), _ptr(pixels.contiguous()), _lib.U16 if pixels.dtype == torch.uint16 else _lib.F32,
-                F, Cn, Z, Y, X, _ptr(pr), len(pr), _ptr(offsets), _ptr(out), out.stride(0), 0, stride, col.get("pearson", -1),
-                col.get("manders_fold", -1), col.get("rwc", -1), col.get("costes", -1), thr, scale_max, _stream_ptr()))
-        return out
+        return self._volume_block(int(offsets[-1]), len(names), ("coloc3d", lambda out: self.lib.aliby_features_coloc3d(
+            self.ctx.handle, _ptr(volume.contiguous()), _ptr(pixels.contiguous()), self._pixel_code(pixels), F, Cn, Z, Y, X, _ptr(pr), len(pr),
+            _ptr(offsets), _ptr(out), out.stride(0), 0, 2 * len(metrics), col.get("pearson", -1), col.get("manders_fold", -1), col.get("rwc", -1),
+            col.get("costes", -1), thr, scale_max, _stream_ptr())))
 
     @property
     def texture3d_lds_voxels(self) -> int:
@@ -518,22 +522,14 @@ class FeatureEngine:
         in 13 directions over each object's bounding box, direction-major.  Rows in (stack, label) order.  A direction without a
         voxel pair gets 13 NaN, a label of 1..counts[f] without voxels a row of NaN.  Bitwise independent of run and batch."""
         F, Cn, Z, Y, X, offsets = self._volume_inputs("texture3d", volume, pixels, counts)
-        for name, v in (("channel", channel), ("scale", scale), ("gray_levels", gray_levels)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-                raise TypeError(f"{name} must be an integer, got {v!r}")
-        channel, scale, gray_levels = int(channel), int(scale), int(gray_levels)
-        if not 0 <= channel < Cn:
-            raise ValueError(f"channel {channel} out of range for {Cn} channels")
+        scale, gray_levels = self._integer("scale", scale), self._integer("gray_levels", gray_levels)
+        channel = self._channel(channel, Cn)
         if scale < 1 or not 2 <= gray_levels <= 256:
             raise ValueError(f"texture3d needs scale >= 1 and 2 <= gray_levels <= 256, got {scale}, {gray_levels}")
-        out = self.new_output(int(offsets[-1]), len(feat.texture3d_names(scale, gray_levels)))
-        if int(offsets[-1]) == 0:
-            return out  # stacks without any object: an empty block
-        with self.timed("texture3d"):
-            _lib.check(self.lib.aliby_features_texture3d(
-                self.ctx.handle, _ptr(volume.contiguous()), _ptr(pixels.contiguous()), _lib.U16 if pixels.dtype == torch.uint16 else _lib.F32,
-                F, Cn, Z, Y, X, channel, _ptr(offsets), scale, gray_levels, _ptr(out), out.stride(0), 0, _stream_ptr()))
-        return out
+        cols = len(feat.texture3d_names(scale, gray_levels))
+        return self._volume_block(int(offsets[-1]), cols, ("texture3d", lambda out: self.lib.aliby_features_texture3d(
+            self.ctx.handle, _ptr(volume.contiguous()), _ptr(pixels.contiguous()), self._pixel_code(pixels), F, Cn, Z, Y, X, channel, _ptr(offsets),
+            scale, gray_levels, _ptr(out), out.stride(0), 0, _stream_ptr())))
 
     def neighbors3d(self, volume: torch.Tensor, counts, distance=None) -> torch.Tensor:
         """Volume labels uint16 [F,Z,Y,X] (1..counts[f] per stack) -> float64 [sum counts, 7] (features.neighbors3d_names(distance);
@@ -548,15 +544,9 @@ class FeatureEngine:
         d = feat.neighbors3d_distance(distance)
         F, Z, Y, X = self._volume_labels("neighbors3d", volume)
         offsets = self._volume_offsets("neighbors3d", F, counts)
-        rows = int(offsets[-1])
-        out = self.new_output(rows, 7)
-        if rows == 0:
-            return out  # stacks without any object: an empty block (the C entry refuses a NULL output)
-        centres = torch.empty((rows, 3), dtype=torch.float64, device=volume.device)
-        with self.timed("neighbors3d"):
-            _lib.check(self.lib.aliby_features_neighbors3d(self.ctx.handle, _ptr(volume.contiguous()), F, Z, Y, X, _ptr(offsets), d, _ptr(centres),
-                                                           _ptr(out), out.stride(0), 0, _stream_ptr()))
-        return out
+        centres = torch.empty((int(offsets[-1]), 3), dtype=torch.float64, device=volume.device)
+        return self._volume_block(int(offsets[-1]), 7, ("neighbors3d", lambda out: self.lib.aliby_features_neighbors3d(
+            self.ctx.handle, _ptr(volume.contiguous()), F, Z, Y, X, _ptr(offsets), d, _ptr(centres), _ptr(out), out.stride(0), 0, _stream_ptr())))
 
     def relabel_sequential(self, labels: torch.Tensor) -> np.ndarray:
         F, Y, X = labels.shape

@@ -144,16 +144,26 @@ def radial_zernike_names() -> list[str]:
 
 
 NEIGHBORS_MAX_DISTANCE = 64  # bounds the per-pixel scan of csrc/feat_neighbors.hip; not a structural limit
+NEIGHBORS3D_MAX_DISTANCE = 16  # bounds the per-voxel scan of csrc/feat_neighbors3d.hip (about 19 k offsets at 16); not a structural limit
+
+
+def _neighbors_distance(family: str, cap: int, distance) -> int:
+    if distance is None:
+        return 1
+    if isinstance(distance, bool) or not isinstance(distance, numbers.Integral) or not 1 <= int(distance) <= cap:
+        raise ValueError(f"{family}: distance must be None or an integer in 1..{cap}, got {distance!r}")
+    return int(distance)
+
+
+def _neighbors_names(suffix: str) -> list[str]:
+    return [f"Neighbors_{n}_{suffix}" for n in ("NumberOfNeighbors", "PercentTouching", "FirstClosestObjectNumber", "FirstClosestDistance",
+                                                "SecondClosestObjectNumber", "SecondClosestDistance", "AngleBetweenNeighbors")]
 
 
 def neighbors_distance(distance=None) -> int:
     """The pixel distance d of the `neighbors` family: None -> 1 (CellProfiler's "Adjacent"), else an integer in 1..64.  Anything
     else is a ValueError.  Needs no device."""
-    if distance is None:
-        return 1
-    if isinstance(distance, bool) or not isinstance(distance, numbers.Integral) or not 1 <= int(distance) <= NEIGHBORS_MAX_DISTANCE:
-        raise ValueError(f"neighbors: distance must be None or an integer in 1..{NEIGHBORS_MAX_DISTANCE}, got {distance!r}")
-    return int(distance)
+    return _neighbors_distance("neighbors", NEIGHBORS_MAX_DISTANCE, distance)
 
 
 def neighbors_names(distance=None) -> list[str]:
@@ -163,9 +173,7 @@ def neighbors_names(distance=None) -> list[str]:
     centrosome, neither of which can be run beside this package.  AngleBetweenNeighbors is atan2(|v1 x v2|, v1 . v2), not
     CellProfiler's arccos of the normalised dot product: the same angle, well-conditioned near 0 and 180 degrees (deliberate).
     Not built: "Expand until adjacent", neighbours from a second object set, distances above 64."""
-    s = "Adjacent" if distance is None else str(neighbors_distance(distance))
-    return [f"Neighbors_{n}_{s}" for n in ("NumberOfNeighbors", "PercentTouching", "FirstClosestObjectNumber", "FirstClosestDistance",
-                                           "SecondClosestObjectNumber", "SecondClosestDistance", "AngleBetweenNeighbors")]
+    return _neighbors_names("Adjacent" if distance is None else str(neighbors_distance(distance)))
 
 
 COLOC = {
@@ -259,17 +267,10 @@ def texture3d_names(scale: int = 3, gray_levels: int = 256) -> list[str]:
     return [f"{h}_{scale}_{d:02d}_{gray_levels}" for d in range(13) for h in HARALICK]
 
 
-NEIGHBORS3D_MAX_DISTANCE = 16  # bounds the per-voxel scan of csrc/feat_neighbors3d.hip (about 19 k offsets at 16); not a structural limit
-
-
 def neighbors3d_distance(distance=None) -> int:
     """The voxel distance d of `FeatureEngine.neighbors3d`: None -> 1 (CellProfiler's "Adjacent"), else an integer in 1..16.  Anything
     else is a ValueError.  Needs no device."""
-    if distance is None:
-        return 1
-    if isinstance(distance, bool) or not isinstance(distance, numbers.Integral) or not 1 <= int(distance) <= NEIGHBORS3D_MAX_DISTANCE:
-        raise ValueError(f"neighbors3d: distance must be None or an integer in 1..{NEIGHBORS3D_MAX_DISTANCE}, got {distance!r}")
-    return int(distance)
+    return _neighbors_distance("neighbors3d", NEIGHBORS3D_MAX_DISTANCE, distance)
 
 
 def neighbors3d_names(distance=None) -> list[str]:
@@ -279,6 +280,4 @@ def neighbors3d_names(distance=None) -> list[str]:
     AngleBetweenNeighbors is atan2(|v1 x v2|, v1 . v2), not CellProfiler's arccos of the normalised dot product: the same angle,
     well-conditioned near 0 and 180 degrees (deliberate).  Not built: "Expand until adjacent", neighbours from a second object set,
     physical-unit (anisotropic) balls, distances above 16."""
-    s = "Adjacent" if distance is None else str(neighbors3d_distance(distance))
-    return [f"Neighbors_{n}_{s}" for n in ("NumberOfNeighbors", "PercentTouching", "FirstClosestObjectNumber", "FirstClosestDistance",
-                                           "SecondClosestObjectNumber", "SecondClosestDistance", "AngleBetweenNeighbors")]
+    return _neighbors_names("Adjacent" if distance is None else str(neighbors3d_distance(distance)))
