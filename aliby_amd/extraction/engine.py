@@ -548,6 +548,57 @@ class FeatureEngine:
         return self._volume_block(int(offsets[-1]), 7, ("neighbors3d", lambda out: self.lib.aliby_features_neighbors3d(
             self.ctx.handle, _ptr(volume.contiguous()), F, Z, Y, X, _ptr(offsets), d, _ptr(centres), _ptr(out), out.stride(0), 0, _stream_ptr())))
 
+    @staticmethod
+    def _granularity3d_shapes(Z: int, Y: int, X: int, subsample_size: float, image_sample_size: float):
+        """-> the subsampled and the background shape of `granularity3d`: ceil(n * size) per axis when the size is below 1, else n
+        (numpy's mgrid[0 : n * size] has that many points)."""
+        sub = tuple(int(np.ceil(n * subsample_size)) if subsample_size < 1 else int(n) for n in (Z, Y, X))
+        return sub, tuple(int(np.ceil(n * image_sample_size)) if image_sample_size < 1 else n for n in sub)
+
+    def granularity3d(self, volume: torch.Tensor, pixels: torch.Tensor, channel: int, counts, subsample_size: float = 0.25,
+                      image_sample_size: float = 0.25, element_size: int = 10, granular_spectrum_length: int = 16) -> torch.Tensor:
+        """Volume labels uint16 [F,Z,Y,X] (1..counts[f] per stack), pixels uint16 or float32 [F,C,Z,Y,X] -> float64 [sum counts, L]
+        (features.granularity3d_names(L); aliby_features_granularity3d): the `granularity` family on volumes, CellProfiler
+        MeasureGranularity's volumetric branch — each stack of `channel` subsampled trilinearly by `subsample_size`, its background
+        (grey erosion and dilation with ball(element_size) on a further `image_sample_size` subsample, resized back) removed, then L
+        rounds of erosion by ball(1) and reconstruction by dilation; Granularity_i = (mean_{i-1} - mean_i) * 100 / max(mean_0, eps)
+        over each object's voxels, mean_0 on the original pixels.  The image mask is the whole stack (CellProfiler's default).  Where
+        the destination axis of a resize has length 1 its coordinate is 0 (CellProfiler divides 0 by 0 there): with this one
+        departure a stack of one plane is the 2-D `granularity`.  Rows in (stack, label) order.  A label of 1..counts[f] without
+        voxels gets a row of NaN; labels above counts[f] are not measured.  Y, X and their two sampled lengths must be above 1, Z may
+        be 1; element_size is an integer in 1..16 (the cap bounds the per-voxel scan of the ball, it is not a structural limit), L
+        in 1..64.  PARITY UNPINNED: the definition is in include/aliby_hip.h, restated in tests/granularity3d_ref.py.  The
+        reconstruction reads a change flag every 16 sweeps, so the call waits on its stream: a main-stream call.  `granularity3d_sweeps`
+        holds the sweeps of each spectrum step of the last call.  Bitwise independent of run and batch."""
+        F, Cn, Z, Y, X, offsets = self._volume_inputs("granularity3d", volume, pixels, counts)
+        channel = self._channel(channel, Cn)
+        sizes = []
+        for name, v in (("subsample_size", subsample_size), ("image_sample_size", image_sample_size)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not (np.isfinite(v) and 0 < v <= 1):
+                raise ValueError(f"granularity3d: {name} must be a finite number in (0, 1], got {v!r}")
+            sizes.append(float(v))
+        element_size, L = self._integer("element_size", element_size), self._integer("granular_spectrum_length", granular_spectrum_length)
+        if not 1 <= element_size <= feat.GRANULARITY3D_MAX_ELEMENT:
+            raise ValueError(f"granularity3d: element_size must lie in 1..{feat.GRANULARITY3D_MAX_ELEMENT}, got {element_size}")
+        names = feat.granularity3d_names(L)  # (refuses a length outside 1..64)
+        sub, back = self._granularity3d_shapes(Z, Y, X, *sizes)
+        if min(Y, X, *sub[1:], *back[1:]) <= 1:
+            raise ValueError(f"granularity3d: Y, X and their sampled lengths must be above 1, got a stack {(Z, Y, X)}, subsampled {sub}, background {back}")
+        rows = int(offsets[-1])
+        sweeps = np.zeros(L, np.int32)
+
+        def launch(out):
+            need = int(self.lib.aliby_granularity3d_workspace_bytes(F, Z, Y, X, rows, sizes[0], sizes[1]))
+            work = torch.empty((need + 7) // 8, dtype=torch.float64, device=volume.device)
+            return self.lib.aliby_features_granularity3d(
+                self.ctx.handle, _ptr(volume.contiguous()), _ptr(pixels.contiguous()), self._pixel_code(pixels), F, Cn, Z, Y, X, channel,
+                _ptr(offsets), sizes[0], sizes[1], element_size, L, _ptr(work), work.numel() * 8, _ptr(sweeps), _ptr(out), out.stride(0), 0,
+                _stream_ptr())
+
+        out = self._volume_block(rows, len(names), ("granularity3d", launch))
+        self.granularity3d_sweeps = sweeps.tolist()
+        return out
+
     def relabel_sequential(self, labels: torch.Tensor) -> np.ndarray:
         F, Y, X = labels.shape
         n = np.zeros(F, np.int32)

@@ -281,3 +281,17 @@ def neighbors3d_names(distance=None) -> list[str]:
     well-conditioned near 0 and 180 degrees (deliberate).  Not built: "Expand until adjacent", neighbours from a second object set,
     physical-unit (anisotropic) balls, distances above 16."""
     return _neighbors_names("Adjacent" if distance is None else str(neighbors3d_distance(distance)))
+
+
+GRANULARITY3D_MAX_ELEMENT = 16  # bounds the per-voxel scan of the ball in csrc/feat_granularity3d.hip (about 17 k offsets at 16); not a structural limit
+GRANULARITY3D_MAX_LENGTH = 64
+
+
+def granularity3d_names(granular_spectrum_length: int = 16) -> list[str]:
+    """Columns of `FeatureEngine.granularity3d` (csrc/feat_granularity3d.hip): Granularity_1..L, the names of the 2-D `granularity`
+    (CellProfiler names a volume's spectrum as it names a plane's).  L is an integer in 1..64; parity with CellProfiler is unpinned."""
+    if isinstance(granular_spectrum_length, bool) or not isinstance(granular_spectrum_length, numbers.Integral):
+        raise TypeError(f"granular_spectrum_length must be an integer, got {granular_spectrum_length!r}")
+    if not 1 <= int(granular_spectrum_length) <= GRANULARITY3D_MAX_LENGTH:
+        raise ValueError(f"granularity3d: granular_spectrum_length must lie in 1..{GRANULARITY3D_MAX_LENGTH}, got {granular_spectrum_length!r}")
+    return granularity_names(int(granular_spectrum_length))

@@ -739,6 +739,38 @@ int aliby_features_texture3d(aliby_ctx* ctx, const uint16_t* labels, const void*
  * independent of the run, of the other stacks of the call and of the batch.  Kernels: csrc/feat_neighbors3d.hip. */
 int aliby_features_neighbors3d(aliby_ctx* ctx, const uint16_t* labels, int F, int Z, int Y, int X, const int32_t* offsets_host,
                                int distance, double* centres_dev, double* out, int ld, int col0, void* stream);
+/* "granularity3d": the `granularity` family (aliby_features_granularity: CellProfiler's MeasureGranularity) on the same labelled
+ * stacks.  PARITY UNPINNED: CellProfiler's volumetric branch, recalled (tests/granularity3d_ref.py restates it).  Everything is
+ * float64; every stack [Z,Y,X] of `channel` is on its own, nothing crosses from one stack of the batch into the next:
+ *   1. shapes: the subsampled shape is ceil(n * subsample_size) per axis when the size is below 1, else n; the background shape is
+ *      the same rule applied to the subsampled shape with image_sample_size.
+ *   2. subsample: scipy.ndimage.map_coordinates(order=1) at positions i / subsample_size (a division): trilinear inside [0, n - 1]
+ *      on every axis, 0 outside.
+ *   3. background: resample again at i / image_sample_size; grey erosion, then grey dilation, with ball(element_size)
+ *      (dz^2 + dy^2 + dx^2 <= r^2) under ndimage's "reflect" border (d c b a | a b c d | d c b a, folded as often as the footprint
+ *      needs); resize back trilinearly at i * ((b - 1) / (s - 1)); pix = max(subsampled - background, 0).
+ *   4. spectrum, spectrum_length times, from ero = pix: ero = grey erosion of ero with ball(1) (the centre and the six face
+ *      neighbours) under "reflect"; rec = reconstruction by dilation of ero under pix with the same footprint (voxels outside the
+ *      stack never contribute); rec resized to the stack's shape at i * ((s - 1) / (n - 1)); mean_i = its mean over the object's
+ *      voxels; out[row * ld + col0 + i - 1] = (mean_{i-1} - mean_i) * 100 / max(mean_0, 2^-52), mean_0 over the ORIGINAL pixels.
+ *   5. the one deliberate departure: where the destination axis of a resize has length 1 its coordinate is 0 (CellProfiler's
+ *      (m - 1) / (n - 1) is 0 / 0 there).  With it a stack of one plane is aliby_features_granularity with the frame as image mask.
+ * The image mask is the whole stack (CellProfiler's default); the "objects" mask of the 2-D entry is not built.
+ * row = offsets_host[f] + L - 1; a label of 1..n_f without voxels gets NaN, labels above n_f are not measured.  Y, X and their two
+ * sampled lengths must be above 1 (Z and its sampled lengths may be 1); element_size in 1..16 (the cap bounds the per-voxel scan of
+ * the ball, about 17 k offsets at 16; it is not a structural limit), spectrum_length in 1..64; else ALIBY_ERR_INVALID.
+ * `workspace` is device memory of at least aliby_granularity3d_workspace_bytes(), 8-byte aligned: the images, the object table
+ * (count and bounding box per row, csrc/volume_table.h) and the offsets.  The reconstruction runs Jacobi sweeps in chunks of 16
+ * between reads of one change flag, so the call waits on `stream` while it iterates (a main-stream call); a step that has not
+ * converged after sz * sh * sw / 2 + 64 sweeps is ALIBY_ERR_TOO_LARGE, never a result.  sweeps_host (may be NULL) [spectrum_length]
+ * receives the sweeps each step ran (a multiple of 16; flag reads = sweeps / 16).  offsets_host[F] == 0 launches nothing.  Per-object
+ * means: one wave per row over the row's bounding box in a fixed lane and reduction order, so results are bitwise independent of the
+ * run, of the other stacks of the call and of the batch.  Kernels: csrc/feat_granularity3d.hip. */
+size_t aliby_granularity3d_workspace_bytes(int F, int Z, int Y, int X, int rows, double subsample_size, double image_sample_size);
+int aliby_features_granularity3d(aliby_ctx* ctx, const uint16_t* labels, const void* pixels, int dtype, int F, int C, int Z, int Y, int X,
+                                 int channel, const int32_t* offsets_host, double subsample_size, double image_sample_size,
+                                 int element_size, int spectrum_length, void* workspace, size_t workspace_bytes, int32_t* sweeps_host,
+                                 double* out, int ld, int col0, void* stream);
 
 /* ---- a17: the step API's files, encoded natively (host code, no GPU work) ------------------ */
 /* profiles/<name>.parquet — pyarrow.parquet.write_table(profiles, path, compression="zstd")
