@@ -175,6 +175,7 @@ _SIGNATURES = {
     "aliby_granularity3d_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, C.c_double, C.c_double]),
     "aliby_features_granularity3d": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_double, C.c_double, _i, _i, _vp, _sz, _vp,
                                           _vp, _i, _i, _vp]),
+    "aliby_features_projection3d": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
     "aliby_parquet_write":(_i, [C.c_char_p, _vp, _i, _vp, _i, _vp, _vp, _i]),
     "aliby_npz_write": (_i, [C.c_char_p, _vp, _i, _i]),
     "aliby_host_codecs": (_i, [C.POINTER(_i), C.POINTER(_i)]),

@@ -390,36 +390,50 @@ class FeatureEngine:
         """dtype code of the pixels of a volume method (uint16 or float32: _volume_inputs)."""
         return _lib.U16 if pixels.dtype == torch.uint16 else _lib.F32
 
-    def _volume_block(self, rows: int, cols: int, *launches) -> torch.Tensor:
-        """The result of a volume method: a NaN block [rows, cols], handed to call(out) of every (profile group, call) of `launches`
-        in turn.  Stacks without any object: the empty block and no launch (found by tests/fuzz/fuzz_volume.py — the C entries refuse
-        a NULL output)."""
-        out = self.new_output(rows, cols)
+    def _volume_block(self, rows: int, cols: int, *launches, out=None, col0: int = 0) -> torch.Tensor:
+        """The result of a volume method: a NaN block [rows, cols], handed to call(out, col0) of every (profile group, call) of
+        `launches` in turn.  Stacks without any object: the empty block and no launch (found by tests/fuzz/fuzz_volume.py — the C
+        entries refuse a NULL output).  With `out` (float64 [rows, >= col0 + cols] on the device, rows contiguous) the calls write
+        out[:, col0 : col0 + cols] in place through the C entries' (out, stride, col0), and that view is returned: what
+        extraction.families.evaluate_volume assembles its matrix with, instead of one block per family and a torch.cat.  Allocate
+        `out` with `new_output` (NaN-filled): a family may leave the cells of a label without voxels as it found them."""
+        if out is None:
+            out, col0, view = self.new_output(rows, cols), 0, None
+        else:
+            col0 = self._integer("col0", col0)
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or not out.is_cuda or out.dim() != 2:
+                raise TypeError("out must be a float64 [rows, columns] tensor on the device")
+            if out.shape[0] != rows or col0 < 0 or col0 + cols > out.shape[1] or (rows and out.stride(1) != 1):
+                raise ValueError(f"out must hold {rows} rows and columns {col0}..{col0 + cols - 1} with unit column stride, got "
+                                 f"{tuple(out.shape)} with strides {tuple(out.stride())}")
+            view = out[:, col0: col0 + cols]
         if rows:
             for name, call in launches:
                 with self.timed(name):
-                    _lib.check(call(out))
-        return out
+                    _lib.check(call(out, col0))
+        return out if view is None else view
 
-    def intensity3d(self, volume: torch.Tensor, pixels: torch.Tensor, channel: int, counts) -> torch.Tensor:
+    def intensity3d(self, volume: torch.Tensor, pixels: torch.Tensor, channel: int, counts, out=None, col0: int = 0) -> torch.Tensor:
         """Volume labels uint16 [F,Z,Y,X] (1..counts[f] per stack), pixels uint16 [F,C,Z,Y,X] -> float64 [sum counts, 12]
         (features.intensity3d_names(); aliby_features_intensity3d).  Rows in (stack, label) order.  A label of 1..counts[f]
         without voxels gets Volume 0 and NaN elsewhere; labels above counts[f] are not measured.  Exact 64-bit integer sums: bitwise
-        independent of run and batch."""
+        independent of run and batch.  out, col0 (here and in every volume method): write the block into out[:, col0:] in place
+        and return that view (`_volume_block`)."""
         F, Cn, Z, Y, X, offsets = self._volume_inputs("intensity3d", volume, pixels, counts)
         if pixels.dtype != torch.uint16:
             raise TypeError(f"intensity3d: pixels must be uint16 (the family has no float form), got {pixels.dtype}")
         channel = self._channel(channel, Cn)
-        return self._volume_block(int(offsets[-1]), 12, ("intensity3d", lambda out: self.lib.aliby_features_intensity3d(
-            self.ctx.handle, _ptr(volume.contiguous()), _ptr(pixels.contiguous()), F, Cn, Z, Y, X, channel, _ptr(offsets), _ptr(out), out.stride(0), 0,
-            _stream_ptr())))
+        return self._volume_block(int(offsets[-1]), 12, ("intensity3d", lambda out, c0: self.lib.aliby_features_intensity3d(
+            self.ctx.handle, _ptr(volume.contiguous()), _ptr(pixels.contiguous()), F, Cn, Z, Y, X, channel, _ptr(offsets), _ptr(out), out.stride(0), c0,
+            _stream_ptr())), out=out, col0=col0)
 
     @property
     def intensity3d_detail_lds_voxels(self) -> int:
         """Largest object, in voxels, that `intensity3d_detail` measures from LDS; larger ones go through global scratch (same results)."""
         return int(self.lib.aliby_intensity3d_detail_lds_voxels())
 
-    def intensity3d_detail(self, volume: torch.Tensor, pixels: torch.Tensor, channel: int, counts, edge_measurements: bool = True) -> torch.Tensor:
+    def intensity3d_detail(self, volume: torch.Tensor, pixels: torch.Tensor, channel: int, counts, edge_measurements: bool = True, out=None,
+                           col0: int = 0) -> torch.Tensor:
         """Volume labels uint16 [F,Z,Y,X] (1..counts[f] per stack), pixels uint16 or float32 [F,C,Z,Y,X] -> float64 [sum counts, 13]
         (8 with edge_measurements=False; features.intensity3d_detail_names(edge_measurements); aliby_features_intensity3d_detail): the
         columns of the 2-D `intensity` family that `intensity3d` lacks, over each object's voxels in raster order (z, y, x) — the five
@@ -434,9 +448,9 @@ class FeatureEngine:
         F, Cn, Z, Y, X, offsets = self._volume_inputs("intensity3d_detail", volume, pixels, counts)
         names = feat.intensity3d_detail_names(edge_measurements)  # (refuses a flag that is not a bool, before the channel's range)
         channel = self._channel(channel, Cn)
-        return self._volume_block(int(offsets[-1]), len(names), ("intensity3d_detail", lambda out: self.lib.aliby_features_intensity3d_detail(
+        return self._volume_block(int(offsets[-1]), len(names), ("intensity3d_detail", lambda out, c0: self.lib.aliby_features_intensity3d_detail(
             self.ctx.handle, _ptr(volume.contiguous()), _ptr(pixels.contiguous()), self._pixel_code(pixels), F, Cn, Z, Y, X, channel, _ptr(offsets),
-            int(edge_measurements), _ptr(out), out.stride(0), 0, _stream_ptr())))
+            int(edge_measurements), _ptr(out), out.stride(0), c0, _stream_ptr())), out=out, col0=col0)
 
     @staticmethod
     def _spacing3d(spacing) -> np.ndarray:
@@ -460,7 +474,7 @@ class FeatureEngine:
         if min(int(Z), int(Y), int(X)) < 2:
             raise ValueError(f"SurfaceArea needs a volume of at least 2 x 2 x 2 voxels (a marching-cubes cell), got {(int(Z), int(Y), int(X))}")
 
-    def sizeshape3d(self, volume: torch.Tensor, counts, spacing=(1.0, 1.0, 1.0), surface_area: bool = False) -> torch.Tensor:
+    def sizeshape3d(self, volume: torch.Tensor, counts, spacing=(1.0, 1.0, 1.0), surface_area: bool = False, out=None, col0: int = 0) -> torch.Tensor:
         """Volume labels uint16 [F,Z,Y,X] (1..counts[f] per stack) -> float64 [sum counts, 19] (features.sizeshape3d_names();
         aliby_features_sizeshape3d).  Rows in (stack, label) order; spacing = physical voxel size (dz, dy, dx).  A label of
         1..counts[f] without voxels gets Volume 0 and NaN elsewhere, as in intensity3d.
@@ -476,13 +490,13 @@ class FeatureEngine:
         offsets = self._volume_offsets("sizeshape3d", F, counts)
         volume = volume.contiguous()
 
-        def launch(fn, col0):
-            return lambda out: fn(self.ctx.handle, _ptr(volume), F, Z, Y, X, _ptr(offsets), _ptr(sp), _ptr(out), out.stride(0), col0, _stream_ptr())
+        def launch(fn, col):
+            return lambda out, c0: fn(self.ctx.handle, _ptr(volume), F, Z, Y, X, _ptr(offsets), _ptr(sp), _ptr(out), out.stride(0), c0 + col, _stream_ptr())
 
         launches = [("sizeshape3d", launch(self.lib.aliby_features_sizeshape3d, 0))]
         if surface_area:
             launches.append(("surface3d", launch(self.lib.aliby_features_surface3d, 19)))
-        return self._volume_block(int(offsets[-1]), 20 if surface_area else 19, *launches)
+        return self._volume_block(int(offsets[-1]), 20 if surface_area else 19, *launches, out=out, col0=col0)
 
     @property
     def coloc3d_lds_voxels(self) -> int:
@@ -490,7 +504,7 @@ class FeatureEngine:
         return int(self.lib.aliby_coloc3d_lds_voxels())
 
     def coloc3d(self, volume: torch.Tensor, pixels: torch.Tensor, pairs, counts, metrics=("pearson", "manders_fold", "rwc", "costes"),
-                thr: float = 15.0, scale_max: float = 255.0) -> torch.Tensor:
+                thr: float = 15.0, scale_max: float = 255.0, out=None, col0: int = 0) -> torch.Tensor:
         """Volume labels uint16 [F,Z,Y,X] (1..counts[f] per stack), pixels uint16 or float32 [F,C,Z,Y,X], pairs = [(c0, c1), ...]
         -> float64 [sum counts, 2 * len(metrics) * len(pairs)] (features.coloc3d_names(pairs, metrics); aliby_features_coloc3d):
         the 2-D colocalisation metrics over each object's voxels.  Rows in (stack, label) order, columns pair-major in the order
@@ -506,17 +520,18 @@ class FeatureEngine:
         if not (np.isfinite(thr) and np.isfinite(scale_max) and scale_max > 0):
             raise ValueError(f"thr must be finite and scale_max positive and finite, got {thr!r}, {scale_max!r}")
         col = {m: 2 * k for k, m in enumerate(metrics)}
-        return self._volume_block(int(offsets[-1]), len(names), ("coloc3d", lambda out: self.lib.aliby_features_coloc3d(
+        return self._volume_block(int(offsets[-1]), len(names), ("coloc3d", lambda out, c0: self.lib.aliby_features_coloc3d(
             self.ctx.handle, _ptr(volume.contiguous()), _ptr(pixels.contiguous()), self._pixel_code(pixels), F, Cn, Z, Y, X, _ptr(pr), len(pr),
-            _ptr(offsets), _ptr(out), out.stride(0), 0, 2 * len(metrics), col.get("pearson", -1), col.get("manders_fold", -1), col.get("rwc", -1),
-            col.get("costes", -1), thr, scale_max, _stream_ptr())))
+            _ptr(offsets), _ptr(out), out.stride(0), c0, 2 * len(metrics), col.get("pearson", -1), col.get("manders_fold", -1), col.get("rwc", -1),
+            col.get("costes", -1), thr, scale_max, _stream_ptr())), out=out, col0=col0)
 
     @property
     def texture3d_lds_voxels(self) -> int:
         """Largest bounding box, in voxels, that `texture3d` measures from LDS; larger boxes go through global scratch (same results)."""
         return int(self.lib.aliby_texture3d_lds_voxels())
 
-    def texture3d(self, volume: torch.Tensor, pixels: torch.Tensor, channel: int, counts, scale: int = 3, gray_levels: int = 256) -> torch.Tensor:
+    def texture3d(self, volume: torch.Tensor, pixels: torch.Tensor, channel: int, counts, scale: int = 3, gray_levels: int = 256, out=None,
+                  col0: int = 0) -> torch.Tensor:
         """Volume labels uint16 [F,Z,Y,X] (1..counts[f] per stack), pixels uint16 or float32 [F,C,Z,Y,X] -> float64 [sum counts, 169]
         (features.texture3d_names(scale, gray_levels); aliby_features_texture3d): the 13 Haralick statistics of the 2-D `texture`
         in 13 directions over each object's bounding box, direction-major.  Rows in (stack, label) order.  A direction without a
@@ -527,11 +542,11 @@ class FeatureEngine:
         if scale < 1 or not 2 <= gray_levels <= 256:
             raise ValueError(f"texture3d needs scale >= 1 and 2 <= gray_levels <= 256, got {scale}, {gray_levels}")
         cols = len(feat.texture3d_names(scale, gray_levels))
-        return self._volume_block(int(offsets[-1]), cols, ("texture3d", lambda out: self.lib.aliby_features_texture3d(
+        return self._volume_block(int(offsets[-1]), cols, ("texture3d", lambda out, c0: self.lib.aliby_features_texture3d(
             self.ctx.handle, _ptr(volume.contiguous()), _ptr(pixels.contiguous()), self._pixel_code(pixels), F, Cn, Z, Y, X, channel, _ptr(offsets),
-            scale, gray_levels, _ptr(out), out.stride(0), 0, _stream_ptr())))
+            scale, gray_levels, _ptr(out), out.stride(0), c0, _stream_ptr())), out=out, col0=col0)
 
-    def neighbors3d(self, volume: torch.Tensor, counts, distance=None) -> torch.Tensor:
+    def neighbors3d(self, volume: torch.Tensor, counts, distance=None, out=None, col0: int = 0) -> torch.Tensor:
         """Volume labels uint16 [F,Z,Y,X] (1..counts[f] per stack) -> float64 [sum counts, 7] (features.neighbors3d_names(distance);
         aliby_features_neighbors3d): the `neighbors` family on volumes — the number of objects within `distance` voxels, the share of
         the plane-by-plane outline in contact with them, the two closest objects of the stack by centre, and the angle between them.
@@ -545,8 +560,8 @@ class FeatureEngine:
         F, Z, Y, X = self._volume_labels("neighbors3d", volume)
         offsets = self._volume_offsets("neighbors3d", F, counts)
         centres = torch.empty((int(offsets[-1]), 3), dtype=torch.float64, device=volume.device)
-        return self._volume_block(int(offsets[-1]), 7, ("neighbors3d", lambda out: self.lib.aliby_features_neighbors3d(
-            self.ctx.handle, _ptr(volume.contiguous()), F, Z, Y, X, _ptr(offsets), d, _ptr(centres), _ptr(out), out.stride(0), 0, _stream_ptr())))
+        return self._volume_block(int(offsets[-1]), 7, ("neighbors3d", lambda out, c0: self.lib.aliby_features_neighbors3d(
+            self.ctx.handle, _ptr(volume.contiguous()), F, Z, Y, X, _ptr(offsets), d, _ptr(centres), _ptr(out), out.stride(0), c0, _stream_ptr())), out=out, col0=col0)
 
     @staticmethod
     def _granularity3d_shapes(Z: int, Y: int, X: int, subsample_size: float, image_sample_size: float):
@@ -556,7 +571,8 @@ class FeatureEngine:
         return sub, tuple(int(np.ceil(n * image_sample_size)) if image_sample_size < 1 else n for n in sub)
 
     def granularity3d(self, volume: torch.Tensor, pixels: torch.Tensor, channel: int, counts, subsample_size: float = 0.25,
-                      image_sample_size: float = 0.25, element_size: int = 10, granular_spectrum_length: int = 16) -> torch.Tensor:
+                      image_sample_size: float = 0.25, element_size: int = 10, granular_spectrum_length: int = 16, out=None,
+                      col0: int = 0) -> torch.Tensor:
         """Volume labels uint16 [F,Z,Y,X] (1..counts[f] per stack), pixels uint16 or float32 [F,C,Z,Y,X] -> float64 [sum counts, L]
         (features.granularity3d_names(L); aliby_features_granularity3d): the `granularity` family on volumes, CellProfiler
         MeasureGranularity's volumetric branch — each stack of `channel` subsampled trilinearly by `subsample_size`, its background
@@ -587,17 +603,34 @@ class FeatureEngine:
         rows = int(offsets[-1])
         sweeps = np.zeros(L, np.int32)
 
-        def launch(out):
+        def launch(out, c0):
             need = int(self.lib.aliby_granularity3d_workspace_bytes(F, Z, Y, X, rows, sizes[0], sizes[1]))
             work = torch.empty((need + 7) // 8, dtype=torch.float64, device=volume.device)
             return self.lib.aliby_features_granularity3d(
                 self.ctx.handle, _ptr(volume.contiguous()), _ptr(pixels.contiguous()), self._pixel_code(pixels), F, Cn, Z, Y, X, channel,
-                _ptr(offsets), sizes[0], sizes[1], element_size, L, _ptr(work), work.numel() * 8, _ptr(sweeps), _ptr(out), out.stride(0), 0,
+                _ptr(offsets), sizes[0], sizes[1], element_size, L, _ptr(work), work.numel() * 8, _ptr(sweeps), _ptr(out), out.stride(0), c0,
                 _stream_ptr())
 
-        out = self._volume_block(rows, len(names), ("granularity3d", launch))
+        block = self._volume_block(rows, len(names), ("granularity3d", launch), out=out, col0=col0)
         self.granularity3d_sweeps = sweeps.tolist()
-        return out
+        return block
+
+    def projection3d(self, volume: torch.Tensor, counts, out=None, col0: int = 0) -> torch.Tensor:
+        """Volume labels uint16 [F,Z,Y,X] (1..counts[f] per stack) -> float64 [sum counts, 4] (features.projection3d_names();
+        aliby_features_projection3d): how the collapse of the stack to 2-D — the maximum over z, then a sequential relabel
+        (`segment.model.max_project_and_relabel`, what a 3-D segment step returns) — sees each object.  With `top` the maximum over z
+        of a column (y, x): Projection_Area = columns holding a voxel of the object (a label that re-enters a column counts once),
+        Projection_VisibleArea = columns whose top it is, Projection_VisibleFraction = their float64 quotient, Projection_Label = the
+        object's label in the collapsed image (the rank of its value among the values that are top somewhere), 0 when it is hidden
+        everywhere.  Rows in (stack, label) order.  A value above counts[f] gets no row but occludes and counts in the rank; a
+        label of 1..counts[f] without voxels gets 0, 0, NaN, 0.  One read of the labels.  The counts and the per-stack presence
+        bits live in the context's scratch: a main-stream call, one in flight per context (the scratch rule,
+        csrc/object_launch.h).  Integers and one division: bitwise independent of run and batch."""
+        F, Z, Y, X = self._volume_labels("projection3d", volume)
+        offsets = self._volume_offsets("projection3d", F, counts)
+        return self._volume_block(int(offsets[-1]), 4, ("projection3d", lambda out, c0: self.lib.aliby_features_projection3d(
+            self.ctx.handle, _ptr(volume.contiguous()), F, Z, Y, X, _ptr(offsets), _ptr(out), out.stride(0), c0, _stream_ptr())),
+            out=out, col0=col0)
 
     def relabel_sequential(self, labels: torch.Tensor) -> np.ndarray:
         F, Y, X = labels.shape

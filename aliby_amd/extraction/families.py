@@ -8,6 +8,9 @@ registered raises KeyError, as `CELL_FUNS[metric]` does (extract.py:147-153).
 
 `evaluate` is `plan` (pure: no engine, table or tensor) followed by one executor for the single-channel and one for the
 channel-pair instructions; tests/test_cpu_feature_dispatch.py replays both on a recording engine.
+
+The volume families (label-keyed measurements of Z-stacks kept as volumes) have a registry, a planner and an evaluator of their own
+at the end of the module: `VOLUME`, `VOLUME_PAIRS`, `plan_volume`, `evaluate_volume` (tests/test_cpu_volume_tree.py).
 """
 
 from __future__ import annotations
@@ -437,3 +440,158 @@ def _run_mono(eng, labels, table, cache, out, fan, p):
     for s in p.steps:
         if s.family.after_join:
             s.family.launch(eng, labels, table, *_inputs(s, cache), out, s.col0, s.kw, cells)
+
+
+# ------------------------------------------------------------------------------------------------
+# volume families: label-keyed measurements of Z-stacks kept as volumes (FeatureEngine.*3d)
+# ------------------------------------------------------------------------------------------------
+# A volume tree has depth 3 throughout: {channel | "None" | (c0, c1): {"None": [names]}}.  The reducer key is always "None", ALIBY's
+# "do not reduce" (as under nuc_conv_3d): a volume family reads the un-reduced stack.  Pixel-free families go under "None", the
+# per-channel ones under their channel, the colocalisation names under a channel pair.  A column is "<key>/None/<name>/<column>".
+@dataclass(frozen=True)
+class VolumeFamily:  # one registered volume family; FeatureEngine's method of the same name measures it
+    names: Callable  # names(kw) -> the keys of its columns
+    needs_pixels: bool = True
+
+
+VOLUME = {
+    "intensity3d": VolumeFamily(lambda kw: feat.intensity3d_names()),
+    "intensity3d_detail": VolumeFamily(lambda kw: feat.intensity3d_detail_names(kw.get("edge_measurements", True))),
+    "texture3d": VolumeFamily(lambda kw: feat.texture3d_names(kw.get("scale", 3), kw.get("gray_levels", 256))),
+    "granularity3d": VolumeFamily(lambda kw: feat.granularity3d_names(kw.get("granular_spectrum_length", 16))),
+    "sizeshape3d": VolumeFamily(lambda kw: feat.sizeshape3d_names(kw.get("surface_area", False)), needs_pixels=False),
+    "neighbors3d": VolumeFamily(lambda kw: feat.neighbors3d_names(kw.get("distance")), needs_pixels=False),
+    "projection3d": VolumeFamily(lambda kw: feat.projection3d_names(), needs_pixels=False),
+}
+# the channel-pair names: groups of them become FeatureEngine.coloc3d calls
+VOLUME_PAIRS = {name: VolumeFamily(lambda kw, _n=name: list(feat.COLOC[_n])) for name in feat.COLOC}
+# per-name keywords of cp_measure_kwargs that the volume methods implement
+VOLUME_KWARGS = {
+    "sizeshape3d": ("spacing", "surface_area"),
+    "intensity3d_detail": ("edge_measurements",),
+    "texture3d": ("scale", "gray_levels"),
+    "granularity3d": ("subsample_size", "image_sample_size", "element_size", "granular_spectrum_length"),
+    "neighbors3d": ("distance",),
+    "manders_fold": ("thr",),
+    "rwc": ("thr",),
+    "costes": ("scale_max",),
+}
+COLOC3D_MAX_PAIRS = 64  # per FeatureEngine.coloc3d call
+
+
+@dataclass(frozen=True)
+class VolumeCall:
+    """One engine call of a volume plan: getattr(eng, method)(volume[, pixels, target], counts, **kw, out=matrix, col0=col0);
+    target = the channel, for coloc3d the list of channel pairs, None for a pixel-free family."""
+
+    method: str
+    target: object
+    kw: dict
+    col0: int
+    ncols: int
+
+
+@dataclass(frozen=True)
+class VolumePlan:
+    blocks: list  # per instruction (first column, names): the second return value of `evaluate_volume`
+    n_cols: int
+    calls: list   # in launch order: ascending col0
+
+
+def _is_channel(c) -> bool:
+    return isinstance(c, int) and not isinstance(c, bool) and c >= 0
+
+
+def plan_volume(instructions, cp_measure_kwargs) -> VolumePlan:
+    """What `evaluate_volume` will do for the instructions of a volume tree, and every refusal that depends on the names and keywords
+    alone.  Pure: no engine, no tensor.  Channel-pair metrics are grouped into coloc3d calls: consecutive metrics of a pair ride
+    together while their parameters agree (manders_fold's thr does not leak into rwc: metrics whose thresholds differ are separate
+    calls), and consecutive pairs that list the same metrics with the same parameters share one call."""
+    cp_measure_kwargs = cp_measure_kwargs or {}
+    blocks, calls = [], []
+    col = 0
+    group = None  # the open coloc3d group of the current pair: dict(pair, metrics, thr, scale_max, col0)
+
+    def close():
+        nonlocal group
+        if group is None:
+            return
+        kw = dict(metrics=tuple(group["metrics"]), thr=15.0 if group["thr"] is None else group["thr"],
+                  scale_max=255.0 if group["scale_max"] is None else group["scale_max"])
+        ncols = 2 * len(group["metrics"])
+        last = calls[-1] if calls else None
+        if (last is not None and last.method == "coloc3d" and last.kw == kw and last.col0 + last.ncols == group["col0"]
+                and len(last.target) < COLOC3D_MAX_PAIRS and group["pair"] not in last.target):
+            calls[-1] = replace(last, target=[*last.target, group["pair"]], ncols=last.ncols + ncols)
+        else:
+            calls.append(VolumeCall("coloc3d", [group["pair"]], kw, group["col0"], ncols))
+        group = None
+
+    for inst in instructions:
+        if len(inst) != 3:
+            raise ValueError(f"a volume tree has depth 3, {{channel | 'None' | (c0, c1): {{'None': [names]}}}}, got the path {inst!r}")
+        key, reducer, name = inst
+        if name not in VOLUME and name not in VOLUME_PAIRS:
+            raise KeyError(name)
+        if reducer != "None":
+            raise ValueError(f"{name}: a volume family reads the un-reduced stack: the reducer key must be 'None', got {reducer!r}")
+        kw = dict(cp_measure_kwargs.get(name, {}))
+        unbuilt = sorted(set(kw) - set(VOLUME_KWARGS.get(name, ())))
+        if unbuilt:
+            raise NotImplementedError(f"cp_measure_kwargs[{name!r}]: {unbuilt} not built (built: {sorted(VOLUME_KWARGS.get(name, ()))})")
+        if isinstance(key, tuple):
+            if len(key) != 2 or not all(_is_channel(c) for c in key) or key[0] == key[1]:
+                raise ValueError(f"{name}: a channel-pair key is two distinct channels (c0, c1), got {key!r}")
+            if name not in VOLUME_PAIRS:
+                raise ValueError(f"{name} measures one channel (or none): list it under a channel or 'None', not under the pair {key!r}")
+            names = VOLUME_PAIRS[name].names(kw)
+            thr = float(kw["thr"]) if "thr" in kw else (15.0 if name in ("manders_fold", "rwc") else None)
+            scale_max = float(kw["scale_max"]) if "scale_max" in kw else (255.0 if name == "costes" else None)
+            fits = (group is not None and group["pair"] == key and name not in group["metrics"]
+                    and (thr is None or group["thr"] in (None, thr)) and (scale_max is None or group["scale_max"] in (None, scale_max)))
+            if not fits:
+                close()
+                group = dict(pair=key, metrics=[], thr=None, scale_max=None, col0=col)
+            group["metrics"].append(name)
+            group["thr"] = group["thr"] if thr is None else thr
+            group["scale_max"] = group["scale_max"] if scale_max is None else scale_max
+        else:
+            close()
+            if name in VOLUME_PAIRS:
+                raise ValueError(f"{name} measures a channel pair: list it under a key (c0, c1), not under {key!r}")
+            fam = VOLUME[name]
+            if key == "None" and not isinstance(key, int):
+                if fam.needs_pixels:
+                    raise ValueError(f"{name} needs the pixels of a channel: list it under a channel, not under 'None'")
+                target = None
+            elif _is_channel(key):
+                if not fam.needs_pixels:
+                    raise ValueError(f"{name} reads labels only: list it under 'None', not under channel {key!r}")
+                target = key
+            else:
+                raise ValueError(f"{name}: a volume tree's key is a channel, 'None' or a channel pair, got {key!r}")
+            names = fam.names(kw)
+            calls.append(VolumeCall(name, target, kw, col, len(names)))
+        blocks.append((col, names))
+        col += len(names)
+    close()
+    return VolumePlan(blocks, col, calls)
+
+
+def evaluate_volume(eng, volume, pixels, counts, instructions, cp_measure_kwargs):
+    """Run every instruction of a volume tree over every object of volume labels uint16 [F,Z,Y,X] with counts [F] objects per stack
+    (pixels [F,C,Z,Y,X] on the device, or None for a pixel-free tree); returns (matrix [sum counts, n_cols] on the device, blocks).
+    One matrix; every call writes its block in place, one after the other on the main stream: several volume families borrow the
+    context's scratch, so there is no fan-out to side streams."""
+    p = plan_volume(instructions, cp_measure_kwargs)
+    rows = sum(int(c) for c in counts)
+    out = eng.new_output(rows, p.n_cols)
+    for call in p.calls:
+        method = getattr(eng, call.method)
+        if call.target is None:
+            method(volume, counts, **call.kw, out=out, col0=call.col0)
+        else:
+            if pixels is None:
+                raise Exception(f"pixels are required for {call.method}")
+            method(volume, pixels, call.target, counts, **call.kw, out=out, col0=call.col0)
+    return out, p.blocks

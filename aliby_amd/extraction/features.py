@@ -203,6 +203,21 @@ def family_names(family: str, **kw) -> list[str]:
         return neighbors_names(kw.get("distance"))
     if family in COLOC:
         return list(COLOC[family])
+    # the volume families (extraction.families.VOLUME)
+    if family == "intensity3d":
+        return intensity3d_names()
+    if family == "intensity3d_detail":
+        return intensity3d_detail_names(kw.get("edge_measurements", True))
+    if family == "sizeshape3d":
+        return sizeshape3d_names(kw.get("surface_area", False))
+    if family == "texture3d":
+        return texture3d_names(kw.get("scale", 3), kw.get("gray_levels", 256))
+    if family == "neighbors3d":
+        return neighbors3d_names(kw.get("distance"))
+    if family == "granularity3d":
+        return granularity3d_names(kw.get("granular_spectrum_length", 16))
+    if family == "projection3d":
+        return projection3d_names()
     raise KeyError(family)
 
 
@@ -295,3 +310,13 @@ def granularity3d_names(granular_spectrum_length: int = 16) -> list[str]:
     if not 1 <= int(granular_spectrum_length) <= GRANULARITY3D_MAX_LENGTH:
         raise ValueError(f"granularity3d: granular_spectrum_length must lie in 1..{GRANULARITY3D_MAX_LENGTH}, got {granular_spectrum_length!r}")
     return granularity_names(int(granular_spectrum_length))
+
+
+def projection3d_names() -> list[str]:
+    """Columns of `FeatureEngine.projection3d` (csrc/feat_projection3d.hip): how the collapse of a 3-D label result (the maximum over
+    z, then a sequential relabel: `segment.model.max_project_and_relabel`) sees each volume object.  With `top` the maximum over z
+    of a column (y, x): Projection_Area, the columns that hold a voxel of the object; Projection_VisibleArea, those whose top it
+    is; Projection_VisibleFraction, their quotient (NaN without voxels); Projection_Label, the label the object carries in the
+    collapsed image — the join key to the rows measured on the collapse — or 0 when it is hidden under other objects everywhere.
+    The definition is in include/aliby_hip.h, restated in tests/projection3d_ref.py."""
+    return ["Projection_Area", "Projection_VisibleArea", "Projection_VisibleFraction", "Projection_Label"]

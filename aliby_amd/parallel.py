@@ -77,8 +77,22 @@ def barrier():
         dist.barrier()
 
 
+def refuse_volume_pipelines(pipelines) -> None:
+    """The batched runner has no volume form: its segmenter entry (`segment.batch`) is 2-D and it knows no `volume_` step.  A
+    pipeline that asks for either is refused up front, before any position is read."""
+    for pipeline in pipelines:
+        steps = pipeline.get("steps", {}) if isinstance(pipeline, dict) else {}
+        for name, params in steps.items():
+            kwargs = params.get("segmenter_kwargs", {}) if isinstance(params, dict) else {}
+            if name.startswith("volume_") or (name.startswith("segment") and isinstance(kwargs, dict) and "do_3D" in kwargs):
+                raise NotImplementedError(f"run_positions has no volume form (step '{name}': a 'volume_' step, or 'do_3D' in a "
+                                          "segmenter's kwargs): run such a pipeline position by position with "
+                                          "aliby_amd.pipe.run_pipeline_and_post")
+
+
 def run_positions(pipelines, names, output_path, **kwargs):
     """Many positions behind the step API, B per device step, sharded i % world == rank: see aliby_amd/runner.py."""
+    refuse_volume_pipelines(pipelines)
     from aliby_amd.runner import run_positions as _run
 
     return _run(pipelines, names, output_path, **kwargs)

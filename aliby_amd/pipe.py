@@ -37,6 +37,9 @@ _PREFIXES = (
     ("track", _tracker),
     ("extract_", lambda name, params, done: core._init_extract(name, params, overlap=False)),
     ("extractmulti_", lambda name, params, done: core._init_extract_multi(name, params)),
+    # (not an "extract" prefix: every step that starts with "extract" is joined to the 2-D rows on metadata_label, which would pair
+    # volume label k with 2-D label k; the volume rows get their own table, profiles3d/)
+    ("volume_", lambda name, params, done: core._init_volume(name, params, done)),
     ("nahual_embed", lambda name, params, done: core._init_nahual(name, params)),
     ("nahual_track", lambda name, params, done: core._init_nahual(name, params)),
 )

@@ -39,7 +39,17 @@ def build_pipeline_steps(
     trackastra_address: str | None = None,
     trackastra_parameters: dict | None = None,
     cp_measure_feature_kwargs: dict[str, dict] | None = None,
+    *,
+    volume_features: Sequence[str] | None = None,
+    volume_coloc: bool = False,
 ) -> dict:
+    """Extension (not in the reference): `volume_features`, a sequence of per-channel volume family names
+    (extraction.families.VOLUME: "intensity3d", "intensity3d_detail", "texture3d", "granularity3d"), makes every segment step
+    segment Z-stacks as volumes (`do_3D=True`) and adds a `volume_<obj>` step per object set: sizeshape3d and projection3d, the
+    given names under every channel of `channels_to_extract`, and with `volume_coloc=True` COLOC_METRICS under every channel
+    pair.  Its rows go to profiles3d/<name>.parquet; the extract steps stay and measure the collapse, so profiles/ is the
+    reference-faithful table and profiles3d/ the true 3-D one, joined on (metadata_tp, metadata_tile, metadata_object,
+    Projection_Label = metadata_label).  With the default None the dict is the reference's."""
     if channels_to_segment is None:
         channels_to_segment = {"nuclei": 1, "cell": 0}
     kind = "cellpose" if nahual_addresses is None else "nahual_cellpose"
@@ -74,6 +84,18 @@ def build_pipeline_steps(
         "save": [f"segment_{obj}" for obj in objects],
         "save_interval": 1,
     }
+    if volume_features is not None:
+        tree = {"None": {"None": ["sizeshape3d", "projection3d"]}}
+        for ch in channels_to_extract:
+            tree[ch] = {"None": list(volume_features)}
+        if volume_coloc:
+            for pair in combinations(channels_to_extract, r=2):
+                tree[pair] = {"None": list(COLOC_METRICS)}
+        for obj in objects:
+            steps[f"segment_{obj}"]["segmenter_kwargs"]["do_3D"] = True
+            steps[f"volume_{obj}"] = {"tree": tree, "volume_from": f"segment_{obj}",
+                                      "kwargs": _step_kwargs(extract_ncores, cp_measure_feature_kwargs)}
+            pipeline["passed_data"][f"volume_{obj}"] = [("pixels", "tile")]
     if steps_to_write is not None:
         pipeline["save"] = list(steps_to_write)
     if trackastra_address is not None:

@@ -32,6 +32,7 @@ from aliby_amd.extraction.extract import (
     format_extraction,
     process_tree_masks,
     process_tree_masks_overlap,
+    process_tree_volumes,
 )
 from aliby_amd.io.write import dispatch_write_fn, write_profiles
 from aliby_amd.tile.tiler import dispatch_image, dispatch_tiler
@@ -81,6 +82,38 @@ def _init_extract(step_name: str, parameters: dict, *, overlap: bool) -> Callabl
 def _init_extract_multi(step_name: str, parameters: dict) -> Callable:
     tree = _need(parameters, "tree", step_name)
     return partial(process_tree_masks, measure_fn=extract_tree_multi, tree=tree, **parameters.get("kwargs", {}))
+
+
+def _init_volume(step_name: str, parameters: dict, other_steps: dict) -> Callable:
+    """A `volume_<obj>` step: the volume families of `tree` (extraction.families.VOLUME / VOLUME_PAIRS) over the volume labels the
+    segment step named by `volume_from` kept on the device (`segment.last_volume`, a 3-D segmentation: `do_3D` in its
+    segmenter_kwargs), with the tile's pixels.  `kwargs`: cp_measure_kwargs, ncores.  Its rows are keyed by the VOLUME label and go
+    to their own table (get_volume_profiles_from_state), never into the join of the extract steps."""
+    from aliby_amd.extraction import families
+    from aliby_amd.extraction.extract import flatten, kv
+
+    tree = _need(parameters, "tree", step_name)
+    source = _need(parameters, "volume_from", step_name)
+    if not isinstance(source, str) or not source.startswith("segment"):
+        raise ValueError(f"Step '{step_name}': 'volume_from' must name a segment step, got {source!r}.")
+    extra = dict(parameters.get("kwargs", {}))
+    families.plan_volume(kv(flatten(tree)), extra.get("cp_measure_kwargs"))  # a tree or keyword that is refused fails here, not at tp 0
+
+    def volume_step(pixels):
+        segment = other_steps.get(source)
+        if segment is None or not hasattr(segment, "last_volume"):
+            raise ValueError(f"Step '{step_name}': 'volume_from' = '{source}' is not a segment step that ran before this one.")
+        if segment.last_volume is None:
+            raise ValueError(f"Step '{step_name}': '{source}' kept no volume labels: it ran without do_3D (set 'do_3D': True in its "
+                             "segmenter_kwargs), or the stack has a single plane.")
+        volume, counts = segment.last_volume
+        shape = tuple(pixels.shape)
+        if len(shape) != 5 or tuple(volume.shape) != (shape[0], *shape[2:]):
+            raise ValueError(f"Step '{step_name}': the volume labels of '{source}' are {tuple(volume.shape)} [F,Z,Y,X], the pixels "
+                             f"{shape} [F,C,Z,Y,X]: they do not match.")
+        return process_tree_volumes(tree, volume, pixels, counts=counts, **extra)
+
+    return volume_step
 
 
 def _init_nahual(step_name: str, parameters: dict) -> Callable:
@@ -268,7 +301,8 @@ DEVICE_LOCK = threading.RLock()
 def _run_pipeline_and_post_impl(pipeline: dict, pipeline_name: str, output_path, overwrite: bool = True, *,
                                 init_step_fn: Callable, post_state_hook: Callable | None = None):
     """One position: `profiles/<name>.parquet` (zstd), `steps/<name>/...`; an existing parquet is skipped
-    unless `overwrite` (resume-by-skip)."""
+    unless `overwrite` (resume-by-skip).  A pipeline with a `volume_` step also gets `profiles3d/<name>.parquet`, returned as
+    `(profiles, {"profiles3d": table})`; without one the files and the return value `(profiles, {})` are the reference's."""
     output_path = Path(output_path)
     profiles_file = output_path / "profiles" / f"{pipeline_name}.parquet"
     validate_pipeline(pipeline)  # before the resume check: a bad / out-of-scope dict fails the same way on every run
@@ -291,9 +325,17 @@ def _run_pipeline_and_post_impl(pipeline: dict, pipeline_name: str, output_path,
         profiles = get_profiles_from_state(state, pipeline)
         profiles_file.parent.mkdir(parents=True, exist_ok=True)
         write_profiles(profiles, profiles_file)
+        extras = {}
+        if any(name.startswith("volume_") for name in pipeline["steps"]):
+            # the true 3-D rows, beside the reference-faithful ones of the collapse: they join on (metadata_tp, metadata_tile,
+            # metadata_object, Projection_Label = metadata_label)
+            extras["profiles3d"] = get_volume_profiles_from_state(state, pipeline)
+            volume_file = output_path / "profiles3d" / f"{pipeline_name}.parquet"
+            volume_file.parent.mkdir(parents=True, exist_ok=True)
+            write_profiles(extras["profiles3d"], volume_file)
         if post_state_hook is not None:
             post_state_hook(state, pipeline, output_path, pipeline_name)
-        return profiles, {}
+        return profiles, extras
     finally:
         if frozen:
             gc.unfreeze()
@@ -338,6 +380,21 @@ def get_profiles_from_state(state: dict, pipeline: dict) -> pa.Table:
     for other in merged[1:]:
         profiles = _join_on_metadata(profiles, other)
     return profiles
+
+
+def get_volume_profiles_from_state(state: dict, pipeline: dict) -> pa.Table:
+    """One wide table per (`volume_` step, tp), concatenated: the metadata columns of `get_profiles_from_state`, with
+    `metadata_label` the VOLUME label.  Kept apart from the extract steps' table, whose labels are those of the collapsed image;
+    `<key>/None/projection3d/Projection_Label` is the row's label there (0: hidden in the collapse)."""
+    tables = []
+    for name in pipeline["steps"]:
+        if not name.startswith("volume_"):
+            continue
+        for tp, output in enumerate(state["data"][name]):
+            table = _wide_table(name, tp, output)
+            if table is not None:
+                tables.append(table)
+    return pa.concat_tables(tables) if tables else _empty_profiles()
 
 
 def _join_on_metadata(left: pa.Table, right: pa.Table, strict: bool = False) -> pa.Table:

@@ -850,6 +850,7 @@ def run_positions(pipelines, names, output_path, overwrite: bool = True, batch_s
             from aliby_amd.pipe import init_step as init_step_fn
         if len(pipelines) != len(names):
             raise ValueError("pipelines and names must have the same length")
+        parallel.refuse_volume_pipelines(pipelines)
         if len(set(names)) != len(names):  # (two positions of one name would write the same files from two writer threads)
             dup = sorted({n for n in names if list(names).count(n) > 1})[:5]
             raise ValueError(f"position names must be unique, got {dup} more than once")

@@ -89,6 +89,9 @@ def dispatch_segmenter(kind: str, channel_to_segment: int, address: str = None, 
         raise ValueError(f"volume_mode={volume_mode!r}: expected 'stitch' or 'flows3d'")
     if per_tile and volume_mode == "flows3d":
         raise ValueError("per_tile=True takes 2-D tiles; volume_mode='flows3d' segments Z-stacks as volumes")
+    # Extension: a `do_3D` entry of the segmenter's kwargs is the default of segment's `do_3D` argument: what a pipeline dict can
+    # set, since the engine calls segment(pixels, **passed_data) (pipe_builder's volume_features does).
+    default_3d = bool(kwargs.get("do_3D", False))
     setup_params = dict(kwargs.get("setup_params", {}))
     gpu = setup_params.pop("gpu", True)
     device = setup_params.pop("device", None)
@@ -153,8 +156,10 @@ def dispatch_segmenter(kind: str, channel_to_segment: int, address: str = None, 
             return devcache.attach(host_stack[0], labels_dev, kind="labels", ready=ready, max_label=n_labels)
         return devcache.attach(labels_dev.cpu().numpy(), labels_dev, kind="labels", max_label=n_labels)
 
-    def segment(pixels, do_3D: bool = False, stitch_threshold=None, **kw):
-        """Assumes FCZYX pixels.  Returns uint16 labels [Y,X] (monotile), as the reference does."""
+    def segment(pixels, do_3D: bool = default_3d, stitch_threshold=None, **kw):
+        """Assumes FCZYX pixels.  Returns uint16 labels [Y,X] (monotile), as the reference does.  `segment.last_volume` is the
+        (volume labels, counts) of this call when it segmented a volume, None when it took the 2-D path."""
+        segment.last_volume = None
         z_size = pixels.shape[2]
         if pixels.ndim > 5:
             pixels = pixels[0]
@@ -242,4 +247,6 @@ def dispatch_segmenter(kind: str, channel_to_segment: int, address: str = None, 
     segment.channel_to_segment = channel_to_segment
     segment.per_tile = per_tile
     segment.volume_mode = volume_mode
+    segment.do_3D = default_3d
+    segment.last_volume = None
     return segment

@@ -771,6 +771,24 @@ int aliby_features_granularity3d(aliby_ctx* ctx, const uint16_t* labels, const v
                                  int channel, const int32_t* offsets_host, double subsample_size, double image_sample_size,
                                  int element_size, int spectrum_length, void* workspace, size_t workspace_bytes, int32_t* sweeps_host,
                                  double* out, int ld, int col0, void* stream);
+/* "projection3d": how the collapse of a 3-D label result to 2-D (the maximum over z, then a sequential relabel: the reference's
+ * segment/dispatch.py:218-223) sees each object of the same labelled stacks.  For a column (f, y, x), `top` is the maximum of the
+ * values labels[f, z, y, x] over z.  Four columns at out[row * ld + col0 ..], row = offsets_host[f] + L - 1:
+ *   0 Projection_Area: the number of columns (y, x) of stack f that hold at least one voxel of L.  A label that enters a column
+ *     twice, with another value or background in between, counts once.
+ *   1 Projection_VisibleArea: the number of columns whose top is L.
+ *   2 Projection_VisibleFraction: double(VisibleArea) / double(Area), one float64 division; NaN when Area is 0.
+ *   3 Projection_Label: the value the object carries in the collapsed image: the 1-based rank of L among the distinct non-zero
+ *     values that are the top of some column of the stack; 0 when L is the top of no column (hidden).
+ * A value above n_f gets no row, but it occludes what lies under it and counts in the rank, so Projection_Label is always the value
+ * in the collapsed image.  A label of 1..n_f without voxels gets 0, 0, NaN, 0.  Everything but the division is an integer: results
+ * are bitwise independent of the run, of the other stacks of the call and of the batch.  Worked example, a stack [2, 1, 4]
+ * (z, y, x) with n = 3: z 0 = (1, 1, 3, 0), z 1 = (2, 0, 3, 7): tops 2, 1, 3, 7, ranks 1 -> 1, 2 -> 2, 3 -> 3, 7 -> 4; rows
+ * (2, 1, 0.5, 1), (1, 1, 1, 2), (1, 1, 1, 3).  The counts and one presence bit per value and stack live in the context's scratch, so
+ * this is a main-stream call: one in flight per context (the scratch rule, csrc/object_launch.h); it waits for `stream` before it
+ * returns.  offsets_host[F] == 0 launches nothing.  Y * X < 2^32.  Kernels: csrc/feat_projection3d.hip. */
+int aliby_features_projection3d(aliby_ctx* ctx, const uint16_t* labels, int F, int Z, int Y, int X, const int32_t* offsets_host,
+                                double* out, int ld, int col0, void* stream);
 
 /* ---- a17: the step API's files, encoded natively (host code, no GPU work) ------------------ */
 /* profiles/<name>.parquet — pyarrow.parquet.write_table(profiles, path, compression="zstd")
