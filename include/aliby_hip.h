@@ -532,7 +532,8 @@ int aliby_features_trap_background(aliby_ctx* ctx, const uint16_t* labels, const
  * original pixels.  image_mask_objects = 0: the image mask is the frame (CellProfiler's default); 1: labels > 0, sampled
  * bilinearly.  The image-level part runs once per (tile, channel), float64.  `workspace` is device memory of at least
  * aliby_granularity_workspace_bytes(); the call synchronises `stream` while it iterates the reconstruction to its fixed
- * point.  PARITY UNPINNED (oracle/granularity_restated.py; cp_measure is not available offline). */
+ * point.  PARITY UNPINNED (oracle/granularity_restated.py; cp_measure is not available offline).  Kernels:
+ * csrc/granularity_pass.h (shared with granularity3d), csrc/feat_granularity.hip. */
 size_t aliby_granularity_workspace_bytes(int F, int Y, int X, int n_obj, double subsample_size, double image_sample_size);
 int aliby_features_granularity(aliby_ctx* ctx, const uint16_t* labels, const void* planes, int dtype, int F, int C, int Y,
                                int X, int channel, const aliby_object* table_dev, int n_obj, double subsample_size,
@@ -765,7 +766,8 @@ int aliby_features_neighbors3d(aliby_ctx* ctx, const uint16_t* labels, int F, in
  * converged after sz * sh * sw / 2 + 64 sweeps is ALIBY_ERR_TOO_LARGE, never a result.  sweeps_host (may be NULL) [spectrum_length]
  * receives the sweeps each step ran (a multiple of 16; flag reads = sweeps / 16).  offsets_host[F] == 0 launches nothing.  Per-object
  * means: one wave per row over the row's bounding box in a fixed lane and reduction order, so results are bitwise independent of the
- * run, of the other stacks of the call and of the batch.  Kernels: csrc/feat_granularity3d.hip. */
+ * run, of the other stacks of the call and of the batch.  Kernels: csrc/granularity_pass.h (shared with
+ * granularity), csrc/feat_granularity3d.hip. */
 size_t aliby_granularity3d_workspace_bytes(int F, int Z, int Y, int X, int rows, double subsample_size, double image_sample_size);
 int aliby_features_granularity3d(aliby_ctx* ctx, const uint16_t* labels, const void* pixels, int dtype, int F, int C, int Z, int Y, int X,
                                  int channel, const int32_t* offsets_host, double subsample_size, double image_sample_size,
