@@ -16,7 +16,13 @@
 // is channel independent and writes one code byte per object pixel into a tile-shaped map
 // (0x80 | wedge<<4 | ring); the statistics kernel then streams labels + map + one pixel plane per
 // (object, channel).  Path lengths are kept as exact (edge steps, diagonal steps) integer pairs packed
-// in one 32-bit LDS word, so the relaxation is race-free and bit-reproducible.
+// in one 32-bit LDS word, so the relaxation is race-free and bit-reproducible.  It sweeps until nothing
+// changes: a winding object (a serpentine, a spiral) has paths of about area / 2 steps, far more than its
+// box suggests.  Pixels that no path inside the object reaches from the centre (a second component) get
+// code 0 and count in no ring.  16 bits per counter hold every path of an object of up to 65536 pixels;
+// a larger one whose path would need more gets code 0 on every pixel, and the statistics kernel then
+// writes NaN in all its columns.
+#include <type_traits>
 #include "common.h"
 #include "object_launch.h"
 
@@ -45,7 +51,7 @@ template <bool GLOBAL>
 __global__ __launch_bounds__(256) void k_radial_geometry(RadialGeoArgs a) {
   extern __shared__ __align__(16) unsigned char lds_raw[];
   __shared__ int red_i[8];
-  __shared__ int s_changed;
+  __shared__ int s_changed, s_overflow;
   unsigned char* ws = GLOBAL ? (a.gscratch + (size_t)blockIdx.x * a.cap_cells * 8) : lds_raw;
   int* d2 = reinterpret_cast<int*>(ws);                                   // squared distance to edge (padded grid)
   unsigned int* aux = reinterpret_cast<unsigned int*>(ws + a.cap_cells * 4);  // g (phase 1) then packed path
@@ -107,40 +113,53 @@ __global__ __launch_bounds__(256) void k_radial_geometry(RadialGeoArgs a) {
     const int ci = CIDX / w, cj = CIDX % w;  // bbox-local centre
     __syncthreads();
     // ---- geodesic relaxation from the centre -------------------------------------------------------
+    // Sweeps until one changes nothing.  A sweep carries a path about one step further, and a path has up to
+    // area - 1 steps (a serpentine fills half its box with ONE path), so no bound taken from the box holds:
+    // h * w + 1 sweeps are never reached and only guard against a hang.
+    // A word always holds the steps of a path that visits no pixel twice (words only decrease), so each counter is
+    // at most area - 1 and fits 16 bits while area <= 65536; a larger object checks every step, and one whose
+    // counter would pass 0xFFFF (0xFFFE diagonal steps: 0xFFFFFFFF means "not reached") gets no code at all.
     for (int i = tid; i < ph * pw; i += blockDim.x) aux[i] = 0xFFFFFFFFu;
     __syncthreads();
-    if (tid == 0) aux[(ci + 1) * pw + cj + 1] = 0u;
+    if (tid == 0) { aux[(ci + 1) * pw + cj + 1] = 0u; s_overflow = 0; }
     __syncthreads();
-    for (int sweep = 0; sweep < 4 * (h + w) + 8; ++sweep) {
-      if (tid == 0) s_changed = 0;
-      __syncthreads();
-      int changed = 0;
-      for (int i = tid; i < h * w; i += blockDim.x) {
-        const int r = i / w + 1, c = i % w + 1;
-        if (d2[r * pw + c] < 0) continue;
-        unsigned int cur = aux[r * pw + c];
-        double cc = (cur == 0xFFFFFFFFu) ? 1e300 : path_cost(cur);
+    auto relax = [&](auto checked) {  // checked: whether a step looks at the counter it is about to raise
+      constexpr bool CHECKED = decltype(checked)::value;
+      for (int sweep = 0; sweep < h * w + 1; ++sweep) {
+        if (tid == 0) s_changed = 0;
+        __syncthreads();
+        int changed = 0, overflow = 0;
+        for (int i = tid; i < h * w; i += blockDim.x) {
+          const int r = i / w + 1, c = i % w + 1;
+          if (d2[r * pw + c] < 0) continue;
+          unsigned int cur = aux[r * pw + c];
+          double cc = (cur == 0xFFFFFFFFu) ? 1e300 : path_cost(cur);
 #pragma unroll
-        for (int dr = -1; dr <= 1; ++dr)
+          for (int dr = -1; dr <= 1; ++dr)
 #pragma unroll
-          for (int dc = -1; dc <= 1; ++dc) {
-            if (dr == 0 && dc == 0) continue;
-            const int rr = r + dr, c2 = c + dc;
-            if (d2[rr * pw + c2] < 0) continue;
-            const unsigned int nb = aux[rr * pw + c2];
-            if (nb == 0xFFFFFFFFu) continue;
-            const unsigned int cand = (dr != 0 && dc != 0) ? nb + 0x10000u : nb + 1u;
-            const double cv = path_cost(cand);
-            if (cv < cc) { cc = cv; cur = cand; }
-          }
-        if (cur != aux[r * pw + c]) { aux[r * pw + c] = cur; changed = 1; }
+            for (int dc = -1; dc <= 1; ++dc) {
+              if (dr == 0 && dc == 0) continue;
+              const int rr = r + dr, c2 = c + dc;
+              if (d2[rr * pw + c2] < 0) continue;
+              const unsigned int nb = aux[rr * pw + c2];
+              if (nb == 0xFFFFFFFFu) continue;
+              if (CHECKED && ((dr != 0 && dc != 0) ? (nb >> 16) >= 0xFFFEu : (nb & 0xFFFFu) == 0xFFFFu)) { overflow = 1; continue; }
+              const unsigned int cand = (dr != 0 && dc != 0) ? nb + 0x10000u : nb + 1u;
+              const double cv = path_cost(cand);
+              if (cv < cc) { cc = cv; cur = cand; }
+            }
+          if (cur != aux[r * pw + c]) { aux[r * pw + c] = cur; changed = 1; }
+        }
+        if (changed) s_changed = 1;
+        if (CHECKED && overflow) s_overflow = 1;
+        __syncthreads();
+        const int any = s_changed;
+        __syncthreads();
+        if (!any) break;
       }
-      if (changed) s_changed = 1;
-      __syncthreads();
-      const int any = s_changed;
-      __syncthreads();
-      if (!any) break;
-    }
+    };
+    if (o.area > 0x10000) relax(std::true_type{}); else relax(std::false_type{});
+    const bool coded = s_overflow == 0;  // (read behind the loop's last barrier; the next write is behind two more)
     // ---- ring / wedge code per object pixel -------------------------------------------------------
     for (int i = tid; i < h * w; i += blockDim.x) {
       const int r = i / w, c = i % w;
@@ -148,7 +167,7 @@ __global__ __launch_bounds__(256) void k_radial_geometry(RadialGeoArgs a) {
       if (dd < 0) continue;
       const unsigned int pth = aux[(r + 1) * pw + c + 1];
       unsigned char code = 0;
-      if (pth != 0xFFFFFFFFu) {
+      if (pth != 0xFFFFFFFFu && coded) {
         const double dfrom = path_cost(pth), dedge = sqrt((double)dd);
         // scaled rings (the default): distance from the centre as a fraction of centre-to-edge; unscaled: in units of
         // maximum_radius pixels, everything beyond it in the overflow ring `bin_count`
@@ -224,7 +243,7 @@ __global__ __launch_bounds__(256) void k_radial_stats(RadialStatArgs a) {
       double m8[8];
       for (int k = 0; k < 8; ++k)
         if (wcnt[tid][k] > 0) { m8[nw] = wsum[tid][k] / (double)wcnt[tid][k]; mean += m8[nw]; ++nw; }
-      double cv = 0.0;
+      double cv = N_ > 0 ? 0.0 : NAN;  // no coded pixel: the geometry gave the object up, every column is NaN (fd = 0 / 0)
       if (nw > 0) {
         mean /= (double)nw;
         double var = 0;
@@ -255,7 +274,9 @@ int aliby_radial_geometry_unscaled(aliby_ctx* ctx, const uint16_t* labels, int F
   ARG_CHECK(labels && table_dev && binmap_dev, "NULL argument");
   ARG_CHECK(F > 0 && Y > 0 && X > 0 && max_h >= 0 && max_w >= 0, "bad shape");
   ARG_CHECK(bin_count >= 1 && bin_count < RD_MAXBINS, "1 <= bin_count < 16");
-  ARG_CHECK(max_h + max_w < 16000, "object too large for 16-bit path counters");
+  // (the padded box is indexed with int and its squared distances stay below BIG = 2^28; the 16-bit path counters are the
+  // kernel's own concern: they count steps, which the object's area bounds and its box does not)
+  ARG_CHECK((long long)(max_h + 2) * (max_w + 2) < (1LL << 28), "object box too large");
   RadialGeoArgs a;
   a.labels = labels; a.F = F; a.Y = Y; a.X = X; a.tab = table_dev; a.n_obj = n_obj; a.bin_count = bin_count;
   a.max_radius = maximum_radius;

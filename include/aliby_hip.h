@@ -436,7 +436,9 @@ int aliby_features_texture(aliby_ctx* ctx, const uint16_t* labels, const void* p
 
 /* cp_measure "radial_distribution" (scaled rings, centre = the object itself), two steps:
  *  1. aliby_radial_geometry: channel-independent ring/wedge code of every object pixel, written into
- *     binmap_dev [F,Y,X] (0x80 | wedge<<4 | ring; 0 = not reached from the centre);
+ *     binmap_dev [F,Y,X] (0x80 | wedge<<4 | ring; 0 = not reached from the centre).  Paths are followed however far
+ *     they wind; an object of more than 65536 pixels with a path of more than 65535 edge or 65534 diagonal steps gets
+ *     0 on every pixel, and step 2 then writes NaN in all its columns;
  *  2. aliby_features_radial_distribution: per channel, 3*bin_count columns
  *     FracAtD_1..n, MeanFrac_1..n, RadialCV_1..n. */
 int aliby_radial_geometry(aliby_ctx* ctx, const uint16_t* labels, int F, int Y, int X,

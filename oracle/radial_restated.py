@@ -68,6 +68,34 @@ def names(bin_count=4, scaled=True):
     return out
 
 
+def object_geometry(labels, lab, scaled=True, bin_count=4, maximum_radius=100):
+    """The per-pixel part of one object: -> (bounding-box slices, mask, reached pixels, ring per pixel, wedge per pixel, centre),
+    all on the bounding box; None where the label is absent."""
+    full = labels == lab
+    if not full.any():
+        return None
+    d_edge_full = distance_to_edge_object(full)
+    sl = ndi.find_objects(full.astype(np.int32))[0]
+    m = full[sl]
+    d_edge = d_edge_full[sl]
+    # centre: maximum of d_to_edge, last raster occurrence among ties
+    flat = np.where(m.ravel(), d_edge.ravel(), -1.0)
+    order = np.argsort(flat, kind="stable")
+    ci, cj = np.unravel_index(order[-1], m.shape)
+    d_from = propagate_from(m, ci, cj)
+    good = m & np.isfinite(d_from)
+    norm = np.zeros(m.shape)
+    if scaled:
+        norm[good] = d_from[good] / (d_from[good] + d_edge[good] + 0.001)
+    else:
+        norm[good] = d_from[good] / maximum_radius
+    bins = (norm * bin_count).astype(int)
+    bins[bins > bin_count] = bin_count
+    ii, jj = np.mgrid[0 : m.shape[0], 0 : m.shape[1]]
+    wedge = (ii > ci).astype(int) + 2 * (jj > cj).astype(int) + 4 * (np.abs(ii - ci) > np.abs(jj - cj)).astype(int)
+    return sl, m, good, bins, wedge, (int(ci), int(cj))
+
+
 def get_radial_distribution(masks, pixels, scaled=True, bin_count=4, maximum_radius=100):
     labels = np.asarray(masks)
     img = np.asarray(pixels).astype(np.float64)
@@ -75,27 +103,11 @@ def get_radial_distribution(masks, pixels, scaled=True, bin_count=4, maximum_rad
     res = {n: np.full(len(idx), np.nan) for n in names(bin_count, scaled)}
     nb = bin_count + 1
     for k, lab in enumerate(idx):
-        full = labels == lab
-        if not full.any():
+        geo = object_geometry(labels, lab, scaled, bin_count, maximum_radius)
+        if geo is None:
             continue
-        d_edge_full = distance_to_edge_object(full)
-        sl = ndi.find_objects(full.astype(np.int32))[0]
-        m = full[sl]
-        d_edge = d_edge_full[sl]
+        sl, m, good, bins, wedge, _ = geo
         px = img[sl]
-        # centre: maximum of d_to_edge, last raster occurrence among ties
-        flat = np.where(m.ravel(), d_edge.ravel(), -1.0)
-        order = np.argsort(flat, kind="stable")
-        ci, cj = np.unravel_index(order[-1], m.shape)
-        d_from = propagate_from(m, ci, cj)
-        good = m & np.isfinite(d_from)
-        norm = np.zeros(m.shape)
-        if scaled:
-            norm[good] = d_from[good] / (d_from[good] + d_edge[good] + 0.001)
-        else:
-            norm[good] = d_from[good] / maximum_radius
-        bins = (norm * bin_count).astype(int)
-        bins[bins > bin_count] = bin_count
         hist = np.zeros(nb)
         cnt = np.zeros(nb)
         np.add.at(hist, bins[good], px[good])
@@ -104,8 +116,6 @@ def get_radial_distribution(masks, pixels, scaled=True, bin_count=4, maximum_rad
             frac_at_d = hist / hist.sum()
             frac_at_bin = cnt / cnt.sum()
             mean_frac = frac_at_d / (frac_at_bin + np.finfo(float).eps)
-        ii, jj = np.mgrid[0 : m.shape[0], 0 : m.shape[1]]
-        wedge = (ii > ci).astype(int) + 2 * (jj > cj).astype(int) + 4 * (np.abs(ii - ci) > np.abs(jj - cj)).astype(int)
         n_out = bin_count if scaled else bin_count + 1
         for b in range(n_out):
             sel = good & (bins == b)

@@ -1,5 +1,6 @@
 """Randomised differential run of every feature family against the oracle on irregular label images: thresholded smoothed noise
-(concave blobs, holes, one-pixel specks, objects on the frame border, very different sizes in one frame).
+(concave blobs, holes, one-pixel specks, objects on the frame border, very different sizes in one frame) and, where the frame
+has room, one winding object.
 usage: python tests/fuzz/fuzz_features.py [first_seed=0] [n=12] [extras]     (GPU box; well under a second per seed)"""
 import sys
 import time
@@ -29,6 +30,17 @@ for seed in range(first, first + n):
     if k > 60:  # (the oracle loops over objects x families: keep a seed within seconds)
         keep = rng.choice(np.arange(1, k + 1), 60, replace=False)
         lab = np.where(np.isin(lab, keep), lab, 0)
+    # smooth noise never winds: where a 25 x 26 window is free (searched on a grid, no random draw: the seeds' other objects stay
+    # as they were), a one-pixel serpentine of 23 x 24 — 299 pixels on ONE path of more steps than 4 (h + w) + 8
+    wound = False
+    for y, x in ((y, x) for y in range(0, Y - 24, 8) for x in range(0, X - 25, 8)):
+        if not lab[y : y + 25, x : x + 26].any():
+            s = np.zeros((23, 24), bool)
+            s[0::2] = True
+            s[1::4, -1] = s[3::4, 0] = True
+            lab[y + 1 : y + 24, x + 1 : x + 25][s] = lab.max() + 1
+            wound = True
+            break
     _, inv = np.unique(lab, return_inverse=True)
     lab = inv.reshape(Y, X).astype(np.uint16)
     C, Z = 2, int(rng.integers(1, 3))
@@ -56,10 +68,10 @@ for seed in range(first, first + n):
                 1: {"max": ["texture", "median", "total", "max5px_median", "moment_of_inertia"]}}
         _run_both(tree, [lab], px, kw=kw)
         _run_both({(0, 1): {"None": {red: ["pearson", "costes", "manders_fold", "rwc"]}}}, [lab], px, multi=True, kw=kw)
-        print(f"seed {seed}: {Y}x{X}, {int(lab.max())} objects, {kind}, {red}, {kw['texture']}, {kw['radial_distribution']}: ok "
+        print(f"seed {seed}: {Y}x{X}, {int(lab.max())} objects, {kind}, {red}, {kw['texture']}, {kw['radial_distribution']}, serpentine {wound}: ok "
               f"({time.perf_counter() - t0:.1f} s)", flush=True)
         continue
     _run_both(tree, [lab], px)
     _run_both({(0, 1): {"None": {"max": ["pearson", "costes", "manders_fold", "rwc"]}}}, [lab], px, multi=True)
     print(f"seed {seed}: {Y}x{X}, {int(lab.max())} objects, areas {np.bincount(lab.ravel())[1:].min()}..{np.bincount(lab.ravel())[1:].max()}, "
-          f"sigma {sigma:.1f}: ok ({time.perf_counter() - t0:.1f} s)", flush=True)
+          f"sigma {sigma:.1f}, serpentine {wound}: ok ({time.perf_counter() - t0:.1f} s)", flush=True)
