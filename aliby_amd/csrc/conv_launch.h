@@ -1,6 +1,7 @@
 // conv_launch.h — the launch front end of the network's persistent convolution kernels (nn_conv.hip: k_conv3x3, k_conv3x3_dma,
 // k_conv_pair32, k_conv_first_pair; nn_conv_deep.hip: k_conv3x3_deep, k_conv3x3_deep16, k_conv3x3_deep_ls, k_conv3x3_kloop64).
-// The counterpart of the per-object feature kernels is object_launch.h.
+// The counterpart of the per-object feature kernels is object_launch.h; the device-side sibling, with the bf16 / MFMA primitives
+// these kernels share, is conv_mfma.h.
 //
 // Every such kernel takes one argument struct with `ntiles` and `order` and loops over the tiles itself (tile_walk, the one
 // device function here): the grid is 8 XCDs x `nslots` workgroups, never more than the tiles need.  A site states how many

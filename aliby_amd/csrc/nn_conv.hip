@@ -19,52 +19,9 @@
 // (MFMA row (reg&3) + 8*(reg>>2) + 4*(lane>>5)  <->  channel 16*(lane>>5) + reg).
 #include "common.h"
 #include "conv_launch.h"
-#include <utility>
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
+#include "conv_mfma.h"
 
 namespace {
-
-// compile-time loop: every index is a constant expression, so register arrays are never indexed dynamically
-template <class F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  static_for_impl(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
-}
-
-__device__ __forceinline__ float cv_bf2f(unsigned h) { return __uint_as_float(h << 16); }
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-// two floats -> packed bf16 pair, round to nearest even (v_cvt_pk_bf16_f32)
-__device__ __forceinline__ unsigned cv_pack2(float lo, float hi) {
-  const f32x2_t f = {lo, hi};
-  const bf16x2_t b = __builtin_convertvector(f, bf16x2_t);
-  return __builtin_bit_cast(unsigned, b);
-}
-__device__ __forceinline__ unsigned cv_f2bf(float f) { return cv_pack2(f, 0.f) & 0xffffu; }
-
-typedef short s16x2_t __attribute__((ext_vector_type(2)));
-// The prologue on one channel octet: bf16 -> relu(scale * x + shift) -> bf16, two channels per instruction
-// (v_pk_fma_f32, v_cvt_pk_bf16_f32; ReLU as v_pk_max_i16 on the bf16 bit patterns: a set sign bit is a negative
-// int16), and zeroed outside the image (`keep` = 0 there: the convolution pads the ACTIVATED tensor).
-__device__ __forceinline__ uint4 conv_act8(uint4 v, const f32x2_t (&sc)[4], const f32x2_t (&sh)[4], unsigned keep) {
-  const unsigned w4[4] = {v.x, v.y, v.z, v.w};
-  unsigned r4[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const f32x2_t x = {__uint_as_float(w4[q] << 16), __uint_as_float(w4[q] & 0xffff0000u)};
-    const f32x2_t y = __builtin_elementwise_fma(sc[q], x, sh[q]);
-    s16x2_t b = __builtin_bit_cast(s16x2_t, __builtin_convertvector(y, bf16x2_t));
-    const s16x2_t zero = {0, 0};
-    b = __builtin_elementwise_max(b, zero);
-    r4[q] = __builtin_bit_cast(unsigned, b) & keep;
-  }
-  return make_uint4(r4[0], r4[1], r4[2], r4[3]);
-}
 
 struct ConvArgs {
   const uint4* in;     // [N, H>>UP, W>>UP, CIN] bf16
@@ -140,10 +97,7 @@ template <int R>
 __device__ __forceinline__ void conv_seed(f32x16_t (&acc)[R], const float4 (&b4)[4], const uint4 (&rr)[R][2], bool has_res) {
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      acc[r][4 * q] = b4[q].x; acc[r][4 * q + 1] = b4[q].y; acc[r][4 * q + 2] = b4[q].z; acc[r][4 * q + 3] = b4[q].w;
-    }
+    acc_seed(acc[r], b4);
     if (has_res) {
       const unsigned rw[8] = {rr[r][0].x, rr[r][0].y, rr[r][0].z, rr[r][0].w, rr[r][1].x, rr[r][1].y, rr[r][1].z, rr[r][1].w};
 #pragma unroll
@@ -188,10 +142,7 @@ __device__ __forceinline__ void conv_store(const ConvArgs& a, int n, int irow, i
     const int gy = row0 + r;
     if (gy >= a.H) continue;
     uint4* op = a.out + (size_t)n * a.H * a.W * a.ocs + a.ocoff + (unsigned)(((irow + gy) * a.W + gx) * a.ocs + (c0 >> 3));
-    op[0] = make_uint4(cv_pack2(acc[r][0], acc[r][1]), cv_pack2(acc[r][2], acc[r][3]),
-                       cv_pack2(acc[r][4], acc[r][5]), cv_pack2(acc[r][6], acc[r][7]));
-    op[1] = make_uint4(cv_pack2(acc[r][8], acc[r][9]), cv_pack2(acc[r][10], acc[r][11]),
-                       cv_pack2(acc[r][12], acc[r][13]), cv_pack2(acc[r][14], acc[r][15]));
+    acc_pack16(acc[r], op[0], op[1]);
   }
 }
 
@@ -207,7 +158,7 @@ struct HeadW { bf16x8_t w[2]; };
 
 __device__ __forceinline__ HeadW head_weights(const float* hw, int hO, int lane) {  // hw [hO][32] float32 (rounded to bf16 here)
   HeadW h;
-  const int m = lane & 31, hh = lane >> 5, o = 16 * ((m >> 2) & 1) + (m & 3) + 4 * (m >> 3);
+  const int hh = lane >> 5, o = conv_row_channel(lane & 31);
 #pragma unroll
   for (int kc = 0; kc < 2; ++kc) {
     unsigned r4[4];
@@ -245,9 +196,7 @@ __device__ __forceinline__ f32x16_t head_apply(uint4 lo, uint4 hi, const float* 
 }
 
 __device__ __forceinline__ f32x16_t head_from_acc(const f32x16_t& acc, const float* sc, const float* sh, const HeadW& hw, int hh) {
-  const uint4 lo = make_uint4(cv_pack2(acc[0], acc[1]), cv_pack2(acc[2], acc[3]), cv_pack2(acc[4], acc[5]), cv_pack2(acc[6], acc[7]));
-  const uint4 hi = make_uint4(cv_pack2(acc[8], acc[9]), cv_pack2(acc[10], acc[11]), cv_pack2(acc[12], acc[13]), cv_pack2(acc[14], acc[15]));
-  return head_apply(lo, hi, sc, sh, hw, hh);
+  return head_apply(acc_pack8(acc, 0), acc_pack8(acc, 1), sc, sh, hw, hh);
 }
 
 template <int CIN, int COUT, bool TALL = false, bool PACK = false, bool HEAD = false>
@@ -738,16 +687,19 @@ __global__ __launch_bounds__(256, (DmaCfg<CIN, COUT, UP, PACK>::WAVES_PER_SIMD))
 //     consumers:  unit B pass 0 of t - 1 | S1 | unit B pass 1 of t - 1    | S2 |
 // Same bits as the two launches.
 // ------------------------------------------------------------------------------------------------
-struct PairCfg {
+struct PairBase {  // the tile geometry k_conv_pair32 and k_conv_first_pair share
   static constexpr int KC = 2, NPL = 4, R = 2, PASSES = 2;
-  static constexpr int TH = 14, TWO = 30, MH = 16, MW = 32, IH = 18, IW = 34;
-  static constexpr int RAW_IN = IH * IW, PLANE_IN = RAW_IN + (10 - RAW_IN % 8) % 8;
+  static constexpr int TH = 14, TWO = 30, MH = 16, MW = 32;  // output tile, intermediate tile (one-pixel halo)
   static constexpr int RAW_MID = MH * MW, PLANE_MID = RAW_MID + (10 - RAW_MID % 8) % 8;
+  static constexpr int MID_SLOTS = NPL * PLANE_MID + 8;      // 16-byte slots of one set of intermediate planes
+  static constexpr int DEPTH = 6;
+};
+struct PairCfg : PairBase {
+  static constexpr int IH = 18, IW = 34;
+  static constexpr int RAW_IN = IH * IW, PLANE_IN = RAW_IN + (10 - RAW_IN % 8) % 8;
   static constexpr int PIX_PER_IT = 256 / NPL, ITERS = (RAW_IN + PIX_PER_IT - 1) / PIX_PER_IT;
-  static constexpr int MID_SLOTS = NPL * PLANE_MID + 8;
   static constexpr int SLOTS = NPL * PLANE_IN + 2 * MID_SLOTS;
   static constexpr int LDS_BYTES = SLOTS * 16;
-  static constexpr int DEPTH = 6;
 };
 
 template <bool POOL, bool HEAD>
@@ -841,9 +793,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_pair32(ConvArgs a) {
             for (int q = 0; q < 4; ++q) b4[q] = bp[q];
           }
 #pragma unroll
-          for (int r = 0; r < R; ++r)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { acc[r][4 * q] = b4[q].x; acc[r][4 * q + 1] = b4[q].y; acc[r][4 * q + 2] = b4[q].z; acc[r][4 * q + 3] = b4[q].w; }
+          for (int r = 0; r < R; ++r) acc_seed(acc[r], b4);
         }
         __builtin_amdgcn_sched_barrier(0);
         conv_mfma<R, KC, cfg::DEPTH, PLANE_IN, IW_>(reinterpret_cast<const bf16x8_t*>(ldsIn) + hh * PLANE_IN + mbase * IW_ + px, wA, acc);
@@ -888,12 +838,8 @@ __global__ __launch_bounds__(512, 1) void k_conv_pair32(ConvArgs a) {
         if (tid < 4) hconst[64 + tid] = tid < a.hO ? a.hbias[tid] : 0.f;
       }  // (visible to the consumers after the two fill barriers below)
     }
-    float4 b4[4] = {};
-    if (a.bias2) {
-      const float4* bp = reinterpret_cast<const float4*>(a.bias2 + c0);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) b4[q] = bp[q];
-    }
+    float4 b4[4];
+    load_bias4(a.bias2, c0, b4);
     __syncthreads();  // the producers' first tile: its S1 ...
     __syncthreads();  // ... and S2
     // (measured and NOT adopted, round 3: requesting a pass's residual rows one pass ahead instead of right before they seed the
@@ -962,16 +908,12 @@ __global__ __launch_bounds__(512, 1) void k_conv_pair32(ConvArgs a) {
 // where the two-launch path stores it, run it through unit 1's prologue and write unit 1's channel-octet planes; they also
 // leave the tile's raw pixels (the projection's input) in LDS.  Waves 4-7 (consumers) hold unit 1's weights and the
 // projection's: 9 x 2 + 1 k-steps per output row, in the order of k_conv3x3's fused projection.  Same bits as the two launches.
-struct FirstPairCfg {
-  static constexpr int KC = 2, NPL = 4, R = 2, PASSES = 2;
-  static constexpr int TH = 14, TWO = 30, MH = 16, MW = 32, AH = 18, AW = 36;
-  static constexpr int RAW_MID = MH * MW, PLANE_MID = RAW_MID + (10 - RAW_MID % 8) % 8;
-  static constexpr int MID_SLOTS = NPL * PLANE_MID + 8;     // 16-byte slots
+struct FirstPairCfg : PairBase {
+  static constexpr int AH = 18, AW = 36;
   static constexpr int P0_WORDS = 2 * AH * AW;              // pair-packed activated window, 32-bit words
   static constexpr int RAWP_WORDS = MH * MW;                // raw pixels of the tile as (ch0, ch1) bf16 pairs
   static constexpr int VALS = 2 * AH * AW, ITERS = (VALS + 255) / 256;
   static constexpr int LDS_BYTES = 2 * MID_SLOTS * 16 + P0_WORDS * 4 + 2 * RAWP_WORDS * 4;
-  static constexpr int DEPTH = 6;
 };
 
 __global__ __launch_bounds__(512, 1) void k_conv_first_pair(ConvArgs a) {
@@ -995,10 +937,10 @@ __global__ __launch_bounds__(512, 1) void k_conv_first_pair(ConvArgs a) {
 
   if (!consumer) {
     // =============================================================== producers: float32 window -> c0 -> unit 1's planes
-    // first-layer weights as MFMA A fragments (row m <-> channel 16*((m>>2)&1) + (m&3) + 4*(m>>3), as k_first_conv)
+    // first-layer weights as MFMA A fragments (row m <-> channel conv_row_channel(m), as k_first_conv)
     bf16x8_t wF[2];
     {
-      const int m = lane & 31, co = 16 * ((m >> 2) & 1) + (m & 3) + 4 * (m >> 3);
+      const int m = lane & 31, co = conv_row_channel(m);
 #pragma unroll
       for (int kc = 0; kc < 2; ++kc) {
         unsigned r4[4];
@@ -1062,16 +1004,15 @@ __global__ __launch_bounds__(512, 1) void k_conv_first_pair(ConvArgs a) {
       const int y0 = ty * TH, x0 = tx * TWO;
       uint4* const ldsMid = ldsMid0 + (it & 1) * cfg::MID_SLOTS;
       unsigned short* const rawPh = reinterpret_cast<unsigned short*>(rawP0 + (it & 1) * cfg::RAWP_WORDS);
-      // ---- activated window, pair-packed: word (c, r, q) = act(q) | act(q + 1) << 16 (k_first_conv's arithmetic: separate multiply
-      // and add, ReLU in float, then round to bf16; zero outside the image), and the tile's raw pixels for the projection
+      // ---- activated window, pair-packed: word (c, r, q) = act(q) | act(q + 1) << 16 (first_relu, then the rounding: k_first_conv's arithmetic), and
+      // the tile's raw pixels for the projection
 #pragma unroll
       for (int u = 0; u < ITERS; ++u) {
         const int i = tid + 256 * u;
         if (i >= cfg::VALS) break;
         const int c = i / (AH * AW), rem = i - c * (AH * AW), r = rem / AW, q = rem - r * AW;
         const bool ok = (inside >> u) & 1u;
-        const float t = ok ? fmaxf(v[u] * (c ? fs1 : fs0) + (c ? fh1 : fh0), 0.f) : 0.f;
-        const unsigned short b = (unsigned short)(cv_pack2(t, 0.f) & 0xffffu);
+        const unsigned short b = (unsigned short)cv_f2bf(ok ? first_relu(v[u], c ? fs1 : fs0, c ? fh1 : fh0) : 0.f);
         P0h[2 * i] = b;                       // low half of word (c, r, q)
         if (q > 0) P0h[2 * (i - 1) + 1] = b;  // high half of word (c, r, q - 1)
         if (q == AW - 1) P0h[2 * i + 1] = 0;
@@ -1131,12 +1072,8 @@ __global__ __launch_bounds__(512, 1) void k_conv_first_pair(ConvArgs a) {
       for (int i = 0; i < 9 * KC; ++i) wB[i] = pb[i * 64];
     }
     const bf16x8_t pfrag = (reinterpret_cast<const bf16x8_t*>(a.pwpk) + lane)[0];
-    float4 b4[4] = {};
-    if (a.bias2) {
-      const float4* bp = reinterpret_cast<const float4*>(a.bias2 + c0);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) b4[q] = bp[q];
-    }
+    float4 b4[4];
+    load_bias4(a.bias2, c0, b4);
     __syncthreads();  // the producers' first tile: its S1 ...
     __syncthreads();  // ... and S2
     for (int it = 0; it < my_tiles; ++it) {
@@ -1153,9 +1090,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_first_pair(ConvArgs a) {
         if (rbase < TH) {  // (the last wave's second pass has no rows)
           f32x16_t acc[R];
 #pragma unroll
-          for (int r = 0; r < R; ++r)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { acc[r][4 * q] = b4[q].x; acc[r][4 * q + 1] = b4[q].y; acc[r][4 * q + 2] = b4[q].z; acc[r][4 * q + 3] = b4[q].w; }
+          for (int r = 0; r < R; ++r) acc_seed(acc[r], b4);
           __builtin_amdgcn_sched_barrier(0);
           conv_mfma<R, KC, cfg::DEPTH, PLANE_MID, MW>(reinterpret_cast<const bf16x8_t*>(ldsMid) + hh * PLANE_MID + rbase * MW + px, wB, acc);
           // the projection of the raw pixels: one more k-step (channels 0-1 real, the rest of the 16 zero)
@@ -1204,7 +1139,7 @@ __global__ __launch_bounds__(256) void k_out_head_mfma(const uint4* __restrict__
 
 // Packed layout: [cout block cb][tap][k-step kc][lane][8 bf16]; lane l holds the MFMA A fragment
 // A[row m = l&31][k = 8*(l>>5) + j] = W[cb*32 + chan(m)][cin = 16*kc + 8*(l>>5) + j][tap], with
-// chan(m) = 16*((m>>2)&1) + (m&3) + 4*(m>>3) (see the header comment).
+// chan(m) = conv_row_channel(m) (conv_mfma.h; see the header comment).
 __global__ void k_pack_conv3x3(const float* w, int cout, int cin_src, int cin, int taps, unsigned short* out, size_t total) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
@@ -1215,7 +1150,7 @@ __global__ void k_pack_conv3x3(const float* w, int cout, int cin_src, int cin, i
   rest /= kcn;
   const int tap = (int)(rest % taps), cb = (int)(rest / taps);
   const int m = lane & 31, h = lane >> 5;
-  const int co = cb * 32 + 16 * ((m >> 2) & 1) + (m & 3) + 4 * (m >> 3);
+  const int co = cb * 32 + 16 * ((m >> 2) & 1) + (m & 3) + 4 * (m >> 3);  // (conv_row_channel(m), written out: see conv_mfma.h)
   const int ci = 16 * kc + 8 * h + j;
   float v = 0.f;
   if (ci < cin_src && co < cout) v = w[((size_t)co * cin_src + ci) * taps + tap];

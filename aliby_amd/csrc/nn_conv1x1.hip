@@ -12,18 +12,9 @@
 //   * the wave's weight fragments (CIN/16 x 4 VGPRs) stay in registers; fragment order and the output-channel
 //     permutation are those of aliby_nn_pack_conv1x1_bf16, so a lane ends with 16 contiguous channels of one pixel.
 #include "common.h"
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
+#include "conv_mfma.h"
 
 namespace {
-
-__device__ __forceinline__ unsigned p1_pack2(float lo, float hi) {
-  const f32x2_t f = {lo, hi};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2_t));
-}
 
 struct P1Args {
   const uint4* in;    // [P, CIN] bf16
@@ -60,24 +51,18 @@ __global__ __launch_bounds__(256) void k_conv1x1(P1Args a) {
   }
   __syncthreads();
   const int c0 = cbg * 32 + hh * 16;
-  float4 b4[4] = {};
-  if (a.bias) {
-    const float4* bp = reinterpret_cast<const float4*>(a.bias + c0);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) b4[q] = bp[q];
-  }
+  float4 b4[4];
+  load_bias4(a.bias, c0, b4);
   const bf16x8_t* L = reinterpret_cast<const bf16x8_t*>(planes) + hh * PP + px;
   for (int g = pg0; g < TP / 32; g += pgs) {
     f32x16_t acc;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { acc[4 * q] = b4[q].x; acc[4 * q + 1] = b4[q].y; acc[4 * q + 2] = b4[q].z; acc[4 * q + 3] = b4[q].w; }
+    acc_seed(acc, b4);
 #pragma unroll
     for (int k = 0; k < KC; ++k) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wfrag[k], L[2 * k * PP + g * 32], acc, 0, 0, 0);
     const size_t gp = p0 + g * 32 + px;
     if (gp < a.P) {
       uint4* op = a.out + gp * (a.COUT / 8) + (c0 >> 3);
-      op[0] = make_uint4(p1_pack2(acc[0], acc[1]), p1_pack2(acc[2], acc[3]), p1_pack2(acc[4], acc[5]), p1_pack2(acc[6], acc[7]));
-      op[1] = make_uint4(p1_pack2(acc[8], acc[9]), p1_pack2(acc[10], acc[11]), p1_pack2(acc[12], acc[13]), p1_pack2(acc[14], acc[15]));
+      acc_pack16(acc, op[0], op[1]);
     }
   }
 }
@@ -108,10 +93,10 @@ __global__ __launch_bounds__(256) void k_first_conv(FirstArgs a) {
   const int px = lane & 31, hh = lane >> 5;
   const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH, n = blockIdx.z;
   const size_t plane = (size_t)a.H * a.W;
-  // ---- weights as MFMA A fragments: row m <-> output channel 16*((m>>2)&1) + (m&3) + 4*(m>>3) (as in nn_conv.hip)
+  // ---- weights as MFMA A fragments: row m <-> output channel conv_row_channel(m) (as in nn_conv.hip)
   bf16x8_t wfrag[2];
   {
-    const int m = lane & 31, co = 16 * ((m >> 2) & 1) + (m & 3) + 4 * (m >> 3);
+    const int m = lane & 31, co = conv_row_channel(m);
 #pragma unroll
     for (int kc = 0; kc < 2; ++kc) {
       unsigned r4[4];
@@ -123,7 +108,7 @@ __global__ __launch_bounds__(256) void k_first_conv(FirstArgs a) {
           const int k = 16 * kc + 8 * hh + 2 * j2 + e, c = k / 12, ty = (k % 12) / 4, tx = k % 4;
           v[e] = (c < a.Cin && tx < 3 && k < 24) ? a.w[((size_t)co * a.Cin + c) * 9 + ty * 3 + tx] : 0.f;
         }
-        r4[j2] = p1_pack2(v[0], v[1]);
+        r4[j2] = cv_pack2(v[0], v[1]);
       }
       wfrag[kc] = __builtin_bit_cast(bf16x8_t, make_uint4(r4[0], r4[1], r4[2], r4[3]));
     }
@@ -134,8 +119,8 @@ __global__ __launch_bounds__(256) void k_first_conv(FirstArgs a) {
     const int gy = y0 - 1 + ly, gx = x0 - 1 + lx;
     float t = 0.f;
     if (c < a.Cin && i < 2 * PLANE && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W)
-      t = fmaxf(a.x[((size_t)n * a.Cin + c) * plane + (size_t)gy * a.W + gx] * a.scale[c] + a.shift[c], 0.f);
-    act[i] = (unsigned short)(p1_pack2(t, 0.f) & 0xffffu);
+      t = first_relu(a.x[((size_t)n * a.Cin + c) * plane + (size_t)gy * a.W + gx], a.scale[c], a.shift[c]);
+    act[i] = (unsigned short)cv_f2bf(t);
   }
   __syncthreads();
   const int gx = x0 + px;
@@ -164,12 +149,11 @@ __global__ __launch_bounds__(256) void k_first_conv(FirstArgs a) {
     if (gx < a.W && gy < a.H) {
       const size_t p = (size_t)n * plane + (size_t)gy * a.W + gx;
       uint4* op = reinterpret_cast<uint4*>(a.c0) + p * 4 + hh * 2;  // lane holds channels 16*hh .. 16*hh + 15
-      op[0] = make_uint4(p1_pack2(acc[0], acc[1]), p1_pack2(acc[2], acc[3]), p1_pack2(acc[4], acc[5]), p1_pack2(acc[6], acc[7]));
-      op[1] = make_uint4(p1_pack2(acc[8], acc[9]), p1_pack2(acc[10], acc[11]), p1_pack2(acc[12], acc[13]), p1_pack2(acc[14], acc[15]));
+      acc_pack16(acc, op[0], op[1]);
       if (hh == 0) {  // raw copy, 8 channels (zeros past Cin)
         const float v0 = a.x[((size_t)n * a.Cin) * plane + (size_t)gy * a.W + gx];
         const float v1 = a.Cin > 1 ? a.x[((size_t)n * a.Cin + 1) * plane + (size_t)gy * a.W + gx] : 0.f;
-        reinterpret_cast<uint4*>(a.raw)[p] = make_uint4(p1_pack2(v0, v1), 0u, 0u, 0u);
+        reinterpret_cast<uint4*>(a.raw)[p] = make_uint4(cv_pack2(v0, v1), 0u, 0u, 0u);
       }
     }
   }

@@ -17,7 +17,7 @@
 //     is 4 waves = 128 output channels (layers with 256 are two tiles per run, adjacent in the schedule so that the second
 //     finds the window in L2);
 //   * K loop over 64-channel slices: the slice's window is staged once into LDS as channel-octet planes with the prologue
-//     (BatchNorm affine + style shift + ReLU, zero padding after the activation — conv_act8 of nn_conv.hip) applied on the
+//     (BatchNorm affine + style shift + ReLU, zero padding after the activation — conv_act8 of conv_mfma.h) applied on the
 //     way, then 4 k-steps x 9 taps x 7 blocks of v_mfma_f32_32x32x16_bf16 run from it;
 //   * weights are NOT resident (9 * CIN/16 fragments per wave do not fit beside the accumulators): each (tap, k-step)
 //     fragment — 1 KiB per wave, already in fragment order in the packed array, L2-resident — is loaded straight into VGPRs
@@ -25,45 +25,9 @@
 //   * two workgroups per CU (<= 256 VGPRs, 44 KiB of LDS each) overlap each other's staging and MFMA phases.
 #include "common.h"
 #include "conv_launch.h"
-#include <utility>
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef short s16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
+#include "conv_mfma.h"
 
 namespace {
-
-template <class F, int... I>
-__device__ __forceinline__ void sfor_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void sfor(F&& f) {
-  sfor_impl(static_cast<F&&>(f), std::make_integer_sequence<int, N>{});
-}
-
-__device__ __forceinline__ float dc_bf2f(unsigned h) { return __uint_as_float(h << 16); }
-__device__ __forceinline__ unsigned dc_pack2(float lo, float hi) {
-  const f32x2_t f = {lo, hi};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2_t));
-}
-// prologue on one channel octet (same arithmetic, same rounding as conv_act8 in nn_conv.hip)
-__device__ __forceinline__ uint4 dc_act8(uint4 v, const f32x2_t (&sc)[4], const f32x2_t (&sh)[4], unsigned keep) {
-  const unsigned w4[4] = {v.x, v.y, v.z, v.w};
-  unsigned r4[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const f32x2_t x = {__uint_as_float(w4[q] << 16), __uint_as_float(w4[q] & 0xffff0000u)};
-    const f32x2_t y = __builtin_elementwise_fma(sc[q], x, sh[q]);
-    s16x2_t b = __builtin_bit_cast(s16x2_t, __builtin_convertvector(y, bf16x2_t));
-    const s16x2_t zero = {0, 0};
-    b = __builtin_elementwise_max(b, zero);
-    r4[q] = __builtin_bit_cast(unsigned, b) & keep;
-  }
-  return make_uint4(r4[0], r4[1], r4[2], r4[3]);
-}
 
 struct DeepArgs {
   const uint4* in;     // [N, H>>up, W>>up, CIN] bf16
@@ -179,8 +143,8 @@ __device__ __forceinline__ void dc_seed32(const DeepArgs& a, int q0, int px, int
       const unsigned rw[8] = {rr[b][0].x, rr[b][0].y, rr[b][0].z, rr[b][0].w, rr[b][1].x, rr[b][1].y, rr[b][1].z, rr[b][1].w};
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        acc[b][2 * j] = b16[2 * j] + dc_bf2f(rw[j] & 0xffffu);
-        acc[b][2 * j + 1] = b16[2 * j + 1] + dc_bf2f(rw[j] >> 16);
+        acc[b][2 * j] = b16[2 * j] + cv_bf2f(rw[j] & 0xffffu);
+        acc[b][2 * j + 1] = b16[2 * j + 1] + cv_bf2f(rw[j] >> 16);
       }
     }
   } else {
@@ -201,10 +165,7 @@ __device__ __forceinline__ void dc_store32(const DeepArgs& a, int q0, int px, in
     const bool ok = q0 + b * 32 + px < a.q_end && y < a.H && x >= 0 && x < a.W && n < a.N;
     if (ok) {
       uint4* op = a.out + (unsigned)(((n * a.H + y) * a.W + x) * ocs + (c0 >> 3));
-      op[0] = make_uint4(dc_pack2(acc[b][0], acc[b][1]), dc_pack2(acc[b][2], acc[b][3]), dc_pack2(acc[b][4], acc[b][5]),
-                         dc_pack2(acc[b][6], acc[b][7]));
-      op[1] = make_uint4(dc_pack2(acc[b][8], acc[b][9]), dc_pack2(acc[b][10], acc[b][11]), dc_pack2(acc[b][12], acc[b][13]),
-                         dc_pack2(acc[b][14], acc[b][15]));
+      acc_pack16(acc[b], op[0], op[1]);
     }
     dc_step32(c, y, n, LW, HP);
   }
@@ -282,7 +243,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep(DeepArgs a) {
         f32x2_t shs[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) shs[k] = ((later >> it) & 1u) ? sh1[k] : sh[k];
-        const uint4 o = dc_act8(v[it], sc, shs, 0u - ((inside >> it) & 1u));
+        const uint4 o = conv_act8(v[it], sc, shs, 0u - ((inside >> it) & 1u));
         const int wp_ = pos0 + 32 * it;
         if (wp_ < WIN) lds[pl * DC_PLANE + wp_] = o;
       }
@@ -301,14 +262,14 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep(DeepArgs a) {
       };
 #pragma unroll
       for (int f = 0; f < DC_PDEPTH - 1; ++f) pring[f] = pfrag(f);
-      sfor<NW>([&](auto ic) {
+      static_for<NW>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
         if constexpr (i == DC_REQ_AT) {  // request the next slice's window (see DC_REQ_AT)
           if (s + 1 < S) request(s + 1);
           __builtin_amdgcn_sched_barrier(0);
         }
         if constexpr (i + DC_WDEPTH - 1 < NW) wring[(i + DC_WDEPTH - 1) % DC_WDEPTH] = wfrag(i + DC_WDEPTH - 1);
-        sfor<DC_NB>([&](auto bc) {
+        static_for<DC_NB>([&](auto bc) {
           constexpr int b = decltype(bc)::value, f = i * DC_NB + b;
           if constexpr (f + DC_PDEPTH - 1 < NF) pring[(f + DC_PDEPTH - 1) % DC_PDEPTH] = pfrag(f + DC_PDEPTH - 1);
           acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wring[i % DC_WDEPTH], pring[f % DC_PDEPTH], acc[b], 0, 0, 0);
@@ -415,7 +376,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_kloop64(DeepArgs a) {
         f32x2_t shs[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) shs[k] = ((later >> it) & 1u) ? sh1[k] : sh[k];
-        const uint4 o = dc_act8(v[it], sc, shs, 0u - ((inside >> it) & 1u));
+        const uint4 o = conv_act8(v[it], sc, shs, 0u - ((inside >> it) & 1u));
         const int wp_ = pos0 + 64 * it;
         if (wp_ < WIN) lds[pl * U_PLANE + wp_] = o;
       }
@@ -432,7 +393,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_kloop64(DeepArgs a) {
       };
 #pragma unroll
       for (int f = 0; f < DC_PDEPTH - 1; ++f) pring[f] = pfrag(f);
-      sfor<U_NW>([&](auto ic) {
+      static_for<U_NW>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
         if constexpr (i + U_WDEPTH - 1 < U_NW) wring[(i + U_WDEPTH - 1) % U_WDEPTH] = wfrag(i + U_WDEPTH - 1);
         if constexpr (i == U_REQ_AT) {
@@ -440,7 +401,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_kloop64(DeepArgs a) {
           if (s + 1 < S) request(s + 1);
           __builtin_amdgcn_sched_barrier(0);
         }
-        sfor<DC_NB>([&](auto bc) {
+        static_for<DC_NB>([&](auto bc) {
           constexpr int b = decltype(bc)::value, f = i * DC_NB + b;
           if constexpr (f + DC_PDEPTH - 1 < NF) pring[(f + DC_PDEPTH - 1) % DC_PDEPTH] = pfrag(f + DC_PDEPTH - 1);
           acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wring[i % U_WDEPTH], pring[f % DC_PDEPTH], acc[b], 0, 0, 0);
@@ -550,10 +511,10 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep16(DeepArgs a) {
             const unsigned rw[4] = {rr[b][h].x, rr[b][h].y, rr[b][h].z, rr[b][h].w};
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-              acc[b][0][h][2 * j] = b8[2 * j] + dc_bf2f(rw[j] & 0xffffu);
-              acc[b][0][h][2 * j + 1] = b8[2 * j + 1] + dc_bf2f(rw[j] >> 16);
-              acc[b][1][h][2 * j] = b8[4 + 2 * j] + dc_bf2f(rw[2 + j] & 0xffffu);
-              acc[b][1][h][2 * j + 1] = b8[4 + 2 * j + 1] + dc_bf2f(rw[2 + j] >> 16);
+              acc[b][0][h][2 * j] = b8[2 * j] + cv_bf2f(rw[j] & 0xffffu);
+              acc[b][0][h][2 * j + 1] = b8[2 * j + 1] + cv_bf2f(rw[j] >> 16);
+              acc[b][1][h][2 * j] = b8[4 + 2 * j] + cv_bf2f(rw[2 + j] & 0xffffu);
+              acc[b][1][h][2 * j + 1] = b8[4 + 2 * j + 1] + cv_bf2f(rw[2 + j] >> 16);
             }
           }
       } else {
@@ -584,7 +545,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep16(DeepArgs a) {
         f32x2_t shs[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) shs[k] = ((later >> it) & 1u) ? sh1[k] : sh[k];
-        const uint4 o = dc_act8(v[it], sc, shs, 0u - ((inside >> it) & 1u));
+        const uint4 o = conv_act8(v[it], sc, shs, 0u - ((inside >> it) & 1u));
         const int wp_ = pos0 + 32 * it;
         if (wp_ < WIN) lds[pl * DC_PLANE16 + wp_] = o;
       }
@@ -603,7 +564,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep16(DeepArgs a) {
       };
 #pragma unroll
       for (int f = 0; f < PD - 1; ++f) pring[f] = pfrag(f);
-      sfor<NW>([&](auto ic) {
+      static_for<NW>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
         if constexpr (i == NW - 5) {  // request the next slice's window (as DC_REQ_AT = 27 of 36 in the 32x32x16 kernel)
           if (s + 1 < S) request(s + 1);
@@ -613,7 +574,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep16(DeepArgs a) {
           wring[(i + WD - 1) % WD][0] = wfrag(i + WD - 1, 0);
           wring[(i + WD - 1) % WD][1] = wfrag(i + WD - 1, 1);
         }
-        sfor<NPF>([&](auto bc) {
+        static_for<NPF>([&](auto bc) {
           constexpr int bh = decltype(bc)::value, f = i * NPF + bh, b = bh >> 1, h = bh & 1;
           if constexpr (f + PD - 1 < NF) pring[(f + PD - 1) % PD] = pfrag(f + PD - 1);
           acc[b][0][h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wring[i % WD][0], pring[f % PD], acc[b][0][h], 0, 0, 0);
@@ -635,8 +596,8 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep16(DeepArgs a) {
         const bool ok = q0 + b * 32 + h * 16 + c16 < a.q_end && y < a.H && x >= 0 && x < a.W && n < a.N;
         if (ok)
           a.out[(unsigned)(((n * a.H + y) * a.W + x) * ocs + (c0 >> 3))] =
-              make_uint4(dc_pack2(acc[b][0][h][0], acc[b][0][h][1]), dc_pack2(acc[b][0][h][2], acc[b][0][h][3]),
-                         dc_pack2(acc[b][1][h][0], acc[b][1][h][1]), dc_pack2(acc[b][1][h][2], acc[b][1][h][3]));
+              make_uint4(cv_pack2(acc[b][0][h][0], acc[b][0][h][1]), cv_pack2(acc[b][0][h][2], acc[b][0][h][3]),
+                         cv_pack2(acc[b][1][h][0], acc[b][1][h][1]), cv_pack2(acc[b][1][h][2], acc[b][1][h][3]));
       }
   }
 }
@@ -659,7 +620,7 @@ __global__ void k_pack_deep16(const float* __restrict__ w, int cout, int cin, un
   const int co = cb * 32 + 8 * (r >> 2) + 4 * aa + (r & 3);
   const int ci = 64 * (k32 >> 1) + 8 * (2 * (k32 & 1) + (kg >> 1) + 4 * (kg & 1)) + j;
   const float v = w[((size_t)co * cin + ci) * 9 + tap];
-  out[i] = (unsigned short)(dc_pack2(v, 0.f) & 0xffffu);
+  out[i] = (unsigned short)cv_f2bf(v);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -736,7 +697,7 @@ __global__ __launch_bounds__(256 + DL_LT, 1) void k_conv3x3_deep_ls(DeepArgs a) 
         f32x2_t shs[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) shs[q] = ((later >> k) & 1u) ? sh1[q] : sh[q];
-        planes[oct * DC_PLANE + wp_] = dc_act8(rawbuf[k * DL_LT + lt], sc, shs, 0u - ((inside >> k) & 1u));
+        planes[oct * DC_PLANE + wp_] = conv_act8(rawbuf[k * DL_LT + lt], sc, shs, 0u - ((inside >> k) & 1u));
       }
     };
     // slice g of the workgroup = (tile g / S, slice g % S); prepared one barrier ahead of its MFMAs
@@ -794,10 +755,10 @@ __global__ __launch_bounds__(256 + DL_LT, 1) void k_conv3x3_deep_ls(DeepArgs a) 
       };
 #pragma unroll
       for (int f = 0; f < DC_PDEPTH - 1; ++f) pring[f] = pfrag(f);
-      sfor<NW>([&](auto ic) {
+      static_for<NW>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
         if constexpr (i + DC_WDEPTH - 1 < NW) wring[(i + DC_WDEPTH - 1) % DC_WDEPTH] = wfrag(i + DC_WDEPTH - 1);
-        sfor<DC_NB>([&](auto bc) {
+        static_for<DC_NB>([&](auto bc) {
           constexpr int b = decltype(bc)::value, f = i * DC_NB + b;
           if constexpr (f + DC_PDEPTH - 1 < NF) pring[(f + DC_PDEPTH - 1) % DC_PDEPTH] = pfrag(f + DC_PDEPTH - 1);
           acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wring[i % DC_WDEPTH], pring[f % DC_PDEPTH], acc[b], 0, 0, 0);
@@ -828,11 +789,11 @@ __global__ void k_maxpool2(const uint4* __restrict__ in, uint4* __restrict__ out
     for (int k = 0; k < 4; ++k) {
       const unsigned w[4] = {k == 0 ? v[0].x : k == 1 ? v[0].y : k == 2 ? v[0].z : v[0].w, k == 0 ? v[1].x : k == 1 ? v[1].y : k == 2 ? v[1].z : v[1].w,
                              k == 0 ? v[2].x : k == 1 ? v[2].y : k == 2 ? v[2].z : v[2].w, k == 0 ? v[3].x : k == 1 ? v[3].y : k == 2 ? v[3].z : v[3].w};
-      float lo = dc_bf2f(w[0] & 0xffffu), hi = dc_bf2f(w[0] >> 16);
+      float lo = cv_bf2f(w[0] & 0xffffu), hi = cv_bf2f(w[0] >> 16);
 #pragma unroll
       for (int j = 1; j < 4; ++j) {
-        lo = fmaxf(lo, dc_bf2f(w[j] & 0xffffu));
-        hi = fmaxf(hi, dc_bf2f(w[j] >> 16));
+        lo = fmaxf(lo, cv_bf2f(w[j] & 0xffffu));
+        hi = fmaxf(hi, cv_bf2f(w[j] >> 16));
       }
       r[k] = (__float_as_uint(lo) >> 16) | (__float_as_uint(hi) & 0xffff0000u);
     }
