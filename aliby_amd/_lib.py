@@ -156,6 +156,10 @@ _SIGNATURES = {
                                          _vp, _i, _i, _vp]),
     "aliby_features_nuc_conv_3d": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, C.c_double, C.c_double, _vp, _i, _i, _vp]),
     "aliby_features_neighbors": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i, _i, _vp]),
+    "aliby_relate_workspace_bytes": (_sz, [_i, _i]),
+    "aliby_features_relate": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i,
+                                   _vp, _i, _i, _vp]),
+    "aliby_tertiary_labels": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "aliby_features_cell": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "aliby_features_coloc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i,
                                   C.c_double, C.c_double, _vp, _vp, _vp]),

@@ -45,11 +45,30 @@ struct NeighborsBitmap {
   }
 };
 
-// a row without pixels: NaN in columns 0-1 and in the centre, which is how k_neighbors_closest knows it
+// a row without pixels: NaN in columns 0-1 and in the centre, which is how k_neighbors_closest knows it (and how the kernels of
+// feat_relate.hip know an absent object of either set)
+template <int DIM>
+__device__ __forceinline__ void neighbors_absent_centre(double* ctr) {
+  for (int k = DIM; k-- > 0;) ctr[k] = NAN;
+}
 template <int DIM>
 __device__ __forceinline__ void neighbors_absent(double* out, double* ctr) {
-  for (int k = DIM; k-- > 0;) ctr[k] = NAN;
+  neighbors_absent_centre<DIM>(ctr);
   out[0] = out[1] = NAN;
+}
+
+// A centre coordinate: the exact 64-bit coordinate sum over the pixel count, one float64 division.  (feat_relate.hip takes its centres
+// from here too.)
+__device__ __forceinline__ double neighbors_centre(long long s, int n) { return (double)s / (double)n; }
+
+// The outline predicate of the 2-D family as a function of one pixel: (y, x) of the tile `lab` [Y,X] holds L; it is on L's outline
+// when it lies on the first or last row or column of the frame or has an 8-neighbour of another value (0 included).
+// k_neighbors_scan finds the same thing inside its walk over the offsets of T, which contain the 3 x 3 square; the kernels that walk
+// no offsets (feat_relate.hip: the minimum distance to a parent's outline, the tertiary image) call this.
+__device__ __forceinline__ bool neighbors_outline(const unsigned short* lab, int Y, int X, int y, int x, int L) {
+  if (y == 0 || y == Y - 1 || x == 0 || x == X - 1) return true;
+  const unsigned short* r = lab + (size_t)y * X + x;
+  return r[-X - 1] != L || r[-X] != L || r[-X + 1] != L || r[-1] != L || r[1] != L || r[X - 1] != L || r[X] != L || r[X + 1] != L;
 }
 
 // The end of a scan kernel, on thread 0 after the block reductions: cnt bits set, n pixels of the object, `outline` of them on its
@@ -59,7 +78,7 @@ __device__ __forceinline__ void neighbors_scan_write(double* out, double* ctr, i
   if (n == 0) return neighbors_absent<sizeof...(Sum)>(out, ctr);  // (a row whose area the labels do not bear out: absent)
   out[0] = (double)cnt;
   out[1] = (double)touching / (double)outline * 100.0;
-  ((*ctr++ = (double)s / (double)n), ...);
+  ((*ctr++ = neighbors_centre(s, n)), ...);
 }
 
 // The two best (key, label) candidates under the order "lower key, then lower label": a total order on distinct labels, so the

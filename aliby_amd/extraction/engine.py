@@ -710,6 +710,59 @@ class FeatureEngine:
                 int(np.diff(table.offsets).max()), d, _ptr(centres), _ptr(out), out.stride(0), col0, _stream_ptr()))
         return 7
 
+    @staticmethod
+    def _offsets_dev(table: ObjectTable, device) -> torch.Tensor:
+        offsets_dev = getattr(table, "_offsets_dev", None)
+        if offsets_dev is None:
+            offsets_dev = table._offsets_dev = torch.from_numpy(np.ascontiguousarray(table.offsets, dtype=np.int32)).to(device)
+        return offsets_dev
+
+    def relate(self, labels_a, table_a: ObjectTable, labels_b, table_b: ObjectTable, out_a=None, col0_a=0, out_b=None, col0_b=0):
+        """Two label blocks uint16 [F,Y,X] of one shape with their object tables -> (matrix_a, matrix_b), float64 [n, 5] each: the rows
+        of A relative to B and of B relative to A (features.relate_names(other); aliby_features_relate) — CellProfiler's RelateObjects:
+        the parent (most shared pixels, ties to the smaller label, 0 = none), that overlap, the number of children, the distance
+        between the centres and from the centre to the parent's outline (NaN without a parent).  out_a / out_b: matrices [n, .] to
+        write columns col0..col0+4 of instead of new ones (the returned matrix is then that window).  Differing F, Y or X is a
+        ValueError.  PARITY UNPINNED; the definition and what is not built are in include/aliby_hip.h.  May use the context's scratch
+        (tiles of more than 8191 labels)."""
+        if tuple(labels_a.shape) != tuple(labels_b.shape) or labels_a.ndim != 3:
+            raise ValueError(f"relate: the two label blocks must share one shape [F,Y,X], got {tuple(labels_a.shape)} and {tuple(labels_b.shape)}")
+        F, Y, X = labels_a.shape
+        if len(table_a.offsets) != F + 1 or len(table_b.offsets) != F + 1:
+            raise ValueError(f"relate: the object tables are not those of {F} tiles")
+        if out_a is None:
+            out_a, col0_a = self.new_output(table_a.n_obj, 5), 0
+        if out_b is None:
+            out_b, col0_b = self.new_output(table_b.n_obj, 5), 0
+        if table_a.n_obj or table_b.n_obj:
+            # (a multiple of 8 bytes; float64 elements keep it 8-byte aligned)
+            work = torch.empty(int(self.lib.aliby_relate_workspace_bytes(table_a.n_obj, table_b.n_obj)) // 8, dtype=torch.float64,
+                               device=labels_a.device)
+            with self.timed("relate"):
+                _lib.check(self.lib.aliby_features_relate(
+                    self.ctx.handle, _ptr(labels_a), _ptr(labels_b), F, Y, X,
+                    _ptr(table_a.dev), table_a.n_obj, table_a.max_h, table_a.max_w, _ptr(table_b.dev), table_b.n_obj, table_b.max_h, table_b.max_w,
+                    _ptr(self._offsets_dev(table_a, labels_a.device)), int(np.diff(table_a.offsets).max()),
+                    _ptr(self._offsets_dev(table_b, labels_b.device)), int(np.diff(table_b.offsets).max()), _ptr(work),
+                    _ptr(out_a) if table_a.n_obj else 0, out_a.stride(0) if table_a.n_obj else 5, col0_a,
+                    _ptr(out_b) if table_b.n_obj else 0, out_b.stride(0) if table_b.n_obj else 5, col0_b, _stream_ptr()))
+        return out_a[:, col0_a:col0_a + 5], out_b[:, col0_b:col0_b + 5]
+
+    def tertiary_labels(self, outer, inner, shrink_inner: bool = True) -> torch.Tensor:
+        """outer, inner uint16 [F,Y,X] of one shape -> device uint16 [F,Y,X] (aliby_tertiary_labels): outer's labels where inner is 0
+        or, with shrink_inner, on the outline of an inner object; 0 elsewhere — CellProfiler's IdentifyTertiaryObjects (the cytoplasm
+        = cell minus nucleus).  Labels keep outer's numbering; one that loses every pixel is absent.  PARITY UNPINNED
+        (include/aliby_hip.h)."""
+        if tuple(outer.shape) != tuple(inner.shape) or outer.ndim != 3:
+            raise ValueError(f"tertiary_labels: outer and inner must share one shape [F,Y,X], got {tuple(outer.shape)} and {tuple(inner.shape)}")
+        F, Y, X = outer.shape
+        out = torch.empty_like(outer)
+        if out.numel():
+            with self.timed("tertiary"):
+                _lib.check(self.lib.aliby_tertiary_labels(self.ctx.handle, _ptr(outer), _ptr(inner), F, Y, X, 1 if shrink_inner else 0,
+                                                          _ptr(out), _stream_ptr()))
+        return out
+
     def zernike(self, labels, planes, dtype, channel, table: ObjectTable, out, col0, weighted: bool):
         F, Y, X = labels.shape
         Cn = planes.shape[1] if planes is not None else 0

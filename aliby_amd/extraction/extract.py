@@ -323,6 +323,66 @@ def process_tree_masks(tree, masks, pixels, measure_fn, ncores=None, progress_ba
     return tuple(lazy), result
 
 
+RELATE_INSTRUCTION = ("None", "None", "relate")  # the one instruction of an `extractrelate_<obj>` step: columns None/None/relate/<name>
+
+
+def _tile_list(who: str, masks) -> list:
+    """What a segment step returns — one [Y,X] label image, or a per_tile list of them — as a list of tiles."""
+    tiles = list(masks) if isinstance(masks, (list, tuple)) else [masks]
+    if not tiles:
+        raise ValueError(f"{who}: no tiles")
+    return tiles
+
+
+def _paired_labels(who: str, first, second, names):
+    """Two segment results of one position -> their device label blocks uint16 [F,Y,X], checked for one tile count and shape."""
+    a, b = _tile_list(who, first), _tile_list(who, second)
+    if len(a) != len(b):
+        raise ValueError(f"{who}: '{names[0]}' has {len(a)} tiles, '{names[1]}' {len(b)}")
+    la, lb = _stack_masks(a), _stack_masks(b)
+    if tuple(la.shape) != tuple(lb.shape):
+        raise ValueError(f"{who}: '{names[0]}' is {tuple(la.shape)} [F,Y,X], '{names[1]}' {tuple(lb.shape)}: they do not match")
+    return la, lb
+
+
+def tertiary_masks(outer, inner, shrink_inner=True, who="tertiary"):
+    """The tertiary labels of two segment results (FeatureEngine.tertiary_labels: `outer` minus the objects of `inner`; the cytoplasm
+    is cells minus nuclei) in the container `outer` came in: one [Y,X] uint16 image or a list of them, each with its device copy
+    attached (devcache, kind="labels"), so that an extract step after it measures them as it measures a segment step's."""
+    from aliby_amd.extraction.engine import FeatureEngine
+
+    lo, li = _paired_labels(who, outer, inner, ("outer", "inner"))
+    dev = FeatureEngine().tertiary_labels(lo, li, shrink_inner=bool(shrink_inner))
+    host = dev.cpu().numpy()
+    tiles = [devcache.attach(host[k], dev[k], kind="labels") for k in range(host.shape[0])]
+    return tiles if isinstance(outer, (list, tuple)) else tiles[0]
+
+
+def relate_masks(masks, others: dict, who="extractrelate"):
+    """The rows of the objects of `masks` relative to every object set of `others` {name: its segment result}: returns
+    (tileid_instructions, results) like process_tree_masks, with the single instruction RELATE_INSTRUCTION and the columns
+    features.relate_names(name) of all names side by side; objects are every (tile, label) of `masks`."""
+    from aliby_amd.extraction.engine import FeatureEngine
+
+    eng = FeatureEngine()
+    names, matrices, table = [], [], None
+    for other, other_masks in others.items():
+        la, lb = _paired_labels(who, masks, other_masks, ("masks", f"masks_{other}"))
+        if table is None:
+            table = eng.object_table(la)
+        rows, _ = eng.relate(la, table, lb, eng.object_table(lb))
+        names.extend(feat.relate_names(other))
+        matrices.append(rows)
+    if table is None or table.n_obj == 0:
+        return (), []
+    import torch
+
+    matrix = eng.to_host(matrices[0] if len(matrices) == 1 else torch.cat(matrices, 1))
+    objects = [(int(t), int(l)) for t, l in zip(table.host["tile"], table.host["label"])]
+    lazy = LazyProduct(objects, [RELATE_INSTRUCTION])
+    return tuple(lazy), DeviceResults(matrix, objects, [RELATE_INSTRUCTION], [(0, names)])
+
+
 def _device_volumes(volumes):
     """Volume labels -> device uint16 [F,Z,Y,X]: a device tensor [F,Z,Y,X], a host array [Z,Y,X] or [F,Z,Y,X], or a list of [Z,Y,X]."""
     import torch

@@ -176,6 +176,21 @@ def neighbors_names(distance=None) -> list[str]:
     return _neighbors_names("Adjacent" if distance is None else str(neighbors_distance(distance)))
 
 
+def relate_names(other: str) -> list[str]:
+    """Columns of `FeatureEngine.relate` for rows related to the object set `other` (csrc/feat_relate.hip): CellProfiler's
+    RelateObjects — the parent in `other`, the overlap that chose it, the number of children in `other`, the distance between the
+    centres and the distance from the centre to the parent's outline.  PARITY UNPINNED: the definition (include/aliby_hip.h,
+    tests/relate_ref.py) is recalled from CellProfiler 4 and centrosome, neither of which can be run beside this package.
+    ParentOverlap is an extension.  `other` is a non-empty string without "_" (a step's object name is what follows the last "_"
+    of its name) and without "/" (the column separator): anything else is a ValueError.  Needs no device.
+    Not built: per-parent means of child measurements, "Expand until adjacent" and `neighbors` against a second object set, volume
+    (3-D) relation, the batched run_positions form."""
+    if not isinstance(other, str) or not other or "_" in other or "/" in other:
+        raise ValueError(f"relate: the other object set's name must be a non-empty string without '_' or '/', got {other!r}")
+    return [f"Parent_{other}", f"ParentOverlap_{other}", f"Children_{other}_Count", f"Distance_Centroid_{other}",
+            f"Distance_Minimum_{other}"]
+
+
 COLOC = {
     "pearson": ["Correlation_Pearson", "Correlation_Slope"],
     "manders_fold": ["Correlation_Manders_1", "Correlation_Manders_2"],

@@ -85,6 +85,37 @@ def nuc_conv_3d(cell_mask, trap_image, pixel_size=0.23, z_spacing=0.6) -> float:
     return float(out[0, 0])
 
 
+def _label_tile(name: str, labels):
+    labels = np.asarray(labels)
+    if labels.ndim != 2:
+        raise ValueError(f"{name} must be one [Y, X] label image, got shape {labels.shape}")
+    return to_device_u16(labels[None])
+
+
+def relate_objects(child_labels, parent_labels):
+    """Two label images [Y, X] of one tile (0 = background, labels 1..n) -> (children, parents), float64 [n, 5] each on the host: the
+    rows of the first set relative to the second and of the second relative to the first, columns as `features.relate_names`
+    (Parent, ParentOverlap, Children count, Distance_Centroid, Distance_Minimum; FeatureEngine.relate, csrc/feat_relate.hip).  Not in
+    the reference: CellProfiler's RelateObjects, PARITY UNPINNED (include/aliby_hip.h)."""
+    a, b = _label_tile("child_labels", child_labels), _label_tile("parent_labels", parent_labels)
+    if a.shape != b.shape:
+        raise ValueError(f"child_labels {tuple(a.shape[1:])} and parent_labels {tuple(b.shape[1:])} differ in shape")
+    eng = FeatureEngine()
+    rows_a, rows_b = eng.relate(a, eng.object_table(a), b, eng.object_table(b))
+    return eng.to_host(rows_a), eng.to_host(rows_b)
+
+
+def tertiary_objects(outer, inner, shrink_inner=True) -> np.ndarray:
+    """Two label images [Y, X] of one tile -> uint16 [Y, X]: `outer`'s labels where `inner` is 0 or, with shrink_inner, on the outline
+    of an inner object; 0 elsewhere (FeatureEngine.tertiary_labels, csrc/feat_relate.hip).  The cytoplasm is
+    tertiary_objects(cells, nuclei).  Not in the reference: CellProfiler's IdentifyTertiaryObjects, PARITY UNPINNED."""
+    a, b = _label_tile("outer", outer), _label_tile("inner", inner)
+    if a.shape != b.shape:
+        raise ValueError(f"outer {tuple(a.shape[1:])} and inner {tuple(b.shape[1:])} differ in shape")
+    eng = FeatureEngine()
+    return eng.tertiary_labels(a, b, shrink_inner=shrink_inner)[0].cpu().numpy()
+
+
 def _background(cell_masks, trap_image):
     trap_image = _as_pixels(trap_image)
     if not len(cell_masks):

@@ -90,9 +90,20 @@ def refuse_volume_pipelines(pipelines) -> None:
                                           "aliby_amd.pipe.run_pipeline_and_post")
 
 
+def refuse_object_link_pipelines(pipelines) -> None:
+    """The batched runner knows no step that reads two object sets together (`tertiary_`, `extractrelate_`): a pipeline with one is
+    refused up front, before any position is read."""
+    for pipeline in pipelines:
+        for name in (pipeline.get("steps", {}) if isinstance(pipeline, dict) else {}):
+            if name.startswith(("tertiary_", "extractrelate_")):
+                raise NotImplementedError(f"run_positions has no batched form of step '{name}' (a 'tertiary_' or 'extractrelate_' step): "
+                                          "run such a pipeline position by position with aliby_amd.pipe.run_pipeline_and_post")
+
+
 def run_positions(pipelines, names, output_path, **kwargs):
     """Many positions behind the step API, B per device step, sharded i % world == rank: see aliby_amd/runner.py."""
     refuse_volume_pipelines(pipelines)
+    refuse_object_link_pipelines(pipelines)
     from aliby_amd.runner import run_positions as _run
 
     return _run(pipelines, names, output_path, **kwargs)

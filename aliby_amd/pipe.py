@@ -37,6 +37,10 @@ _PREFIXES = (
     ("track", _tracker),
     ("extract_", lambda name, params, done: core._init_extract(name, params, overlap=False)),
     ("extractmulti_", lambda name, params, done: core._init_extract_multi(name, params)),
+    # two object sets of one tile read together (extensions; csrc/feat_relate.hip): a tertiary compartment's labels, measured by the
+    # extract steps after it like a segment step's, and the parent / children / distance rows of one object set relative to others
+    ("tertiary_", lambda name, params, done: core._init_tertiary(name, params)),
+    ("extractrelate_", lambda name, params, done: core._init_relate(name, params)),
     # (not an "extract" prefix: every step that starts with "extract" is joined to the 2-D rows on metadata_label, which would pair
     # volume label k with 2-D label k; the volume rows get their own table, profiles3d/)
     ("volume_", lambda name, params, done: core._init_volume(name, params, done)),

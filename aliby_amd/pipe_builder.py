@@ -29,6 +29,31 @@ def _create_extract_multich_tree(channels, extract_ncores, cp_measure_feature_kw
     return {"tree": tree, "kwargs": _step_kwargs(extract_ncores, cp_measure_feature_kwargs)}
 
 
+def _object_links(objects, relate, tertiary):
+    """The `relate` and `tertiary` keywords of build_pipeline_steps, checked against the object sets: ({obj: [partners]} in first-seen
+    order, {name: (outer, inner)})."""
+    from aliby_amd.extraction.features import relate_names
+
+    tertiary = dict(tertiary or {})
+    for name, pair in tertiary.items():
+        relate_names(name)  # (a name that a step name or a column name cannot carry)
+        if name in objects:
+            raise ValueError(f"tertiary: '{name}' is already a segmented object set")
+        if not isinstance(pair, (tuple, list)) or len(pair) != 2 or pair[0] == pair[1] or any(o not in objects for o in pair):
+            raise ValueError(f"tertiary['{name}'] must be (outer, inner), two different object sets of {objects}, got {pair!r}")
+    related: dict[str, list] = {}
+    for pair in relate or ():
+        if not isinstance(pair, (tuple, list)) or len(pair) != 2 or pair[0] == pair[1]:
+            raise ValueError(f"relate: every entry is a pair (a, b) of two different object sets, got {pair!r}")
+        for a, b in (pair, pair[::-1]):
+            if a not in objects and a not in tertiary:
+                raise ValueError(f"relate: '{a}' is not an object set of {[*objects, *tertiary]}")
+            relate_names(a)
+            if b not in related.setdefault(a, []):
+                related[a].append(b)
+    return related, {name: tuple(pair) for name, pair in tertiary.items()}
+
+
 def build_pipeline_steps(
     channels_to_segment: dict[str, int] | None = None,
     channels_to_extract: Sequence[int] | None = None,
@@ -42,6 +67,8 @@ def build_pipeline_steps(
     *,
     volume_features: Sequence[str] | None = None,
     volume_coloc: bool = False,
+    relate: Sequence[tuple[str, str]] | None = None,
+    tertiary: dict[str, tuple[str, str]] | None = None,
 ) -> dict:
     """Extension (not in the reference): `volume_features`, a sequence of per-channel volume family names
     (extraction.families.VOLUME: "intensity3d", "intensity3d_detail", "texture3d", "granularity3d"), makes every segment step
@@ -49,17 +76,29 @@ def build_pipeline_steps(
     given names under every channel of `channels_to_extract`, and with `volume_coloc=True` COLOC_METRICS under every channel
     pair.  Its rows go to profiles3d/<name>.parquet; the extract steps stay and measure the collapse, so profiles/ is the
     reference-faithful table and profiles3d/ the true 3-D one, joined on (metadata_tp, metadata_tile, metadata_object,
-    Projection_Label = metadata_label).  With the default None the dict is the reference's."""
+    Projection_Label = metadata_label).  With the default None the dict is the reference's.
+
+    Extensions (not in the reference; CellProfiler's RelateObjects and IdentifyTertiaryObjects, csrc/feat_relate.hip): `relate`, pairs
+    (a, b) of object sets, adds an `extractrelate_<obj>` step per object set named in a pair, which relates it to its partners in both
+    directions (columns None/None/relate/Parent_<other>, ... on the rows of <obj>).  `tertiary`, {name: (outer, inner)}, adds a
+    `tertiary_<name>` step right after the segment steps (outer's labels minus inner's objects: {"cytoplasm": ("cell", "nuclei")}),
+    saved like them, and `extract_<name>` / `extractmulti_<name>` steps with the shared specs: rows with metadata_object = <name>
+    whose metadata_label is the outer object's.  A name that is not an object set is a ValueError.  With both None the dict is the
+    reference's."""
     if channels_to_segment is None:
         channels_to_segment = {"nuclei": 1, "cell": 0}
     kind = "cellpose" if nahual_addresses is None else "nahual_cellpose"
     if channels_to_extract is None:
         channels_to_extract = list(channels_to_segment.values())
     objects = list(channels_to_segment)
+    related, tertiary = _object_links(objects, relate, tertiary)
+    producer = {obj: f"segment_{obj}" for obj in objects} | {name: f"tertiary_{name}" for name in tertiary}
 
     steps = {"tile": {"tile_size": None}}
     for obj, ch in channels_to_segment.items():
         steps[f"segment_{obj}"] = {"segmenter_kwargs": {"kind": kind}, "channel_to_segment": ch}
+    for name in tertiary:
+        steps[f"tertiary_{name}"] = {"shrink_inner": True}
 
     # the single-channel spec is shared by every object set (as in the reference, where both
     # extract_<obj> entries point at the same dict)
@@ -70,20 +109,26 @@ def build_pipeline_steps(
     multi = _create_extract_multich_tree(channels_to_extract, extract_ncores, cp_measure_feature_kwargs)
     for prefix, spec in (("extract", mono), ("extractmulti", multi)):
         if len(spec):
-            for obj in objects:
+            for obj in (*objects, *tertiary):
                 steps[f"{prefix}_{obj}"] = spec
+    for obj, others in related.items():
+        steps[f"extractrelate_{obj}"] = {"others": others, "kwargs": _step_kwargs(extract_ncores, cp_measure_feature_kwargs)}
 
     pipeline = {
         "steps": steps,
         "passed_data": {
-            f"extract{m}_{obj}": [("masks", f"segment_{obj}"), ("pixels", "tile")]
-            for obj in objects
+            f"extract{m}_{obj}": [("masks", producer[obj]), ("pixels", "tile")]
+            for obj in (*objects, *tertiary)
             for m in ("", "multi")
         },
         "passed_methods": {f"segment_{obj}": ("tile", "get_fczyx") for obj in objects},
-        "save": [f"segment_{obj}" for obj in objects],
+        "save": [producer[obj] for obj in (*objects, *tertiary)],
         "save_interval": 1,
     }
+    for name, (outer, inner) in tertiary.items():
+        pipeline["passed_data"][f"tertiary_{name}"] = [("masks", f"segment_{outer}", "outer"), ("masks", f"segment_{inner}", "inner")]
+    for obj, others in related.items():
+        pipeline["passed_data"][f"extractrelate_{obj}"] = [("masks", producer[obj])] + [("masks", producer[o], f"masks_{o}") for o in others]
     if volume_features is not None:
         tree = {"None": {"None": ["sizeshape3d", "projection3d"]}}
         for ch in channels_to_extract:

@@ -116,6 +116,75 @@ def _init_volume(step_name: str, parameters: dict, other_steps: dict) -> Callabl
     return volume_step
 
 
+def _relate_others(step_name: str, parameters: dict) -> list:
+    """The `others` of an `extractrelate_<obj>` step: a non-empty sequence of distinct object-set names that make column names."""
+    from aliby_amd.extraction import features
+
+    others = _need(parameters, "others", step_name)
+    if isinstance(others, str) or not isinstance(others, (list, tuple)) or not others or len(set(others)) != len(others):
+        raise ValueError(f"Step '{step_name}': 'others' must be a non-empty sequence of distinct object-set names, got {others!r}.")
+    for other in others:
+        features.relate_names(other)  # (refuses what cannot be told apart in a column or step name)
+    return list(others)
+
+
+def _init_relate(step_name: str, parameters: dict) -> Callable:
+    """An `extractrelate_<obj>` step: the rows of <obj>'s objects relative to every object set of `others` (CellProfiler's
+    RelateObjects; extraction.extract.relate_masks).  Inputs: `masks` = <obj>'s segment result, `masks_<other>` = the other set's,
+    through aliased `passed_data` entries.  It returns (tileid_instructions, results) with the one instruction None/None/relate; the
+    profile table joins the rows onto <obj>'s extract rows."""
+    from aliby_amd.extraction.extract import relate_masks
+
+    others = _relate_others(step_name, parameters)  # (`kwargs`: the extract steps' ncores / cp_measure_kwargs; nothing here reads them)
+
+    def relate_step(masks=None, **inputs):
+        missing = [f"masks_{o}" for o in others if inputs.get(f"masks_{o}") is None]
+        if masks is None or missing:
+            raise ValueError(f"Step '{step_name}': no input for {['masks'] * (masks is None) + missing}: 'passed_data' must hand it "
+                             "'masks' and one aliased 'masks_<other>' per entry of 'others', from steps that ran before it.")
+        return relate_masks(masks, {o: inputs[f"masks_{o}"] for o in others}, who=f"Step '{step_name}'")
+
+    return relate_step
+
+
+def _init_tertiary(step_name: str, parameters: dict) -> Callable:
+    """A `tertiary_<name>` step: the labels of the `outer` object set minus the objects of the `inner` one (CellProfiler's
+    IdentifyTertiaryObjects: the cytoplasm; extraction.extract.tertiary_masks), in the container the outer segment step returned, so
+    that `extract_<name>` / `extractmulti_<name>` steps measure it like a segment step's labels.  `shrink_inner` (default True)
+    leaves the inner objects' outlines in."""
+    from aliby_amd.extraction.extract import tertiary_masks
+
+    unknown = set(parameters) - {"shrink_inner"}
+    if unknown:
+        raise ValueError(f"Step '{step_name}': unknown parameters {sorted(unknown)}.")
+    shrink = parameters.get("shrink_inner", True)
+    if not isinstance(shrink, bool):
+        raise ValueError(f"Step '{step_name}': 'shrink_inner' must be a bool, got {shrink!r}.")
+
+    def tertiary_step(outer=None, inner=None):
+        if outer is None or inner is None:
+            raise ValueError(f"Step '{step_name}': no input for {['outer'] * (outer is None) + ['inner'] * (inner is None)}: "
+                             "'passed_data' must hand it the masks of two segment steps under the aliases 'outer' and 'inner'.")
+        return tertiary_masks(outer, inner, shrink_inner=shrink, who=f"Step '{step_name}'")
+
+    return tertiary_step
+
+
+def _check_object_links(steps: dict, passed_data: dict) -> None:
+    """The wiring of the two-object-set steps, before any timepoint: every input they need is an aliased `passed_data` entry."""
+    for name, params in steps.items():
+        if name.startswith("extractrelate_") and isinstance(params, dict):
+            wanted = ["masks"] + [f"masks_{o}" for o in _relate_others(name, params)]
+        elif name.startswith("tertiary_"):
+            wanted = ["outer", "inner"]
+        else:
+            continue
+        have = {dep[2] if len(dep) > 2 else dep[0] for dep in passed_data.get(name, ())}
+        missing = [w for w in wanted if w not in have]
+        if missing:
+            raise ValueError(f"Step '{name}' needs the inputs {missing} in 'passed_data' (entries ('masks', <segment step>, <alias>)).")
+
+
 def _init_nahual(step_name: str, parameters: dict) -> Callable:
     if parameters.get("address") is None:
         raise ValueError(f"If using Nahual you must have an address, currently it is None in step '{step_name}'")
@@ -200,6 +269,7 @@ def validate_pipeline(pipeline: dict) -> None:
             raise TypeError(f"Parameters for step '{name}' must be a dictionary.")
         if name.startswith("nahual") and "address" not in params:
             raise ValueError(f"Nahual-deployed step '{name}' must provide an 'address' parameter.")
+    _check_object_links(steps, passed_data)
     if pipeline.get("global_steps"):
         if "global_passed_data" not in pipeline:
             raise ValueError("Pipeline defines 'global_steps' but is missing 'global_passed_data'.")
@@ -373,13 +443,32 @@ def get_profiles_from_state(state: dict, pipeline: dict) -> pa.Table:
             table = _wide_table(name, tp, output)
             if table is not None:
                 bucket.append(table)
+    # the `extractrelate` steps of different object sets carry different columns (Parent_cell on nuclei rows, Parent_nuclei on cell
+    # rows): that prefix alone is concatenated with its schemas unified, null-filled, and joined after the others
+    related = by_prefix.pop(_RELATE_PREFIX, None)
     merged = [pa.concat_tables(tables) for tables in by_prefix.values() if tables]
-    if not merged:
+    if not merged and not related:
         return _empty_profiles()
+    if related:
+        merged.append(pa.concat_tables(related, promote_options="default"))
     profiles = merged[0]
-    for other in merged[1:]:
-        profiles = _join_on_metadata(profiles, other)
+    for k, other in enumerate(merged[1:], 1):
+        profiles = _join_related(profiles, other) if related and k == len(merged) - 1 else _join_on_metadata(profiles, other)
     return profiles
+
+
+_RELATE_PREFIX = "extractrelate"
+
+
+def _join_related(left: pa.Table, right: pa.Table) -> pa.Table:
+    """The `extractrelate` rows onto the rows of the extract steps: a left join on the metadata columns that keeps the left table's
+    row order (rows without a relation — a tertiary compartment's — get nulls)."""
+    joined = _join_on_metadata(left, right, strict=True)
+    if joined is not None:
+        return joined
+    order = "__row__"
+    numbered = left.append_column(order, pa.array(numpy.arange(left.num_rows, dtype=numpy.int64)))
+    return numbered.join(right, keys=[f"metadata_{k}" for k in _META_KEYS]).sort_by(order).drop_columns([order])
 
 
 def get_volume_profiles_from_state(state: dict, pipeline: dict) -> pa.Table:

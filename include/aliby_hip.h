@@ -519,6 +519,57 @@ int aliby_features_nuc_conv_3d(aliby_ctx* ctx, const uint16_t* labels, const voi
 int aliby_features_neighbors(aliby_ctx* ctx, const uint16_t* labels, int F, int Y, int X, const aliby_object* table_dev, int n_obj,
                              int max_h, int max_w, const int32_t* offsets_dev, int max_count, int distance, double* centres_dev,
                              double* out, int ld, int col0, void* stream);
+/* "relate": two object sets of one tile read together — CellProfiler's RelateObjects and IdentifyTertiaryObjects.  PARITY UNPINNED:
+ * recalled from CellProfiler 4's relateobjects.py and identifytertiaryobjects.py and centrosome's outline, none of which can be run
+ * beside this library (tests/relate_ref.py restates it).
+ * Per tile, A and B are two label images of one shape [Y,X]: uint16, 0 = background, labels 1..n_A and 1..n_B, a label may be absent
+ * (area 0).  Row L of A relative to B, out[row * ld + col0 + k], k = 0..4:
+ *   0 Parent: the label p >= 1 of B that covers the most pixels of L, ties to the smallest p; 0 when no pixel of L has a non-zero B
+ *     label, or when L is absent
+ *   1 ParentOverlap: that pixel count, an exact integer; 0 without a parent (an extension: the number Parent is the argmax of)
+ *   2 Children count: the B objects whose Parent in A, under the same rule with the roles swapped, is L
+ *   3 Distance_Centroid: centres (sum y / area, sum x / area) from exact 64-bit sums and one float64 division each, as the
+ *     `neighbors` family's; dy = py - cy, dx = px - cx (parent minus L), sqrt(dy dy + dx dx); NaN without a parent
+ *   4 Distance_Minimum: the smallest sqrt(dy dy + dx dx) from the centre of L to the centre (y, x) of an outline pixel of its parent,
+ *     dy = y - cy, dx = x - cx: the minimum over the squares first, then one sqrt (order-free).  The outline is the `neighbors`
+ *     family's: pixels of the parent on the first or last row or column of the tile, or with an 8-neighbour of another value.  NaN
+ *     without a parent.
+ * Every float64 operation is rounded on its own (-ffp-contract=off); columns 0-2 are integers.
+ * The tertiary image T(outer, inner, shrink_inner): T[q] = outer[q] where inner[q] == 0, or where shrink_inner is set and q is an
+ * outline pixel of its inner object; 0 elsewhere.  It keeps outer's labels (a row of the new compartment joins its outer object on the
+ * label), removes the interior of ANY inner object, not only the outer object's own child (as CellProfiler does), and a label that
+ * loses all its pixels is simply absent.
+ * Worked example, a 6 x 8 tile.  B = cells: 1 on columns 0..3, 2 on columns 4..7, all rows.  A = nuclei: 1 on rows 1..2 x columns 1..2,
+ * 2 on rows 3..4 x columns 3..4, 3 on row 0 x columns 6..7.
+ *   nucleus  Parent  ParentOverlap  Children  Distance_Centroid  Distance_Minimum
+ *   1        1       4              1         1                  sqrt(2.5)
+ *   2        1       2              1         sqrt(5)            sqrt(0.5)     (a tie, 2 pixels in either cell: the smaller label)
+ *   3        2       2              0         sqrt(7.25)         0.5
+ *   cell     Parent  ParentOverlap  Children
+ *   1        1       4              2
+ *   2        2       2              1                                          (nuclei 2 and 3 tie at 2 pixels)
+ * Tertiary areas of cells 1 and 2: 18 and 20 with shrink_inner = 0; 24 and 24 with shrink_inner = 1 (every pixel of these small
+ * nuclei is an outline pixel).  A 3 x 3 nucleus loses exactly its one interior pixel.
+ * Not built: per-parent means of child measurements, "Expand until adjacent" and `neighbors` against a second object set, volume
+ * (3-D) relation.
+ *
+ * The relate entry fills both directions in one call: rows of A relative to B into out_a, rows of B relative to A into out_b; either
+ * may be NULL (both directions are still computed: column 2 of one needs the parents of the other).  table_*: device tables of the
+ * two label blocks [F,Y,X] with n_* rows and largest boxes max_h_* x max_w_*; offsets_*_dev [dev, F + 1]: their row offsets (row
+ * offsets[tile] + l - 1 is label l); max_count_*: the largest tile's rows, which sizes the per-workgroup counters — one int per
+ * label of the other set's tile, in LDS up to 32 KiB and in ctx scratch above (same bits): no cap on how many objects one object may
+ * meet.  work_dev [dev]: the bytes the workspace function below returns for (n_a, n_b), 8-byte aligned.  A label above its tile's
+ * table count (a wrong max_labels hint) is not counted.  n_a == n_b == 0 launches nothing.  Kernels: csrc/feat_relate.hip. */
+size_t aliby_relate_workspace_bytes(int n_a, int n_b);
+int aliby_features_relate(aliby_ctx* ctx, const uint16_t* labels_a, const uint16_t* labels_b, int F, int Y, int X,
+                          const aliby_object* table_a, int n_a, int max_h_a, int max_w_a, const aliby_object* table_b, int n_b,
+                          int max_h_b, int max_w_b, const int32_t* offsets_a_dev, int max_count_a, const int32_t* offsets_b_dev,
+                          int max_count_b, void* work_dev, double* out_a, int ld_a, int col0_a, double* out_b, int ld_b, int col0_b,
+                          void* stream);
+/* The tertiary image of outer and inner [dev, F x Y x X uint16] into out (same shape; must not alias an input).  One pass, 6 bytes of
+ * algorithmic traffic per pixel; 16-byte accesses where X is a multiple of 8 and the three pointers are 16-byte aligned. */
+int aliby_tertiary_labels(aliby_ctx* ctx, const uint16_t* outer, const uint16_t* inner, int F, int Y, int X, int shrink_inner,
+                          uint16_t* out, void* stream);
 /* trap.imBackground / trap.background_max5 (src/extraction/core/functions/trap.py:6-43): per tile, over the pixels of
  * `channel` under NO mask (labels == 0): out[f*2] = their median (numpy.median), out[f*2+1] = the mean of the five largest
  * (of all of them when fewer); NaN for a tile without background. */
