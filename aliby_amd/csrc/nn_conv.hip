@@ -683,8 +683,10 @@ __global__ __launch_bounds__(256, (DmaCfg<CIN, COUT, UP, PACK>::WAVES_PER_SIMD))
 // into one of two sets of channel-octet planes.  Waves 4-7 (consumers) hold unit B's weights and turn the previous tile's
 // planes into 14 x 30 output pixels (+ residual, + pooled output) meanwhile.  One weight set per wave: no spills, and the
 // consumers' MFMAs overlap the producers' load latency.  Every wave passes the same two barriers per tile:
-//     producers:  stage window(t)        | S1 | unit A -> planes[t & 1]   | S2 |
-//     consumers:  unit B pass 0 of t - 1 | S1 | unit B pass 1 of t - 1    | S2 |
+//     producers:  stage window(t)        | S1 | request window(t + 1), unit A -> planes[t & 1] | S2 |
+//     consumers:  unit B pass 0 of t - 1 | S1 | unit B pass 1 of t - 1                          | S2 |
+// The producers request the next window right after S1 and issue no other vector-memory load before S2 (unit A's bias is in LDS),
+// so the only vmcnt wait that drains the window is the one in front of the next tile's staging.
 // Same bits as the two launches.
 // ------------------------------------------------------------------------------------------------
 struct PairBase {  // the tile geometry k_conv_pair32 and k_conv_first_pair share
@@ -713,6 +715,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_pair32(ConvArgs a) {
   uint4* const ldsIn = lds;
   uint4* const ldsMid0 = lds + NPL * PLANE_IN;
   __shared__ __align__(16) float tabB[64];  // unit B's scale[32], shift[32] of the producers' current tile
+  __shared__ __align__(16) float biasA[32];  // unit A's bias (zeros when NULL), written once: the producers read it after their first S1
   __shared__ float hconst[HEAD ? 2 * 32 + 4 : 1];  // output head: scale, shift, bias (see k_conv3x3)
 
   const int consumer = threadIdx.x >> 8;            // wave-uniform: waves 4-7
@@ -736,7 +739,10 @@ __global__ __launch_bounds__(512, 1) void k_conv_pair32(ConvArgs a) {
     f32x2_t sc[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) sc[k] = f32x2_t{a.scale[pl * 8 + 2 * k], a.scale[pl * 8 + 2 * k + 1]};
-    // the window of tile t + 1 is requested while unit A works on tile t: its loads are in flight behind the MFMA loop
+    if (tid < 32) biasA[tid] = a.bias ? a.bias[tid] : 0.f;
+    // the window of tile t + 1 is requested while unit A works on tile t.  Its loads stay in flight behind the MFMA loop only
+    // because no vector-memory load is issued between request() and S2: vmcnt retires in issue order, so a wait for any younger
+    // load (unit A's bias once was one, reloaded every pass) is a wait for the whole window.  The bias comes from LDS instead.
     uint4 v[ITERS];
     unsigned inside = 0;
     auto request = [&](int tile) {
@@ -786,12 +792,9 @@ __global__ __launch_bounds__(512, 1) void k_conv_pair32(ConvArgs a) {
         const int mbase = (wave * PASSES + pass) * R;  // first intermediate row of this wave and pass (image row y0 - 1 + mbase)
         f32x16_t acc[R];
         {
-          float4 b4[4] = {};
-          if (a.bias) {
-            const float4* bp = reinterpret_cast<const float4*>(a.bias + c0);
+          float4 b4[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) b4[q] = bp[q];
-          }
+          for (int q = 0; q < 4; ++q) b4[q] = reinterpret_cast<const float4*>(biasA + c0)[q];
 #pragma unroll
           for (int r = 0; r < R; ++r) acc_seed(acc[r], b4);
         }
@@ -842,8 +845,10 @@ __global__ __launch_bounds__(512, 1) void k_conv_pair32(ConvArgs a) {
     load_bias4(a.bias2, c0, b4);
     __syncthreads();  // the producers' first tile: its S1 ...
     __syncthreads();  // ... and S2
-    // (measured and NOT adopted, round 3: requesting a pass's residual rows one pass ahead instead of right before they seed the
-    // accumulators — 8.03 against 7.75 ms per step for the down-block pair: the consumers are not what the launch waits for)
+    // (measured and NOT adopted, twice: requesting a pass's residual rows one pass ahead, before the previous pass's MFMA loop.
+    // Round 3: 8.03 against 7.75 ms per step.  Again on top of the producers' LDS bias, with the request kept clear of compiler-made
+    // waits: 875 against 913 us per pooled launch with a residual tensor of its own, but 7.13 against 7.10 ms per step in the network,
+    // where the residual IS the block's input and the producers have just read those rows — profiles/pair_prefetch_timing.txt)
     for (int it = 0; it < my_tiles; ++it) {
       const int tile = walk.first + it * walk.step;
       const int tx = tile % a.tiles_x, tyn = tile / a.tiles_x;

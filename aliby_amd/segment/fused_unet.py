@@ -418,7 +418,11 @@ class FusedUNet:
         x1 = self._unit(c0s, u[1], shift=sh[0], bias=d["pb1"], res=p_low, res_up=up)
         # (round 2: with the head summed on the vector unit in its consumers' epilogue the pair measured 1139 us against 454 + 610 for
         # conv2 and the unit-with-head launch; round 3: the head is two MFMA k-steps (csrc/nn_conv.hip, head_apply), the pair with
-        # the head measures 944 us against 412 + 512: a tie, so the two launches stay the default — ALIBY_NET_PAIR_HEAD=1 for the pair)
+        # the head measures 944 us against 412 + 512: a tie, so the two launches stay the default — ALIBY_NET_PAIR_HEAD=1 for the pair.
+        # Again after the pair's producers took unit A's bias from LDS: launch by launch the pair with the head is 912-922 us against
+        # 875-884 for the two launches with a residual tensor of its own, 868-876 against 893-906 with the residual aliased to the
+        # input as here; but in the network the step does not move (unet 88.9-89.1 against 88.9-89.3 ms, the conv groups sum to
+        # 45.7 against 45.5 ms): the pair's range does not lie below the two launches', so still off — profiles/pair_prefetch_timing.txt)
         pair_shapes = tuple(u[2].w32.shape[:2]) == (32, 32) and tuple(u[3].w32.shape[:2]) == (32, 32)
         if self.fused_pair and pair_shapes and (head_out is None or self.pair_head):
             return self._pair(x1, u[2], u[3], sh[1], sh[2], u[2].bias, u[3].bias, x1, head_out=head_out)

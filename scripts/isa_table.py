@@ -5,7 +5,7 @@ import re, sys
 KEYS = ("vgpr_count", "sgpr_count", "private_segment_fixed_size", "vgpr_spill_count", "group_segment_fixed_size")
 OPS = ("v_mfma", "ds_read", "global_load", "global_store", "buffer_", "s_barrier", "")
 def kernels(text, out={}):
-    for name, body in re.findall(r"^(\w+):\s*; @\1\n(.*?)^\s*s_endpgm", text, re.M | re.S):
+    for name, body in re.findall(r"^(\w+):\s*; @\1\n(.*?)^\.Lfunc_end\d+:", text, re.M | re.S):  # (a kernel can hold several s_endpgm)
         ops = [l.split()[0] for l in body.splitlines() if l.startswith("\t") and l.lstrip()[0] not in ";."]
         m = [i for i, o in enumerate(ops) if o.startswith("v_mfma")] or [0]
         meta = re.search(r"^  - \.agpr_count((?!^  - ).)*?^    \.name: +%s\n.*?^    \.wavefront_size" % name, text, re.M | re.S).group(0)
