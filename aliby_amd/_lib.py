@@ -176,6 +176,7 @@ _SIGNATURES = {
     "aliby_texture3d_lds_voxels": (_i, []),
     "aliby_features_texture3d": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _i, _vp]),
     "aliby_features_neighbors3d": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _vp]),
+    "aliby_features_relate3d": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
     "aliby_granularity3d_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, C.c_double, C.c_double]),
     "aliby_features_granularity3d": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_double, C.c_double, _i, _i, _vp, _sz, _vp,
                                           _vp, _i, _i, _vp]),

@@ -19,7 +19,9 @@
 // The tertiary image T(outer, inner, shrink_inner): T[q] = outer[q] where inner[q] == 0, or where shrink_inner is set and q is an
 // outline pixel of its inner object; 0 elsewhere.  It keeps outer's labels, removes the interior of ANY inner object, and a label
 // that loses all its pixels is simply absent.
-// Not built: per-parent means of child measurements, volume (3-D) relation, a batched run_positions form.
+// Not built: per-parent means of child measurements, a batched run_positions form.  (Volume labels: feat_relate3d.hip, which shares
+// the counters, the absent row, the children atomic, the row write and the workspace layout with this file: relate_stats.h.  The run
+// folding and the argmax loop are written out in either overlap kernel: as shared functions they changed this kernel's code.)
 //
 // k_relate_overlap<GLOBAL>  one workgroup per object of one set ("self"), threads striding over its box (object_launch.h's two forms).
 //                      The working set is one int per label of the OTHER set's tile (sized from the largest tile's count: no cap on
@@ -39,8 +41,8 @@
 // k_tertiary_scalar    the same image one pixel per thread, for any width and alignment.
 // A row carries the same bits whatever the batch, the launch form, the workgroup size and the stream.
 #include "common.h"
-#include "neighbors_stats.h"
 #include "object_launch.h"
+#include "relate_stats.h"
 
 typedef unsigned short u16;
 
@@ -63,34 +65,6 @@ struct RelateArgs {
   unsigned char* gscratch;
 };
 
-extern __shared__ __align__(16) int relate_lds[];
-
-// the counters of this workgroup: named LDS in the LDS form (no flat pointer), a slab of the context's scratch in the global one
-template <bool GLOBAL>
-struct RelateCounts {
-  int* g;
-  __device__ __forceinline__ void zero(int k) const {
-    if constexpr (GLOBAL) g[k] = 0;
-    else relate_lds[k] = 0;
-  }
-  __device__ __forceinline__ void add(int k, int n) const {
-    if constexpr (GLOBAL) atomicAdd(&g[k], n);
-    else atomicAdd(&relate_lds[k], n);
-  }
-  // (global form: the adds were made in L2, so the read goes there too)
-  __device__ __forceinline__ int get(int k) const {
-    if constexpr (GLOBAL) return __hip_atomic_load(&g[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else return relate_lds[k];
-  }
-};
-
-// a row without pixels: the `neighbors` family's NaN centre (how k_relate_finish and the other direction know it), no parent
-__device__ __forceinline__ void relate_absent(const RelateArgs& a, int oi) {
-  neighbors_absent_centre<2>(a.centres + 2 * (size_t)oi);
-  a.parent[oi] = 0;
-  a.overlap[oi] = 0;
-}
-
 template <bool GLOBAL>
 __global__ __launch_bounds__(256) void k_relate_overlap(RelateArgs a) {
   __shared__ int red_i[8];
@@ -102,7 +76,7 @@ __global__ __launch_bounds__(256) void k_relate_overlap(RelateArgs a) {
     double* ctr = a.centres + 2 * (size_t)oi;
     const int y0 = max(o.y0, 0), y1 = min(o.y1, a.Y), x0 = max(o.x0, 0), x1 = min(o.x1, a.X);
     if (o.area <= 0 || o.tile < 0 || o.tile >= a.F || y0 >= y1 || x0 >= x1) {  // (block-uniform)
-      if (tid == 0) relate_absent(a, oi);
+      if (tid == 0) relate_absent<2>(a.centres, a.parent, a.overlap, oi);
       continue;
     }
     const int X = a.X, h = y1 - y0, w = x1 - x0, L = o.label;
@@ -146,14 +120,11 @@ __global__ __launch_bounds__(256) void k_relate_overlap(RelateArgs a) {
     sx = block_sum_i64(sx, red_l);
     if (tid == 0) {
       if (n == 0) {  // (a row whose area the labels do not bear out: absent)
-        relate_absent(a, oi);
+        relate_absent<2>(a.centres, a.parent, a.overlap, oi);
       } else {
         ctr[0] = neighbors_centre(sy, n);
         ctr[1] = neighbors_centre(sx, n);
-        const bool has = top > 0;
-        a.parent[oi] = has ? p : 0;
-        a.overlap[oi] = has ? top : 0;
-        if (has) atomicAdd(&a.children_other[row0 + p - 1], 1);  // (p <= nt <= row1 - row0: inside the other table)
+        relate_parent_write(a.parent, a.overlap, a.children_other, oi, row0, top, p);  // (p <= nt <= row1 - row0: inside the other table)
       }
     }
     __syncthreads();  // the counters are read before the next object clears them
@@ -203,30 +174,7 @@ __global__ __launch_bounds__(RELATE_FINISH_BLOCK) void k_relate_finish(RelateFin
       d_min = sqrt(best);
     }
   }
-  if (lane == 0) {
-    double* out = a.out + (size_t)row * a.ld + a.col0;
-    out[0] = (double)p;
-    out[1] = (double)a.overlap[row];
-    out[2] = (double)a.children[row];
-    out[3] = d_centre;
-    out[4] = d_min;
-  }
-}
-
-// the workspace of one side: centres [n, 2] float64, then parent, overlap and children [n] int32 each, rounded up to 8 bytes (the next
-// side starts with float64)
-struct RelateSide {
-  double* centres;
-  int *parent, *overlap, *children;
-};
-static inline size_t relate_side_bytes(int n) { return ((size_t)n * (2 * sizeof(double) + 3 * sizeof(int)) + 7) & ~(size_t)7; }
-static inline RelateSide relate_side(unsigned char* base, int n) {
-  RelateSide s;
-  s.centres = reinterpret_cast<double*>(base);
-  s.parent = reinterpret_cast<int*>(base + (size_t)n * 2 * sizeof(double));
-  s.overlap = s.parent + n;
-  s.children = s.overlap + n;
-  return s;
+  if (lane == 0) relate_row_write(a.out + (size_t)row * a.ld + a.col0, p, a.overlap[row], a.children[row], d_centre, d_min);
 }
 
 static int relate_overlap_launch(aliby_ctx* ctx, const u16* self, const u16* other, int F, int Y, int X, const aliby_object* tab, int n_obj,
@@ -237,7 +185,7 @@ static int relate_overlap_launch(aliby_ctx* ctx, const u16* self, const u16* oth
   a.self = self; a.other = other; a.F = F; a.Y = Y; a.X = X; a.tab = tab; a.n_obj = n_obj; a.off_other = off_other;
   a.n_other = n_other; a.max_count = max_count_other; a.centres = mine.centres; a.parent = mine.parent; a.overlap = mine.overlap;
   a.children_other = theirs.children;
-  a.need = (((size_t)max_count_other + 1) * sizeof(int) + 15) & ~(size_t)15;
+  a.need = relate_counter_bytes(max_count_other);
   return object_launch(ctx, k_relate_overlap<false>, k_relate_overlap<true>, a, n_obj, a.need, (size_t)RELATE_LDS_BUDGET,
                        (long long)max_h * max_w, s);
 }
@@ -256,7 +204,7 @@ static void relate_finish_launch(const u16* other, int F, int Y, int X, const al
 
 extern "C" size_t aliby_relate_workspace_bytes(int n_a, int n_b) {
   if (n_a < 0 || n_b < 0) return 0;
-  return relate_side_bytes(n_a) + relate_side_bytes(n_b);
+  return relate_side_bytes<2>(n_a) + relate_side_bytes<2>(n_b);
 }
 
 extern "C" int aliby_features_relate(aliby_ctx* ctx, const uint16_t* labels_a, const uint16_t* labels_b, int F, int Y, int X,
@@ -278,7 +226,7 @@ extern "C" int aliby_features_relate(aliby_ctx* ctx, const uint16_t* labels_a, c
   ARG_CHECK(((uintptr_t)work_dev & 7) == 0, "work_dev must be 8-byte aligned");
   hipStream_t s = as_stream(stream);
   unsigned char* base = static_cast<unsigned char*>(work_dev);
-  const RelateSide sa = relate_side(base, n_a), sb = relate_side(base + relate_side_bytes(n_a), n_b);
+  const RelateSide sa = relate_side<2>(base, n_a), sb = relate_side<2>(base + relate_side_bytes<2>(n_a), n_b);
   if (n_a) HIP_TRY(hipMemsetAsync(sa.children, 0, (size_t)n_a * sizeof(int), s));
   if (n_b) HIP_TRY(hipMemsetAsync(sb.children, 0, (size_t)n_b * sizeof(int), s));
   int rc = relate_overlap_launch(ctx, labels_a, labels_b, F, Y, X, table_a, n_a, max_h_a, max_w_a, offsets_b_dev, n_b, max_count_b, sa, sb, s);

@@ -1,5 +1,5 @@
 // volume_table.h — the front end of the per-object kernels on volume labels [F, Z, Y, X] (feat_coloc3d.hip, feat_texture3d.hip,
-// feat_intensity3d_detail.hip; feat_neighbors3d.hip takes the table and the plan):
+// feat_intensity3d_detail.hip; feat_neighbors3d.hip and feat_relate3d.hip take the table and the plan):
 // the object table (k_volume_table: voxel count and bounding box per (stack, label), one read of the labels), the host's plan
 // around it (volume_plan), the arguments and the prologue every such kernel opens with, and the launch of a <dtype, GLOBAL> kernel.
 // (The index decode of k_volume_table and the entries' shape check are volume_pass.h, shared with the whole-stack kernels.)
@@ -147,19 +147,27 @@ struct VolumePlan {
   std::unique_ptr<unsigned[]> host;  // the table as read back and the item list: lives as long as the plan, whatever the exit
 };
 
+// bytes of a plan's head in the context's scratch: the table, the offsets, the extra words and the item list, 256-byte aligned
+inline size_t volume_plan_head_bytes(int n, int F, size_t extra_words) {
+  return (((size_t)n * 7 + (size_t)(F + 1) + extra_words + (size_t)n) * 4 + 255) & ~(size_t)255;
+}
+
 // size_of_row(count, bmin[3], bmax[3]) = what a row is measured by against lds_limit; bytes_for(largest such measure above the
-// limit) = one workgroup's bytes in global scratch; per_block_mult = workgroups per grid column.  Scratch: [count n][bmin 3n]
-// [bmax 3n][offsets F+1][extra][items n], then (256-byte aligned) the global-scratch form's working sets.  Needs offsets_host[F] > 0.
+// limit) = one workgroup's bytes in global scratch; per_block_mult = workgroups per grid column.  Scratch, from byte `base` (a
+// multiple of 256) on: [count n][bmin 3n][bmax 3n][offsets F+1][extra][items n], then (256-byte aligned) the global-scratch form's
+// working sets.  Needs offsets_host[F] > 0.  base: a call that needs the tables of two label stacks (feat_relate3d.hip) places the
+// second plan behind the first one's volume_plan_head_bytes; it sizes the scratch for both BEFORE the first plan (a block that
+// grows moves, and only the plan that grows it puts its own table back) and asks for an lds_limit no row exceeds.
 template <class SizeOf, class BytesFor>
 int volume_plan(aliby_ctx* ctx, const uint16_t* labels, int F, int Z, int Y, int X, const int32_t* offsets_host, const int32_t* extra_host,
                 size_t extra_words, size_t lds_limit, SizeOf size_of_row, BytesFor bytes_for, size_t per_block_mult, hipStream_t s, VolumePlan* p,
-                const char* who) {
+                const char* who, size_t base = 0) {
   const int n = offsets_host[F];
   const size_t tab_words = (size_t)n * 7, off_bytes = sizeof(int) * (size_t)(F + 1);
-  const size_t head_bytes = ((tab_words + (size_t)(F + 1) + extra_words + (size_t)n) * 4 + 255) & ~(size_t)255;
-  int rc = aliby_ensure_scratch(ctx, head_bytes);
+  const size_t head_bytes = volume_plan_head_bytes(n, F, extra_words);
+  int rc = aliby_ensure_scratch(ctx, base + head_bytes);
   if (rc) return rc;
-  unsigned* table = (unsigned*)ctx->scratch;
+  unsigned* table = (unsigned*)((unsigned char*)ctx->scratch + base);
   HIP_TRY(hipMemcpyAsync(table + tab_words, offsets_host, off_bytes, hipMemcpyHostToDevice, s));
   rc = volume_table_launch(labels, F, Z, Y, X, (const int*)(table + tab_words), n, table, s);
   if (rc) return rc;
@@ -183,10 +191,10 @@ int volume_plan(aliby_ctx* ctx, const uint16_t* labels, int F, int Z, int Y, int
     const size_t fit = VOLUME_GLOBAL_BYTES / p->need / per_block_mult;
     p->grid_big = (int)std::min<size_t>({fit > 0 ? fit : 1, VOLUME_GLOBAL_BLOCKS, (size_t)p->n_big});
     void* before = ctx->scratch;
-    rc = aliby_ensure_scratch(ctx, head_bytes + p->need * (size_t)p->grid_big * per_block_mult);
+    rc = aliby_ensure_scratch(ctx, base + head_bytes + p->need * (size_t)p->grid_big * per_block_mult);
     if (rc) return rc;
     if (ctx->scratch != before) {  // the block moved: put the table and the offsets back
-      table = (unsigned*)ctx->scratch;
+      table = (unsigned*)((unsigned char*)ctx->scratch + base);
       e = hipMemcpyAsync(table, table_host, sizeof(unsigned) * tab_words, hipMemcpyHostToDevice, s);
       if (e == hipSuccess) e = hipMemcpyAsync(table + tab_words, offsets_host, off_bytes, hipMemcpyHostToDevice, s);
     }
@@ -198,7 +206,7 @@ int volume_plan(aliby_ctx* ctx, const uint16_t* labels, int F, int Z, int Y, int
   if (e == hipSuccess && p->n_big) e = hipMemcpyAsync(d_items, items_host, sizeof(int) * (size_t)p->n_big, hipMemcpyHostToDevice, s);
   if (e != hipSuccess) { aliby_set_error("%s: upload failed: %s", who, hipGetErrorString(e)); return ALIBY_ERR_HIP; }
   p->n = n;
-  p->gscratch = (unsigned char*)ctx->scratch + head_bytes;
+  p->gscratch = (unsigned char*)ctx->scratch + base + head_bytes;
   p->args = VolumeArgs{labels, F, Z, Y, X, d_off, table, table + n, table + (size_t)n * 4, d_items, n};
   return ALIBY_OK;
 }

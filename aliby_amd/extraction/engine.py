@@ -763,6 +763,65 @@ class FeatureEngine:
                                                           _ptr(out), _stream_ptr()))
         return out
 
+    def _relate3d_out(self, which: str, out, col0, rows: int):
+        """The output window of one side of `relate3d`: a new NaN matrix [rows, 5], or columns col0..col0+4 of `out`."""
+        if out is None:
+            return self.new_output(rows, 5), 0
+        col0 = self._integer(f"col0_{which}", col0)
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or not out.is_cuda or out.dim() != 2:
+            raise TypeError(f"relate3d: out_{which} must be a float64 [rows, columns] tensor on the device")
+        if out.shape[0] != rows or col0 < 0 or col0 + 5 > out.shape[1] or (rows and out.stride(1) != 1):
+            raise ValueError(f"relate3d: out_{which} must hold {rows} rows and columns {col0}..{col0 + 4} with unit column stride, got "
+                             f"{tuple(out.shape)} with strides {tuple(out.stride())}")
+        return out, col0
+
+    def relate3d(self, volume_a, counts_a, volume_b, counts_b, spacing=(1.0, 1.0, 1.0), out_a=None, col0_a=0, out_b=None, col0_b=0):
+        """Two sets of volume labels uint16 [F,Z,Y,X] of one shape (1..counts_*[f] per stack) -> (matrix_a, matrix_b), float64
+        [sum counts, 5] each, rows in (stack, label) order: the rows of A relative to B and of B relative to A
+        (features.relate3d_names(other); aliby_features_relate3d) — the `relate` family on volumes: the parent (most shared voxels, ties
+        to the smaller label, 0 = none), that overlap, the number of children, the distance between the centres and from the centre to
+        the parent's plane-by-plane outline (NaN without a parent), in the units of `spacing` = (dz, dy, dx), positive and finite.  On
+        a stack of one plane with unit spacing every column carries the bits of `relate`.  out_a / out_b: matrices [rows, .] to write
+        columns col0..col0+4 of instead of new ones (the returned matrix is then that window).  An empty set gives a [0, 5] matrix, and
+        the other side's rows then have no parent and no children.  Volumes that are not uint16 [F,Z,Y,X] of one shape, counts of
+        the wrong length and a bad spacing are ValueErrors.  PARITY UNPINNED; the definition is in include/aliby_hip.h.  The object
+        tables and the counters live in the context's scratch: a main-stream call.  Bitwise independent of run, batch and launch form."""
+        for name, v in (("volume_a", volume_a), ("volume_b", volume_b)):
+            if not isinstance(v, torch.Tensor) or v.dtype != torch.uint16 or v.dim() != 4 or not v.is_cuda:
+                raise ValueError(f"relate3d: {name} must be a uint16 [F,Z,Y,X] tensor on the device, got "
+                                 f"{(v.dtype, tuple(v.shape)) if isinstance(v, torch.Tensor) else type(v).__name__}")
+        if tuple(volume_a.shape) != tuple(volume_b.shape):
+            raise ValueError(f"relate3d: the two volumes must share one shape [F,Z,Y,X], got {tuple(volume_a.shape)} and {tuple(volume_b.shape)}")
+        F, Z, Y, X = (int(v) for v in volume_a.shape)
+        sp = self._spacing3d(spacing)
+        off_a, off_b = self._volume_offsets("relate3d (counts_a)", F, counts_a), self._volume_offsets("relate3d (counts_b)", F, counts_b)
+        n_a, n_b = int(off_a[-1]), int(off_b[-1])
+        out_a, col0_a = self._relate3d_out("a", out_a, col0_a, n_a)
+        out_b, col0_b = self._relate3d_out("b", out_b, col0_b, n_b)
+        if (n_a or n_b) and volume_a.numel():
+            va, vb = volume_a.contiguous(), volume_b.contiguous()
+            with self.timed("relate3d"):
+                _lib.check(self.lib.aliby_features_relate3d(
+                    self.ctx.handle, _ptr(va), _ptr(vb), F, Z, Y, X, _ptr(off_a), _ptr(off_b), _ptr(sp),
+                    _ptr(out_a) if n_a else 0, out_a.stride(0) if n_a else 5, col0_a,
+                    _ptr(out_b) if n_b else 0, out_b.stride(0) if n_b else 5, col0_b, _stream_ptr()))
+        return out_a[:, col0_a:col0_a + 5], out_b[:, col0_b:col0_b + 5]
+
+    def tertiary_volume(self, outer, inner, shrink_inner: bool = True) -> torch.Tensor:
+        """outer, inner uint16 [F,Z,Y,X] of one shape -> device uint16 [F,Z,Y,X]: outer's labels where inner is 0 or, with
+        shrink_inner, on the plane-by-plane outline of an inner object; 0 elsewhere — the tertiary image of every plane
+        (aliby_tertiary_labels on the [F Z, Y, X] view: the outline of a volume is taken plane by plane, so no other kernel is
+        needed).  It keeps outer's labels and counts; a label that loses every voxel is absent.  At a nucleus's top and bottom caps
+        only the cap's in-plane rim is kept.  PARITY UNPINNED (include/aliby_hip.h)."""
+        for name, v in (("outer", outer), ("inner", inner)):
+            if not isinstance(v, torch.Tensor) or v.dtype != torch.uint16 or v.dim() != 4 or not v.is_cuda:
+                raise ValueError(f"tertiary_volume: {name} must be a uint16 [F,Z,Y,X] tensor on the device")
+        if tuple(outer.shape) != tuple(inner.shape):
+            raise ValueError(f"tertiary_volume: outer and inner must share one shape [F,Z,Y,X], got {tuple(outer.shape)} and {tuple(inner.shape)}")
+        F, Z, Y, X = (int(v) for v in outer.shape)
+        planes = self.tertiary_labels(outer.contiguous().view(F * Z, Y, X), inner.contiguous().view(F * Z, Y, X), shrink_inner=shrink_inner)
+        return planes.view(F, Z, Y, X)
+
     def zernike(self, labels, planes, dtype, channel, table: ObjectTable, out, col0, weighted: bool):
         F, Y, X = labels.shape
         Cn = planes.shape[1] if planes is not None else 0

@@ -428,6 +428,33 @@ def process_tree_volumes(tree, volumes, pixels, counts=None, cp_measure_kwargs=N
     return LazyProduct(objects, instructions), DeviceResults(eng.to_host(matrix_dev), objects, instructions, blocks)
 
 
+RELATE3D_INSTRUCTION = ("None", "None", "relate3d")  # the one instruction of a `volumerelate_<obj>` step: None/None/relate3d/<name>
+
+
+def relate_volumes(volume, counts, others: dict, spacing=(1.0, 1.0, 1.0)):
+    """The rows of the objects of volume labels (device uint16 [F,Z,Y,X] with counts [F]: a segment step's `last_volume`) relative to
+    every object set of `others` {name: (volume, counts)} of the same shape (FeatureEngine.relate3d): returns (tileid_instructions,
+    results) like process_tree_volumes, with the single instruction RELATE3D_INSTRUCTION and the columns
+    features.relate3d_names(name) of all names side by side; objects are every (stack, label) of `volume`, in that order."""
+    from aliby_amd.extraction.engine import FeatureEngine
+
+    eng = FeatureEngine()
+    counts = np.asarray(counts, np.int64).reshape(-1)
+    names, matrices = [], []
+    for other, (other_volume, other_counts) in others.items():
+        rows, _ = eng.relate3d(volume, counts, other_volume, np.asarray(other_counts, np.int64).reshape(-1), spacing=spacing)
+        names.extend(feat.relate3d_names(other))
+        matrices.append(rows)
+    objects = [(f, lab) for f in range(len(counts)) for lab in range(1, int(counts[f]) + 1)]
+    if not matrices or not objects:
+        return (), []
+    import torch
+
+    matrix = eng.to_host(matrices[0] if len(matrices) == 1 else torch.cat(matrices, 1))
+    lazy = LazyProduct(objects, [RELATE3D_INSTRUCTION])
+    return tuple(lazy), DeviceResults(matrix, objects, [RELATE3D_INSTRUCTION], [(0, names)])
+
+
 def process_tree_masks_overlap(tree, masks, pixels, measure_fn, ncores=None, progress_bar=False, overlap=True,
                                cp_measure_kwargs=None):
     """Overlapping masks (BABY's layered output): `masks[tile]` is a [stack, Y, X] integer array whose planes hold objects

@@ -183,12 +183,19 @@ def relate_names(other: str) -> list[str]:
     tests/relate_ref.py) is recalled from CellProfiler 4 and centrosome, neither of which can be run beside this package.
     ParentOverlap is an extension.  `other` is a non-empty string without "_" (a step's object name is what follows the last "_"
     of its name) and without "/" (the column separator): anything else is a ValueError.  Needs no device.
-    Not built: per-parent means of child measurements, "Expand until adjacent" and `neighbors` against a second object set, volume
-    (3-D) relation, the batched run_positions form."""
+    Not built: per-parent means of child measurements, "Expand until adjacent" and `neighbors` against a second object set, the
+    batched run_positions form.  (Volume labels: `relate3d_names`.)"""
     if not isinstance(other, str) or not other or "_" in other or "/" in other:
         raise ValueError(f"relate: the other object set's name must be a non-empty string without '_' or '/', got {other!r}")
     return [f"Parent_{other}", f"ParentOverlap_{other}", f"Children_{other}_Count", f"Distance_Centroid_{other}",
             f"Distance_Minimum_{other}"]
+
+
+def relate3d_names(other: str) -> list[str]:
+    """Columns of `FeatureEngine.relate3d` for rows related to the object set `other` (csrc/feat_relate3d.hip): the five of
+    `relate_names`, on volume labels — overlaps in voxels, distances in the units of the call's `spacing`, the parent's outline taken
+    plane by plane.  PARITY UNPINNED like the 2-D family (include/aliby_hip.h, tests/relate3d_ref.py).  Needs no device."""
+    return relate_names(other)
 
 
 COLOC = {

@@ -116,6 +116,35 @@ def tertiary_objects(outer, inner, shrink_inner=True) -> np.ndarray:
     return eng.tertiary_labels(a, b, shrink_inner=shrink_inner)[0].cpu().numpy()
 
 
+def _label_stack(name: str, labels):
+    labels = np.asarray(labels)
+    if labels.ndim != 3:
+        raise ValueError(f"{name} must be one [Z, Y, X] label stack, got shape {labels.shape}")
+    return to_device_u16(labels[None]), int(labels.max()) if labels.size else 0
+
+
+def relate_objects_3d(child_labels, parent_labels, spacing=(1.0, 1.0, 1.0)):
+    """Two label stacks [Z, Y, X] of one shape (0 = background, labels 1..n) -> (children, parents), float64 [n, 5] each on the host:
+    the volume form of `relate_objects` (FeatureEngine.relate3d, csrc/feat_relate3d.hip), overlaps in voxels and distances in the units
+    of `spacing` = (dz, dy, dx).  Not in the reference: CellProfiler's RelateObjects, PARITY UNPINNED (include/aliby_hip.h)."""
+    (a, na), (b, nb) = _label_stack("child_labels", child_labels), _label_stack("parent_labels", parent_labels)
+    if a.shape != b.shape:
+        raise ValueError(f"child_labels {tuple(a.shape[1:])} and parent_labels {tuple(b.shape[1:])} differ in shape")
+    eng = FeatureEngine()
+    rows_a, rows_b = eng.relate3d(a, [na], b, [nb], spacing=spacing)
+    return eng.to_host(rows_a), eng.to_host(rows_b)
+
+
+def tertiary_objects_3d(outer, inner, shrink_inner=True) -> np.ndarray:
+    """Two label stacks [Z, Y, X] of one shape -> uint16 [Z, Y, X]: `outer`'s labels where `inner` is 0 or, with shrink_inner, on the
+    plane-by-plane outline of an inner object; 0 elsewhere (FeatureEngine.tertiary_volume).  The cytoplasm of a stack is
+    tertiary_objects_3d(cells, nuclei).  Not in the reference: CellProfiler's IdentifyTertiaryObjects, PARITY UNPINNED."""
+    (a, _), (b, _) = _label_stack("outer", outer), _label_stack("inner", inner)
+    if a.shape != b.shape:
+        raise ValueError(f"outer {tuple(a.shape[1:])} and inner {tuple(b.shape[1:])} differ in shape")
+    return FeatureEngine().tertiary_volume(a, b, shrink_inner=shrink_inner)[0].cpu().numpy()
+
+
 def _background(cell_masks, trap_image):
     trap_image = _as_pixels(trap_image)
     if not len(cell_masks):

@@ -44,6 +44,11 @@ _PREFIXES = (
     # (not an "extract" prefix: every step that starts with "extract" is joined to the 2-D rows on metadata_label, which would pair
     # volume label k with 2-D label k; the volume rows get their own table, profiles3d/)
     ("volume_", lambda name, params, done: core._init_volume(name, params, done)),
+    # two object sets of one stack read together (csrc/feat_relate3d.hip), from the volume labels the steps they name kept: the
+    # tertiary volume, which a volume_ step measures, and the relate3d rows, joined onto the volume_ rows in profiles3d/.  (Neither
+    # starts with "extract" or "volume_": the table code tells the steps apart by those.)
+    ("volumetertiary_", lambda name, params, done: core._VolumeTertiary(name, params, done)),
+    ("volumerelate_", lambda name, params, done: core._init_volume_relate(name, params, done)),
     ("nahual_embed", lambda name, params, done: core._init_nahual(name, params)),
     ("nahual_track", lambda name, params, done: core._init_nahual(name, params)),
 )

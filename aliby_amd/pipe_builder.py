@@ -69,6 +69,7 @@ def build_pipeline_steps(
     volume_coloc: bool = False,
     relate: Sequence[tuple[str, str]] | None = None,
     tertiary: dict[str, tuple[str, str]] | None = None,
+    volume_relate: bool = False,
 ) -> dict:
     """Extension (not in the reference): `volume_features`, a sequence of per-channel volume family names
     (extraction.families.VOLUME: "intensity3d", "intensity3d_detail", "texture3d", "granularity3d"), makes every segment step
@@ -84,7 +85,14 @@ def build_pipeline_steps(
     `tertiary_<name>` step right after the segment steps (outer's labels minus inner's objects: {"cytoplasm": ("cell", "nuclei")}),
     saved like them, and `extract_<name>` / `extractmulti_<name>` steps with the shared specs: rows with metadata_object = <name>
     whose metadata_label is the outer object's.  A name that is not an object set is a ValueError.  With both None the dict is the
-    reference's."""
+    reference's.
+
+    `volume_relate=True` (with `volume_features` and at least one of `relate` / `tertiary`, else a ValueError) takes both to the volume
+    labels (csrc/feat_relate3d.hip): a `volumetertiary_<name>` step per tertiary entry right after the segment and tertiary steps
+    (the tertiary volume of the two segment steps' kept volumes), a `volume_<name>` step that measures it with the shared volume tree,
+    and a `volumerelate_<obj>` step per related object set (columns None/None/relate3d/Parent_<other>, ...).  Their rows go to
+    profiles3d/: nuclei, cell and cytoplasm rows keyed by volume label, the relate3d columns joined onto the rows of their object set.
+    With the default False the dict is what it is without the keyword."""
     if channels_to_segment is None:
         channels_to_segment = {"nuclei": 1, "cell": 0}
     kind = "cellpose" if nahual_addresses is None else "nahual_cellpose"
@@ -92,6 +100,11 @@ def build_pipeline_steps(
         channels_to_extract = list(channels_to_segment.values())
     objects = list(channels_to_segment)
     related, tertiary = _object_links(objects, relate, tertiary)
+    if not isinstance(volume_relate, bool):
+        raise ValueError(f"volume_relate must be a bool, got {volume_relate!r}")
+    if volume_relate and (volume_features is None or not (related or tertiary)):
+        raise ValueError("volume_relate=True needs volume_features (the volume labels come from 3-D segment steps) and at least one "
+                         "of relate / tertiary")
     producer = {obj: f"segment_{obj}" for obj in objects} | {name: f"tertiary_{name}" for name in tertiary}
 
     steps = {"tile": {"tile_size": None}}
@@ -99,6 +112,9 @@ def build_pipeline_steps(
         steps[f"segment_{obj}"] = {"segmenter_kwargs": {"kind": kind}, "channel_to_segment": ch}
     for name in tertiary:
         steps[f"tertiary_{name}"] = {"shrink_inner": True}
+    if volume_relate:
+        for name, (outer, inner) in tertiary.items():
+            steps[f"volumetertiary_{name}"] = {"outer": f"segment_{outer}", "inner": f"segment_{inner}", "shrink_inner": True}
 
     # the single-channel spec is shared by every object set (as in the reference, where both
     # extract_<obj> entries point at the same dict)
@@ -141,6 +157,17 @@ def build_pipeline_steps(
             steps[f"volume_{obj}"] = {"tree": tree, "volume_from": f"segment_{obj}",
                                       "kwargs": _step_kwargs(extract_ncores, cp_measure_feature_kwargs)}
             pipeline["passed_data"][f"volume_{obj}"] = [("pixels", "tile")]
+        if volume_relate:
+            # (the volumetertiary and volumerelate steps read the kept volumes through the initialised steps, as a volume step
+            # does: they have no passed_data entry)
+            volume_producer = {obj: f"segment_{obj}" for obj in objects} | {name: f"volumetertiary_{name}" for name in tertiary}
+            for name in tertiary:
+                steps[f"volume_{name}"] = {"tree": tree, "volume_from": f"volumetertiary_{name}",
+                                           "kwargs": _step_kwargs(extract_ncores, cp_measure_feature_kwargs)}
+                pipeline["passed_data"][f"volume_{name}"] = [("pixels", "tile")]
+            for obj, others in related.items():
+                steps[f"volumerelate_{obj}"] = {"volume_from": volume_producer[obj], "others": {o: volume_producer[o] for o in others},
+                                                "spacing": (1.0, 1.0, 1.0)}
     if steps_to_write is not None:
         pipeline["save"] = list(steps_to_write)
     if trackastra_address is not None:

@@ -84,29 +84,44 @@ def _init_extract_multi(step_name: str, parameters: dict) -> Callable:
     return partial(process_tree_masks, measure_fn=extract_tree_multi, tree=tree, **parameters.get("kwargs", {}))
 
 
+_VOLUME_SOURCES = ("segment", "volumetertiary_")  # the steps that keep volume labels in `last_volume`
+
+
+def _kept_volume(step_name: str, key: str, source: str, other_steps: dict):
+    """(volume uint16 [F,Z,Y,X] on the device, counts [F]) that the step `source` kept at this timepoint, or a ValueError that names
+    the step `step_name`, its parameter `key` and the cause."""
+    producer = other_steps.get(source)
+    if producer is None or not hasattr(producer, "last_volume"):
+        raise ValueError(f"Step '{step_name}': '{key}' = '{source}' is not a segment step or a volumetertiary step that ran before this one.")
+    if producer.last_volume is None:
+        raise ValueError(f"Step '{step_name}': '{source}' kept no volume labels: it ran without do_3D (set 'do_3D': True in its "
+                         "segmenter_kwargs), or the stack has a single plane.")
+    return producer.last_volume
+
+
+def _volume_source(step_name: str, parameters: dict, key: str) -> str:
+    source = _need(parameters, key, step_name)
+    if not isinstance(source, str) or not source.startswith(_VOLUME_SOURCES):
+        raise ValueError(f"Step '{step_name}': '{key}' must name a segment step (or a volumetertiary step), got {source!r}.")
+    return source
+
+
 def _init_volume(step_name: str, parameters: dict, other_steps: dict) -> Callable:
     """A `volume_<obj>` step: the volume families of `tree` (extraction.families.VOLUME / VOLUME_PAIRS) over the volume labels the
     segment step named by `volume_from` kept on the device (`segment.last_volume`, a 3-D segmentation: `do_3D` in its
-    segmenter_kwargs), with the tile's pixels.  `kwargs`: cp_measure_kwargs, ncores.  Its rows are keyed by the VOLUME label and go
-    to their own table (get_volume_profiles_from_state), never into the join of the extract steps."""
+    segmenter_kwargs) — or a `volumetertiary_` step (its tertiary volume) — with the tile's pixels.  `kwargs`: cp_measure_kwargs,
+    ncores.  Its rows are keyed by the VOLUME label and go to their own table (get_volume_profiles_from_state), never into the join
+    of the extract steps."""
     from aliby_amd.extraction import families
     from aliby_amd.extraction.extract import flatten, kv
 
     tree = _need(parameters, "tree", step_name)
-    source = _need(parameters, "volume_from", step_name)
-    if not isinstance(source, str) or not source.startswith("segment"):
-        raise ValueError(f"Step '{step_name}': 'volume_from' must name a segment step, got {source!r}.")
+    source = _volume_source(step_name, parameters, "volume_from")
     extra = dict(parameters.get("kwargs", {}))
     families.plan_volume(kv(flatten(tree)), extra.get("cp_measure_kwargs"))  # a tree or keyword that is refused fails here, not at tp 0
 
     def volume_step(pixels):
-        segment = other_steps.get(source)
-        if segment is None or not hasattr(segment, "last_volume"):
-            raise ValueError(f"Step '{step_name}': 'volume_from' = '{source}' is not a segment step that ran before this one.")
-        if segment.last_volume is None:
-            raise ValueError(f"Step '{step_name}': '{source}' kept no volume labels: it ran without do_3D (set 'do_3D': True in its "
-                             "segmenter_kwargs), or the stack has a single plane.")
-        volume, counts = segment.last_volume
+        volume, counts = _kept_volume(step_name, "volume_from", source, other_steps)
         shape = tuple(pixels.shape)
         if len(shape) != 5 or tuple(volume.shape) != (shape[0], *shape[2:]):
             raise ValueError(f"Step '{step_name}': the volume labels of '{source}' are {tuple(volume.shape)} [F,Z,Y,X], the pixels "
@@ -114,6 +129,86 @@ def _init_volume(step_name: str, parameters: dict, other_steps: dict) -> Callabl
         return process_tree_volumes(tree, volume, pixels, counts=counts, **extra)
 
     return volume_step
+
+
+class _VolumeTertiary:
+    """A `volumetertiary_<name>` step: the tertiary volume (FeatureEngine.tertiary_volume: the `outer` step's kept volume labels minus
+    the objects of the `inner` step's, plane by plane; the cytoplasm of a stack) of two segment steps named in its parameters.  It
+    keeps `last_volume` = (the tertiary volume on the device, outer's counts) for the `volume_<name>` and `volumerelate_` steps after
+    it, and returns the labels on the host, one [Z,Y,X] uint16 array or a list of them for several tiles: listed under `save` they
+    are written like a segment step's masks."""
+
+    def __init__(self, step_name: str, parameters: dict, other_steps: dict):
+        unknown = set(parameters) - {"outer", "inner", "shrink_inner"}
+        if unknown:
+            raise ValueError(f"Step '{step_name}': unknown parameters {sorted(unknown)}.")
+        self.step_name, self.other_steps = step_name, other_steps
+        self.outer, self.inner = _volume_source(step_name, parameters, "outer"), _volume_source(step_name, parameters, "inner")
+        if self.outer == self.inner:
+            raise ValueError(f"Step '{step_name}': 'outer' and 'inner' must name two different steps, got {self.outer!r} twice.")
+        self.shrink = parameters.get("shrink_inner", True)
+        if not isinstance(self.shrink, bool):
+            raise ValueError(f"Step '{step_name}': 'shrink_inner' must be a bool, got {self.shrink!r}.")
+        self.last_volume = None
+
+    def __call__(self):
+        from aliby_amd.extraction.engine import FeatureEngine
+
+        self.last_volume = None
+        outer, counts = _kept_volume(self.step_name, "outer", self.outer, self.other_steps)
+        inner, _ = _kept_volume(self.step_name, "inner", self.inner, self.other_steps)
+        if tuple(outer.shape) != tuple(inner.shape):
+            raise ValueError(f"Step '{self.step_name}': the volume labels of '{self.outer}' are {tuple(outer.shape)} [F,Z,Y,X], those of "
+                             f"'{self.inner}' {tuple(inner.shape)}: they do not match.")
+        volume = FeatureEngine().tertiary_volume(outer, inner, shrink_inner=self.shrink)
+        self.last_volume = (volume, counts)
+        host = volume.cpu().numpy()
+        return host[0] if host.shape[0] == 1 else [host[f] for f in range(host.shape[0])]
+
+
+def _volume_relate_others(step_name: str, parameters: dict) -> dict:
+    """The `others` of a `volumerelate_<obj>` step: a non-empty {object-set name: the step that keeps its volume labels}."""
+    from aliby_amd.extraction import features
+
+    others = _need(parameters, "others", step_name)
+    if not isinstance(others, dict) or not others:
+        raise ValueError(f"Step '{step_name}': 'others' must be a non-empty dict {{object set: its segment or volumetertiary step}}, "
+                         f"got {others!r}.")
+    for other, source in others.items():
+        features.relate3d_names(other)  # (refuses what cannot be told apart in a column or step name)
+        _volume_source(step_name, {"others": source}, "others")
+    return dict(others)
+
+
+def _init_volume_relate(step_name: str, parameters: dict, other_steps: dict) -> Callable:
+    """A `volumerelate_<obj>` step: the rows of <obj>'s volume objects relative to every object set of `others` (the `relate` family
+    on volume labels; extraction.extract.relate_volumes), from the volumes the named steps kept.  `spacing` = (dz, dy, dx), default
+    (1, 1, 1).  It returns (tileid_instructions, results) with the one instruction None/None/relate3d; the volume profile table joins
+    the rows onto <obj>'s `volume_` rows."""
+    from aliby_amd.extraction.engine import FeatureEngine
+    from aliby_amd.extraction.extract import relate_volumes
+
+    unknown = set(parameters) - {"volume_from", "others", "spacing"}
+    if unknown:
+        raise ValueError(f"Step '{step_name}': unknown parameters {sorted(unknown)}.")
+    source = _volume_source(step_name, parameters, "volume_from")
+    others = _volume_relate_others(step_name, parameters)
+    try:
+        spacing = tuple(float(v) for v in FeatureEngine._spacing3d(parameters.get("spacing", (1.0, 1.0, 1.0))))
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"Step '{step_name}': {e}") from None
+
+    def volume_relate_step():
+        volume, counts = _kept_volume(step_name, "volume_from", source, other_steps)
+        kept = {}
+        for other, other_source in others.items():
+            kept[other] = _kept_volume(step_name, "others", other_source, other_steps)
+            if tuple(kept[other][0].shape) != tuple(volume.shape):
+                raise ValueError(f"Step '{step_name}': the volume labels of '{source}' are {tuple(volume.shape)} [F,Z,Y,X], those of "
+                                 f"'{other_source}' {tuple(kept[other][0].shape)}: they do not match.")
+        return relate_volumes(volume, counts, kept, spacing=spacing)
+
+    return volume_relate_step
 
 
 def _relate_others(step_name: str, parameters: dict) -> list:
@@ -170,8 +265,35 @@ def _init_tertiary(step_name: str, parameters: dict) -> Callable:
     return tertiary_step
 
 
+def _check_volume_links(steps: dict) -> None:
+    """The wiring of the volume steps of two object sets, before any timepoint: a `volumetertiary_` or `volumerelate_` step, and a
+    `volume_` step fed by a `volumetertiary_` one, names steps of the pipeline that run before it and keep volume labels."""
+    order = {name: k for k, name in enumerate(steps)}
+    for name, params in steps.items():
+        if not isinstance(params, dict):
+            continue
+        if name.startswith("volumetertiary_"):
+            wanted = {"outer": params.get("outer"), "inner": params.get("inner")}
+        elif name.startswith("volumerelate_"):
+            wanted = {"volume_from": params.get("volume_from")}
+            wanted.update({f"others[{o!r}]": src for o, src in _volume_relate_others(name, params).items()})
+        elif name.startswith("volume_") and isinstance(params.get("volume_from"), str) and params["volume_from"].startswith("volumetertiary_"):
+            wanted = {"volume_from": params["volume_from"]}
+        else:
+            continue
+        for key, source in wanted.items():
+            if not isinstance(source, str) or not source.startswith(_VOLUME_SOURCES):
+                raise ValueError(f"Step '{name}': '{key}' must name a segment step (or a volumetertiary step), got {source!r}.")
+            if source not in steps or order[source] >= order[name]:
+                raise ValueError(f"Step '{name}': '{key}' = '{source}' is not a step of the pipeline that runs before it.")
+            kwargs = steps[source].get("segmenter_kwargs", {}) if isinstance(steps[source], dict) else {}
+            if source.startswith("segment") and not (isinstance(kwargs, dict) and kwargs.get("do_3D")):
+                raise ValueError(f"Step '{name}': '{key}' = '{source}' keeps no volume labels: set 'do_3D': True in its segmenter_kwargs.")
+
+
 def _check_object_links(steps: dict, passed_data: dict) -> None:
     """The wiring of the two-object-set steps, before any timepoint: every input they need is an aliased `passed_data` entry."""
+    _check_volume_links(steps)
     for name, params in steps.items():
         if name.startswith("extractrelate_") and isinstance(params, dict):
             wanted = ["masks"] + [f"masks_{o}" for o in _relate_others(name, params)]
@@ -474,16 +596,28 @@ def _join_related(left: pa.Table, right: pa.Table) -> pa.Table:
 def get_volume_profiles_from_state(state: dict, pipeline: dict) -> pa.Table:
     """One wide table per (`volume_` step, tp), concatenated: the metadata columns of `get_profiles_from_state`, with
     `metadata_label` the VOLUME label.  Kept apart from the extract steps' table, whose labels are those of the collapsed image;
-    `<key>/None/projection3d/Projection_Label` is the row's label there (0: hidden in the collapse)."""
-    tables = []
+    `<key>/None/projection3d/Projection_Label` is the row's label there (0: hidden in the collapse).  The rows of `volumerelate_`
+    steps carry different columns per object set (Parent_cell on nuclei rows, Parent_nuclei on cell rows): they are concatenated with
+    their schemas unified, null-filled, and left-joined onto the `volume_` rows on the metadata columns, keeping the row order (the
+    arrangement of `_join_related`).  A tertiary compartment's rows carry its own name as metadata_object and the outer object's
+    volume label: cytoplasm rows join their cell on (metadata_tp, metadata_tile, metadata_label).  Without such steps the table is
+    the `volume_` rows alone."""
+    tables, related = [], []
     for name in pipeline["steps"]:
-        if not name.startswith("volume_"):
+        bucket = tables if name.startswith("volume_") else related if name.startswith(_VOLUME_RELATE_PREFIX) else None
+        if bucket is None:
             continue
         for tp, output in enumerate(state["data"][name]):
             table = _wide_table(name, tp, output)
             if table is not None:
-                tables.append(table)
-    return pa.concat_tables(tables) if tables else _empty_profiles()
+                bucket.append(table)
+    if not tables:
+        return _empty_profiles()
+    profiles = pa.concat_tables(tables)
+    return _join_related(profiles, pa.concat_tables(related, promote_options="default")) if related else profiles
+
+
+_VOLUME_RELATE_PREFIX = "volumerelate_"
 
 
 def _join_on_metadata(left: pa.Table, right: pa.Table, strict: bool = False) -> pa.Table:

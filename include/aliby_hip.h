@@ -550,8 +550,8 @@ int aliby_features_neighbors(aliby_ctx* ctx, const uint16_t* labels, int F, int 
  *   2        2       2              1                                          (nuclei 2 and 3 tie at 2 pixels)
  * Tertiary areas of cells 1 and 2: 18 and 20 with shrink_inner = 0; 24 and 24 with shrink_inner = 1 (every pixel of these small
  * nuclei is an outline pixel).  A 3 x 3 nucleus loses exactly its one interior pixel.
- * Not built: per-parent means of child measurements, "Expand until adjacent" and `neighbors` against a second object set, volume
- * (3-D) relation.
+ * Not built: per-parent means of child measurements, "Expand until adjacent" and `neighbors` against a second object set.  (Volume
+ * labels: aliby_features_relate3d below.)
  *
  * The relate entry fills both directions in one call: rows of A relative to B into out_a, rows of B relative to A into out_b; either
  * may be NULL (both directions are still computed: column 2 of one needs the parents of the other).  table_*: device tables of the
@@ -793,6 +793,56 @@ int aliby_features_texture3d(aliby_ctx* ctx, const uint16_t* labels, const void*
  * independent of the run, of the other stacks of the call and of the batch.  Kernels: csrc/feat_neighbors3d.hip. */
 int aliby_features_neighbors3d(aliby_ctx* ctx, const uint16_t* labels, int F, int Z, int Y, int X, const int32_t* offsets_host,
                                int distance, double* centres_dev, double* out, int ld, int col0, void* stream);
+/* "relate3d": the `relate` family (aliby_features_relate: CellProfiler's RelateObjects) on two sets of labelled stacks, and the
+ * tertiary volume.  PARITY UNPINNED: recalled from CellProfiler 4's relateobjects.py and identifytertiaryobjects.py and centrosome's
+ * outline, none of which can be run beside this library (tests/relate3d_ref.py restates it).
+ * Per stack, A and B are two label volumes of one shape [Z,Y,X]: uint16, 0 = background, labels 1..n_A and 1..n_B from the offsets;
+ * a label may be absent; values above the count are not measured and have no counter.  Row L of A relative to B,
+ * out[row * ld + col0 + k], k = 0..4, row = offsets[f] + L - 1 — the 2-D family's five columns:
+ *   0 Parent: the label p >= 1 of B under the most voxels of L, ties to the smallest p; 0 when no voxel of L lies under a B label in
+ *     1..n_B, or when L is absent
+ *   1 ParentOverlap: that voxel count, exact; 0 without a parent
+ *   2 Children count: the B objects whose Parent in A, by the same rule with the roles swapped, is L
+ *   3 Distance_Centroid: centres (sum z, sum y, sum x) / count from exact 64-bit sums and one float64 division each.  With
+ *     spacing = (sz, sy, sx): ez = (pz - cz) sz, ey = (py - cy) sy, ex = (px - cx) sx (parent minus L), sqrt((ez ez + ey ey) + ex ex),
+ *     every operation rounded on its own (-ffp-contract=off); NaN without a parent
+ *   4 Distance_Minimum: the same expression with a voxel (z, y, x) in place of the parent's centre, over the outline voxels of the
+ *     parent, reduced with fmin (order-free, exact), then one sqrt; NaN without a parent.  The outline is taken plane by plane, exactly
+ *     as neighbors3d defines it: a voxel of p on the first or last row or column of its plane, or with one of its 8 in-plane
+ *     neighbours of another value; the first and last planes are no borders, and the voxels above and below do not make an outline
+ *     voxel.
+ * Consequences.  With Z = 1 and spacing (1, 1, 1), cz = pz = 0.0, so ez = 0, 0 + ey ey is exact and a product with 1.0 is exact:
+ * every column carries the bits of aliby_features_relate.  Distances are in the units of `spacing` (positive and finite; anisotropic
+ * Z is the normal case for stacks).
+ * The tertiary volume T(outer, inner, shrink_inner): T[q] = outer[q] where inner[q] == 0, or where shrink_inner is set and q is a
+ * plane-by-plane outline voxel of its inner object; 0 elsewhere.  It keeps outer's labels and counts; a label that loses every voxel
+ * is absent.  With the plane-wise outline this is aliby_tertiary_labels over the F * Z planes: call it on the [F * Z, Y, X] view (no
+ * entry of its own).  At a nucleus's top and bottom caps the plane-wise rule removes the cap's interior although cytoplasm lies above
+ * (below) it, and keeps only the cap's in-plane rim: CellProfiler's way of outlining a volume.
+ * Worked example, a stack [3, 6, 8] (z, y, x), spacing (1, 1, 1).  B = cells: 1 on x 0..3, 2 on x 4..7, every plane and row.
+ * A = nuclei: 1 on z 0..1, y 1..2, x 1..2; 2 on z 1..2, y 3..4, x 3..4; 3 on z 2, y 0, x 6..7.
+ *   nucleus  Parent  ParentOverlap  Children  Distance_Centroid  Distance_Minimum
+ *   1        1       8              1         sqrt(1.25)         sqrt(2.75)
+ *   2        1       4              1         sqrt(5.25)         sqrt(0.75)    (a tie, 4 voxels in either cell: the smaller label)
+ *   3        2       2              0         sqrt(8.25)         0.5
+ *   cell     Parent  ParentOverlap  Children  Distance_Centroid  Distance_Minimum
+ *   1        1       8              2         sqrt(1.25)         sqrt(0.5)
+ *   2        2       4              1         sqrt(5.25)         sqrt(2.5)
+ * Tertiary volumes of cells 1 and 2: 60 and 66 voxels with shrink_inner = 0; 72 and 72 with shrink_inner = 1.
+ * Not built: per-parent means of child measurements, a batched run_positions form.
+ *
+ * The entry fills both directions in one call: rows of A relative to B into out_a, rows of B relative to A into out_b; either may be
+ * NULL (both directions are still computed: column 2 of one needs the parents of the other).  vol_a, vol_b [dev, F x Z x Y x X
+ * uint16]; offsets_a, offsets_b [host, F + 1]: row offsets (offsets[0] = 0, non-decreasing, at most 65535 rows a stack); spacing
+ * [host, 3].  The counters are one int per label of the other set's stack, sized from the largest count of the call: in LDS up to
+ * 8191 labels and in ctx scratch above (same bits).  The object tables, the per-row workspace and those counters live in the
+ * context's scratch, so this is a main-stream call: one in flight per context (the scratch rule, csrc/object_launch.h); it waits for
+ * `stream` before it returns.  offsets_a[F] == offsets_b[F] == 0 launches nothing.  A bad shape, F <= 0, offsets that are not
+ * monotone or a bad spacing is ALIBY_ERR_INVALID with a message.  Results are bitwise independent of the run, of the other stacks of
+ * the call, of the launch form and of the batch.  Kernels: csrc/feat_relate3d.hip. */
+int aliby_features_relate3d(aliby_ctx* ctx, const uint16_t* vol_a, const uint16_t* vol_b, int F, int Z, int Y, int X,
+                            const int32_t* offsets_a, const int32_t* offsets_b, const double* spacing, double* out_a, int ld_a,
+                            int col0_a, double* out_b, int ld_b, int col0_b, void* stream);
 /* "granularity3d": the `granularity` family (aliby_features_granularity: CellProfiler's MeasureGranularity) on the same labelled
  * stacks.  PARITY UNPINNED: CellProfiler's volumetric branch, recalled (tests/granularity3d_ref.py restates it).  Everything is
  * float64; every stack [Z,Y,X] of `channel` is on its own, nothing crosses from one stack of the batch into the next:
