@@ -13,6 +13,11 @@
 //             (persistent workgroups), the pixel operand is one conflict-free ds_read_b128 per MFMA
 //   epilogue  OUT = bf16( D + bias[cout] + RES[n, y>>RU, x>>RU, cout] )  written as 32-byte runs per lane
 //
+// Upsampled input (UP) in the LDS-DMA variant k_conv3x3_dma: both LDS images stay at INPUT resolution, the raw window the DMA
+// writes and the activated planes (DmaCfg::LOWA): a raw pixel is activated and written once (6 x 18 pixels per plane for an
+// 8 x 32 tile, where the output-resolution image had 10 x 34), and the MFMA loop's fragment reads go through the upsample with
+// constant row offsets and two per-lane column bases (conv_mfma LOW).  Same fragments into the same MFMAs: same bits.
+//
 // Operand roles: the weights are the MFMA "A" operand (row m = output channel) and the pixels the "B"
 // operand (column n = pixel), so that a lane ends up with 16 output channels of ONE pixel; the row order of
 // the weights is permuted at pack time so that those 16 channels are contiguous in memory
@@ -113,11 +118,19 @@ __device__ __forceinline__ void conv_seed(f32x16_t (&acc)[R], const float4 (&b4)
 // output rows r = ir - dy it is a tap of, so it is read from LDS once: (R+2)*3*KC ds_read_b128 for 9*KC*R MFMAs.  The
 // reads run DEPTH fragments ahead of their MFMAs through a register ring; the sched_barrier keeps the compiler from
 // hoisting them further (it would spill the resident weights: register budget in ConvCfg / DmaCfg).
-template <int R, int KC, int DEPTH, int PLANE, int LW>
-__device__ __forceinline__ void conv_mfma(const bf16x8_t* L, const bf16x8_t (&wfrag)[9 * KC], f32x16_t (&acc)[R]) {
+// LOW: the planes hold the window at INPUT resolution and the fragments are read through the 2x upsample (k_conv3x3_dma): the
+// pass starts on an even output row, so input row ir of the pass is low row (ir + 1) >> 1 of it, a constant; column offset dx
+// of the lane's pixel px is low column ((px + 1) >> 1) + {0, 1 - (px & 1), 1}: L points at the first, L1 at the second.  LW is
+// the low row width then.  The same fragments enter the same MFMAs in the same order.
+template <int R, int KC, int DEPTH, int PLANE, int LW, bool LOW = false>
+__device__ __forceinline__ void conv_mfma(const bf16x8_t* L, const bf16x8_t (&wfrag)[9 * KC], f32x16_t (&acc)[R], const bf16x8_t* L1 = nullptr) {
   constexpr int NF = (R + 2) * 3 * KC;
   bf16x8_t ring[DEPTH];
-  auto frag = [&](int f) { return L[2 * (f % KC) * PLANE + (f / (3 * KC)) * LW + (f / KC) % 3]; };
+  auto frag = [&](int f) {
+    const int ir = f / (3 * KC), dx = (f / KC) % 3;
+    if constexpr (LOW) return (dx == 1 ? L1 : L)[2 * (f % KC) * PLANE + ((ir + 1) >> 1) * LW + (dx == 2)];
+    else return L[2 * (f % KC) * PLANE + ir * LW + dx];
+  };
 #pragma unroll
   for (int f = 0; f < DEPTH - 1; ++f) ring[f] = frag(f);
   static_for<NF>([&](auto fc) {
@@ -493,12 +506,17 @@ struct DmaCfg {
   static constexpr int RG = 4 / NCB;
   static constexpr int TH = RG * R * PASSES, TW = 32, LH = TH + 2, LW = TW + 2 + (PACK ? 1 : 0);  // PACK: + the seam's zero column
   static constexpr int RAW = LH * LW;
-  static constexpr int PLANE = NPL == 4 ? RAW + (10 - RAW % 8) % 8 : (RAW | 1);
-  static constexpr int A_SLOTS = NPL * PLANE;
-  static constexpr int PIX_PER_IT = 256 / NPL;
-  static constexpr int ITERS = (RAW + PIX_PER_IT - 1) / PIX_PER_IT;
   // raw window (at the input resolution)
   static constexpr int RLH = UP ? TH / 2 + 2 : LH, RLW = UP ? TW / 2 + 2 : LW;
+  // LOWA (upsampled input, not packed): the activated image A stays at the input resolution too, RLH x RLW pixels per octet plane
+  // instead of LH x LW, each raw pixel activated and written once; the MFMA loop reads it through the upsample (conv_mfma LOW)
+  static constexpr bool LOWA = UP && !PACK;
+  static constexpr int APIX = LOWA ? RLH * RLW : RAW;
+  static constexpr int PLANE = NPL == 4 ? APIX + (10 - APIX % 8) % 8 : (APIX | 1);
+  static constexpr int A_SLOTS = NPL * PLANE;
+  static constexpr int PIX_PER_IT = 256 / NPL;
+  static constexpr int ITERS = (APIX + PIX_PER_IT - 1) / PIX_PER_IT;
+  static_assert(!LOWA || (R % 2 == 0 && 256 % NPL == 0), "LOWA: passes start on even rows; a thread activates the units it fetched");
   static constexpr int RUNITS = RLH * RLW * NPL;            // 16-byte units
   static constexpr int GIT = (RUNITS + 255) / 256;          // DMA instructions per wave and tile
   static constexpr int R_SLOTS = GIT * 256;
@@ -616,7 +634,21 @@ __global__ __launch_bounds__(256, (DmaCfg<CIN, COUT, UP, PACK>::WAVES_PER_SIMD))
     __syncthreads();                                   // ... and everyone's; the previous tile's reads of A are over
     CONV_STAMP(2);
     // ---- prologue R -> A
-    {
+    if constexpr (cfg::LOWA) {  // pixel by pixel of the raw window: unit tid + 256 it is octet pl of raw pixel pix0 + it PIX_PER_IT
+      const int ry0 = (y0 >> 1) - 1, rx0 = (x0 >> 1) - 1;
+      int p0 = pix0;
+      asm volatile("" : "+v"(p0));
+#pragma unroll
+      for (int it = 0; it < ITERS; ++it) {
+        const int rpix = p0 + it * PIX_PER_IT;
+        const int rly = rpix / RLW, rlx = rpix - rly * RLW;
+        const unsigned keep = 0u - (unsigned)((unsigned)(ry0 + rly) < (unsigned)IH && (unsigned)(rx0 + rlx) < (unsigned)IW);
+        // (the last round can run past the window: its raw index is clamped, its value never stored)
+        const uint4 o = conv_act8(ldsR[min(rpix, cfg::APIX - 1) * NPL + pl], sc, sh, keep);
+        if (it == ITERS - 1 && rpix >= cfg::APIX) continue;
+        ldsA[pl * PLANE + rpix] = o;
+      }
+    } else {
       const int ry0 = UP ? (y0 >> 1) - 1 : y0 - 1, rx0 = UP ? (x0 >> 1) - 1 : x0 - 1;
       int p0 = pix0, qy = ly0, qx = lx0;
       asm volatile("" : "+v"(p0), "+v"(qy), "+v"(qx));
@@ -664,7 +696,12 @@ __global__ __launch_bounds__(256, (DmaCfg<CIN, COUT, UP, PACK>::WAVES_PER_SIMD))
       if (pass + 1 < PASSES && a.res) load_res(pass + 1);                   // consumed after this pass's MFMA loop
       __builtin_amdgcn_sched_barrier(0);
       if (pass == 0) CONV_STAMP(4);
-      conv_mfma<R, KC, cfg::DEPTH, PLANE, LW>(reinterpret_cast<const bf16x8_t*>(ldsA) + hh * PLANE + rbase * LW + px + second, wfrag, acc);
+      if constexpr (cfg::LOWA) {
+        const bf16x8_t* L0 = reinterpret_cast<const bf16x8_t*>(ldsA) + hh * PLANE + (rbase >> 1) * RLW + ((px + 1) >> 1);
+        conv_mfma<R, KC, cfg::DEPTH, PLANE, RLW, true>(L0, wfrag, acc, L0 + 1 - (px & 1));
+      } else {
+        conv_mfma<R, KC, cfg::DEPTH, PLANE, LW>(reinterpret_cast<const bf16x8_t*>(ldsA) + hh * PLANE + rbase * LW + px + second, wfrag, acc);
+      }
       if (pass == PASSES - 1) CONV_STAMP(5);
       conv_store<R>(a, nimg, irow, y0 + rbase, gx, c0, acc);
     }

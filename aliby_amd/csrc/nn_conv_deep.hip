@@ -22,10 +22,17 @@
 //   * weights are NOT resident (9 * CIN/16 fragments per wave do not fit beside the accumulators): each (tap, k-step)
 //     fragment — 1 KiB per wave, already in fragment order in the packed array, L2-resident — is loaded straight into VGPRs
 //     through a 3-deep ring, seven MFMAs of cover each;
-//   * two workgroups per CU (<= 256 VGPRs, 44 KiB of LDS each) overlap each other's staging and MFMA phases.
+//   * two workgroups per CU (<= 256 VGPRs, 44 KiB of LDS each) overlap each other's staging and MFMA phases;
+//   * input read through the 2x upsample (UP): the window is kept at INPUT resolution, the same tall image built over the
+//     H/2 x W/2 inputs (conv_upmap.h).  A tile's window is then the <= DCU_WIN_MAX low positions that cover it: every raw pixel
+//     is fetched, activated and written to LDS once per slice (5 staging rounds per thread instead of 11, 20 window registers
+//     instead of 44, 25 KiB of LDS instead of 71), and the MFMA loop's fragment address is the lane's low base plus 0 / row parity / 1 low rows
+//     and 0 / column parity / 1 columns: one v_add per read.  The same values enter the same MFMAs in the same order as with the
+//     window at output resolution: same bits (tests/test_gpu_conv_upstage.py, against in_up = 0 on the materialised upsample).
 #include "common.h"
 #include "conv_launch.h"
 #include "conv_mfma.h"
+#include "conv_upmap.h"
 
 namespace {
 
@@ -64,12 +71,28 @@ constexpr int DC_LDS_BYTES = 8 * DC_PLANE * 16 + DC_ITERS * 256 * 4 + 3 * 256 * 
 constexpr int DC_WDEPTH = 3;  // weight fragments in flight
 constexpr int DC_PDEPTH = 4;  // pixel fragments in flight
 constexpr int DC_REQ_AT = 27;  // weight fragment (of 36 per slice) before which the next slice's window is requested
+// The UP instantiations keep the window at INPUT resolution (conv_upmap.h): a quarter of the pixels, each fetched, activated and
+// written to LDS once; the MFMA loop's fragment reads go through the upsample.  DCU_WIN_MAX low positions cover every tile of every
+// shape the entry point admits (up_win_fits checks the launch's own tiles; 145 is the most any even H, W <= DC_WMAX needs).
+constexpr int DCU_WIN_MAX = 160;
+constexpr int DCU_PLANE = DCU_WIN_MAX | 1;  // odd slot pitch: a ds_write_b128 lane group is the 8 octets of one position
+constexpr int DCU_ITERS = DCU_WIN_MAX / 32;
+constexpr int DCU_LDS_BYTES = 8 * DCU_PLANE * 16 + DCU_ITERS * 256 * 4;  // planes + per-thread input offsets
+static_assert(DCU_WIN_MAX % 32 == 0 && DCU_WIN_MAX >= 2 * (DC_WMAX / 2 + 2) + 2, "window image of the UP form");
 
 // ---- the stages that the three kernels of this file share (they differ in their K loops)
 // 32 positions further in the tall image: column c, row y of image n
 __device__ __forceinline__ void dc_step32(int& c, int& y, int& n, int LW, int HP) {
   c += 32;
   while (c >= LW) {  // (at most two wraps: LW >= 30 at the levels these kernels serve)
+    c -= LW;
+    if (++y == HP) { y = 0; ++n; }
+  }
+}
+// pos positions further, any pos >= 0
+__device__ __forceinline__ void dc_step(int& c, int& y, int& n, int LW, int HP, int pos) {
+  c += pos;
+  while (c >= LW) {
     c -= LW;
     if (++y == HP) { y = 0; ++n; }
   }
@@ -99,6 +122,37 @@ __device__ __forceinline__ int dc_win_off(const DeepArgs& a, int c, int y, int n
   later |= (unsigned)(n > n0) << bit;
   const int nn = min(n, a.N - 1), yy = min(max(y, 0), a.H - 1), xx = min(max(c - 1, 0), a.W - 1);
   return ((nn * IH + (UP ? yy >> 1 : yy)) * IW + (UP ? xx >> 1 : xx)) * cs + oct;
+}
+// the same for a position (c, y, n) of the tall image at INPUT resolution (the UP forms: conv_upmap.h)
+__device__ __forceinline__ int dc_low_off(const DeepArgs& a, int c, int y, int n, int n0, int cs, int oct, bool valid, int bit,
+                                          unsigned& inside, unsigned& later) {
+  const int IH = a.H >> 1, IW = a.W >> 1;
+  const bool ok = valid && y >= 0 && y < IH && c >= 1 && c <= IW && n < a.N;
+  inside |= (unsigned)ok << bit;
+  later |= (unsigned)(n > n0) << bit;
+  const int nn = min(n, a.N - 1), yy = min(max(y, 0), IH - 1), xx = min(max(c - 1, 0), IW - 1);
+  return ((nn * IH + yy) * IW + xx) * cs + oct;
+}
+// UP forms: this lane's window addresses.  lb[b]: slot of the first window position of output position q0 + px + 32 b in the
+// low window image that starts at low position lstart, bit b of rbits: its row parity bit (up_row_bit).  Clamped so that every
+// tap of every lane reads inside a plane of `plane` slots (the positions that are not stored may read anything there)
+__device__ __forceinline__ void dc_low_bases(int q0, int px, int LW, int HP, int lstart, int plane, int (&lb)[DC_NB], unsigned& rbits) {
+  const int LWl = up_low_width(LW);
+  int c, y, n;
+  dc_out_pos(q0 + px, LW, HP, c, y, n);
+  rbits = 0;
+#pragma unroll
+  for (int b = 0; b < DC_NB; ++b) {
+    lb[b] = min(max(up_base(c, y, n, LW, HP) - lstart, 0), plane - LWl - 2);
+    rbits |= (unsigned)up_row_bit(y) << b;
+    dc_step32(c, y, n, LW, HP);
+  }
+}
+// (The fragment addresses of a k-step are sums of lb[b], the row term and the column bit.  Re-read through an empty asm at the head of
+// every k-step, the sums are formed again where they are used, one v_add per read, instead of being kept for the slice's other
+// k-steps in registers that the accumulators do not leave: that spills.)
+__device__ __forceinline__ void dc_fresh(int (&lb)[DC_NB]) {
+  asm volatile("" : "+v"(lb[0]), "+v"(lb[1]), "+v"(lb[2]), "+v"(lb[3]), "+v"(lb[4]), "+v"(lb[5]), "+v"(lb[6]));
 }
 // prologue constants of K slice s for one channel octet: scale, and the style shifts of images n0 and n1
 __device__ __forceinline__ void dc_prologue_consts(const DeepArgs& a, int s, int oct, int n0, int n1, f32x2_t (&sc)[4], f32x2_t (&sh)[4],
@@ -179,9 +233,12 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep(DeepArgs a) {
   const int px = lane & 31, hh = lane >> 5;
   const int pl = tid & 7, pos0 = tid >> 3;  // staging role: a fixed channel octet of position pos0 + 32 * round
   const int LW = a.LW, HP = a.HP;
-  const int WIN = DC_RUN + 2 * LW + 2;
+  // the window image in LDS: at output resolution, or (UP) at input resolution, DCU_* and conv_upmap.h
+  constexpr int PLANE = UP ? DCU_PLANE : DC_PLANE, ITERS = UP ? DCU_ITERS : DC_ITERS;
+  const int LWI = UP ? up_low_width(LW) : LW, HPI = UP ? up_low_period(HP) : HP;  // its row width and period
+  int WIN = DC_RUN + 2 * LW + 2;  // its positions (UP: per tile)
   const int cs = CIN / 8;
-  int* const goff = reinterpret_cast<int*>(lds + 8 * DC_PLANE) + tid;  // goff[it * 256]: this thread's input offsets of the tile
+  int* const goff = reinterpret_cast<int*>(lds + 8 * PLANE) + tid;  // goff[it * 256]: this thread's input offsets of the tile
 
   const TileWalk walk = tile_walk(a.ntiles, a.order);
   if ((blockIdx.x >> 3) >= (gridDim.x >> 4))  // the upper half of every XCD's slots
@@ -192,28 +249,36 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep(DeepArgs a) {
     DC_STAMP(0);
     const int half = tile % a.nhalf, run = tile / a.nhalf;
     const int q0 = a.q_begin + run * DC_RUN;
-    const int p_first = q0 - LW - 1;  // flat index of window position 0
+    int p_first = q0 - LW - 1;  // flat index of window position 0 (UP: in the low tall image)
     // ---- this thread's window positions -> input pixel offsets, once per tile (they do not depend on the K slice):
     // (r, c) of the first position by division, the following ones by stepping 32 positions at a time
     unsigned inside = 0, later = 0;
     const int n0 = max(0, ((p_first / LW) - 1) / HP);  // image of the window's first row (clamped)
+    int c, y, n;
+    if constexpr (UP) {  // (the first low position as column, row, image, and this thread's by stepping: no division by LWI, HPI)
+      up_win_span(q0, DC_RUN, LW, HP, p_first, WIN, n, y, c);
+      WIN = min(WIN, DCU_WIN_MAX);  // (the launch has checked that no tile needs more)
+      if (--y < 0 && n > 0) { y = HPI - 1; --n; }
+      dc_step(c, y, n, LWI, HPI, pos0);
+    } else {
+      dc_win_pos(p_first + pos0, LWI, HPI, c, y, n);
+    }
     {
-      int c, y, n;
-      dc_win_pos(p_first + pos0, LW, HP, c, y, n);
 #pragma unroll
-      for (int it = 0; it < DC_ITERS; ++it) {
-        goff[it * 256] = dc_win_off<UP>(a, c, y, n, n0, cs, pl, true, it, inside, later);
-        dc_step32(c, y, n, LW, HP);
+      for (int it = 0; it < ITERS; ++it) {
+        if constexpr (UP) goff[it * 256] = dc_low_off(a, c, y, n, n0, cs, pl, pos0 + 32 * it < WIN, it, inside, later);
+        else goff[it * 256] = dc_win_off<UP>(a, c, y, n, n0, cs, pl, true, it, inside, later);
+        dc_step32(c, y, n, LWI, HPI);
       }
     }
     const int n1 = min(n0 + 1, a.N - 1);
     // The raw window of a slice travels global -> registers while the matrix cores still work on the previous slice (the
     // loads are issued before the last k-step's 63 MFMAs): a slice's staging phase is then prologue + LDS writes only.
-    uint4 v[DC_ITERS];
+    uint4 v[ITERS];
     auto request = [&](int s) {
       const uint4* inS = a.in + s * 8;
 #pragma unroll
-      for (int it = 0; it < DC_ITERS; ++it) v[it] = inS[(unsigned)goff[it * 256]];
+      for (int it = 0; it < ITERS; ++it) v[it] = inS[(unsigned)goff[it * 256]];
     };
     request(0);
 
@@ -221,6 +286,9 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep(DeepArgs a) {
     const int ocs = a.COUT / 8;
     f32x16_t acc[DC_NB];
     dc_seed32(a, q0, px, c0, ocs, LW, HP, acc);
+    int lb[DC_NB];  // UP: this lane's window slots and row parities (dc_low_bases)
+    unsigned rbits;
+    if constexpr (UP) dc_low_bases(q0, px, LW, HP, p_first, PLANE, lb, rbits);
     const bf16x8_t* wbase = reinterpret_cast<const bf16x8_t*>(a.wpk) + (size_t)(half * 4 + cb) * 9 * KCT * 64 + lane;
     DC_STAMP(1);
 
@@ -239,31 +307,34 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep(DeepArgs a) {
       DC_STAMP(2 + 4 * s);
       // ---- stage: prologue (BatchNorm affine + style shift + ReLU, zero outside the image) into the octet planes
 #pragma unroll
-      for (int it = 0; it < DC_ITERS; ++it) {
+      for (int it = 0; it < ITERS; ++it) {
         f32x2_t shs[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) shs[k] = ((later >> it) & 1u) ? sh1[k] : sh[k];
         const uint4 o = conv_act8(v[it], sc, shs, 0u - ((inside >> it) & 1u));
         const int wp_ = pos0 + 32 * it;
-        if (wp_ < WIN) lds[pl * DC_PLANE + wp_] = o;
+        if (wp_ < WIN) lds[pl * PLANE + wp_] = o;
       }
       DC_STAMP(3 + 4 * s);
       __syncthreads();
       DC_STAMP(4 + 4 * s);
 
       // ---- 4 k-steps x 9 taps x 7 blocks; weight fragment (tap, k-step) comes from global through the ring
-      const bf16x8_t* L = reinterpret_cast<const bf16x8_t*>(lds) + hh * DC_PLANE + px;
+      const bf16x8_t* L = reinterpret_cast<const bf16x8_t*>(lds) + hh * PLANE + (UP ? 0 : px);
       const int row_off[3] = {0, LW, 2 * LW};
+      const int cbit = up_col_bit(px);  // (LW and the tile's first position are even: the column's parity is the lane's)
       constexpr int NF = NW * DC_NB;  // pixel fragments (= MFMAs) per slice
       bf16x8_t pring[DC_PDEPTH];
       auto pfrag = [&](int f) {
         const int i = f / DC_NB, b = f % DC_NB, kc = i / 9, tap = i % 9;
-        return L[2 * kc * DC_PLANE + b * 32 + row_off[tap / 3] + tap % 3];
+        if constexpr (UP) return L[2 * kc * PLANE + up_tap(lb[b], (rbits >> b) & 1u, cbit, LWI, tap / 3, tap % 3)];
+        else return L[2 * kc * PLANE + b * 32 + row_off[tap / 3] + tap % 3];
       };
 #pragma unroll
       for (int f = 0; f < DC_PDEPTH - 1; ++f) pring[f] = pfrag(f);
       static_for<NW>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
+        if constexpr (UP && i % 9 == 0) dc_fresh(lb);
         if constexpr (i == DC_REQ_AT) {  // request the next slice's window (see DC_REQ_AT)
           if (s + 1 < S) request(s + 1);
           __builtin_amdgcn_sched_barrier(0);
@@ -294,26 +365,31 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_deep(DeepArgs a) {
 // (run + 2 LW + 2) is 1.5 runs at LW = 114 where one position group would stage 2.0.  What changes against k_conv3x3_deep:
 //   * K slices of 32 channels (4 octet planes, two k-steps): the window of 448 + 2 LW + 2 positions x 64 channels is 85 KiB and
 //     would leave one workgroup per CU (3.2: 691 against 888 TFLOP/s), and its raw copy 88 registers per thread; with 32
-//     channels the planes are 44 KiB and the raw window 48 registers, as in k_conv3x3_deep;
+//     channels the planes were 44 KiB and the raw window 48 registers, as in k_conv3x3_deep (before the window moved to input
+//     resolution: now 20 KiB and 20 registers, the slice width stays);
 //   * the slice's weight ring is 6 fragments deep and the next slice's window is requested right after the slice's LAST
 //     fragment load has been issued: the vmcnt counter retires in order, so a fragment requested behind the window loads would
 //     make its MFMAs wait for HBM (the k_conv3x3_deep_ls note below); here nothing that the running slice needs is behind them;
-//   * the raw window is read at half resolution through dc_win_off<true>: the 2 x 2 positions of a raw pixel are neighbouring
-//     lanes or come from L2, HBM sees each raw pixel once per slice.
+//   * the window image is kept at INPUT resolution, as in the UP forms of k_conv3x3_deep (DCU_*, conv_upmap.h): every raw pixel
+//     of the window is fetched, activated and written to LDS once per slice (5 staging rounds per thread, 11 at output
+//     resolution), and the fragment reads go through the upsample.  This kernel has no other form: its one user reads through
+//     the upsample.
 // Any H, W with W <= U_WMAX; summation order: channels 0-15, 16-31, ... of every tap in turn, fp32 throughout.
 constexpr int U_RUN = 2 * DC_RUN;     // output positions per tile: two position groups of DC_NB blocks
 constexpr int U_WMAX = 128;           // widest image the LDS window is sized for
-constexpr int U_WIN_MAX = U_RUN + 2 * (U_WMAX + 2) + 2;
-constexpr int U_PLANE = U_WIN_MAX | 1;            // odd slot pitch, as DC_PLANE
-constexpr int U_ITERS = (U_WIN_MAX + 63) / 64;    // staging rounds: 64 positions x 4 octets per round of 256 threads
-constexpr int U_LDS_BYTES = 4 * U_PLANE * 16 + U_ITERS * 256 * 4;  // planes + per-thread input offsets
 constexpr int U_NW = 18;              // weight fragments per slice, in (k-step, tap) order
 constexpr int U_WDEPTH = 6;           // weight fragments in flight
 constexpr int U_REQ_AT = U_NW - U_WDEPTH;  // the step that issues the slice's last fragment load, then the next window's request
-static_assert(U_ITERS <= 32, "the inside / later masks hold one bit per staging round");
+// the window image: 294 low positions is the most any even H, W <= U_WMAX needs (up_win_fits checks the launch's own tiles)
+constexpr int UU_WIN_MAX = 320;
+constexpr int UU_PLANE = UU_WIN_MAX + 2;  // pitch = 2 mod 4: a ds_write_b128 lane group is 4 octets x 2 positions, 8 distinct slots of 8
+constexpr int UU_ITERS = UU_WIN_MAX / 64;  // staging rounds: 64 positions x 4 octets per round of 256 threads
+constexpr int UU_LDS_BYTES = 4 * UU_PLANE * 16 + UU_ITERS * 256 * 4;  // planes + per-thread input offsets
+static_assert(UU_WIN_MAX % 64 == 0 && UU_PLANE % 4 == 2 && UU_WIN_MAX >= 2 * (U_WMAX / 2 + 2) + 2, "window image of the UP form");
 
 template <int CIN, bool UP>
 __global__ __launch_bounds__(256, 2) void k_conv3x3_kloop64(DeepArgs a) {
+  static_assert(UP, "k_conv3x3_kloop64 reads its input through the 2x upsample");
   constexpr int S = CIN / 32, KCT = CIN / 16;  // K slices, k-steps in the packed array
   extern __shared__ uint4 lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -321,34 +397,40 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_kloop64(DeepArgs a) {
   const int px = lane & 31, hh = lane >> 5;
   const int pl = tid & 3, pos0 = tid >> 2;  // staging role: a fixed channel octet of position pos0 + 64 * round
   const int LW = a.LW, HP = a.HP;
-  const int WIN = U_RUN + 2 * LW + 2;
+  // the window image in LDS, at input resolution (UU_*, conv_upmap.h)
+  constexpr int PLANE = UU_PLANE, ITERS = UU_ITERS;
+  const int LWI = up_low_width(LW), HPI = up_low_period(HP);  // its row width and period
   const int cs = CIN / 8;
-  int* const goff = reinterpret_cast<int*>(lds + 4 * U_PLANE) + tid;  // goff[it * 256]: this thread's input offsets of the tile
+  int* const goff = reinterpret_cast<int*>(lds + 4 * PLANE) + tid;  // goff[it * 256]: this thread's input offsets of the tile
 
   const TileWalk walk = tile_walk(a.ntiles, a.order);
 
   for (int ti = 0; ti < walk.count; ++ti) {
     const int tile = walk.first + ti * walk.step;
     const int q0 = a.q_begin + tile * U_RUN;
-    const int p_first = q0 - LW - 1;  // flat index of window position 0
     unsigned inside = 0, later = 0;
-    const int n0 = max(0, ((p_first / LW) - 1) / HP);  // image of the window's first row (clamped)
+    const int n0 = max(0, (((q0 - LW - 1) / LW) - 1) / HP);  // image of the window's first row (clamped)
+    // the window in the low tall image: WIN positions from p_first on.  The first one as column, row, image, and this thread's by
+    // stepping: no division by LWI, HPI
+    int p_first, WIN, c, y, n;
+    up_win_span(q0, U_RUN, LW, HP, p_first, WIN, n, y, c);
+    WIN = min(WIN, UU_WIN_MAX);  // (the launch has checked that no tile needs more)
+    if (--y < 0 && n > 0) { y = HPI - 1; --n; }
+    dc_step(c, y, n, LWI, HPI, pos0);
     {
-      int c, y, n;
-      dc_win_pos(p_first + pos0, LW, HP, c, y, n);
 #pragma unroll
-      for (int it = 0; it < U_ITERS; ++it) {
-        goff[it * 256] = dc_win_off<UP>(a, c, y, n, n0, cs, pl, true, it, inside, later);
-        dc_step32(c, y, n, LW, HP);
-        dc_step32(c, y, n, LW, HP);
+      for (int it = 0; it < ITERS; ++it) {
+        goff[it * 256] = dc_low_off(a, c, y, n, n0, cs, pl, pos0 + 64 * it < WIN, it, inside, later);
+        dc_step32(c, y, n, LWI, HPI);
+        dc_step32(c, y, n, LWI, HPI);
       }
     }
     const int n1 = min(n0 + 1, a.N - 1);
-    uint4 v[U_ITERS];
+    uint4 v[ITERS];
     auto request = [&](int s) {
       const uint4* inS = a.in + s * 4;
 #pragma unroll
-      for (int it = 0; it < U_ITERS; ++it) v[it] = inS[(unsigned)goff[it * 256]];
+      for (int it = 0; it < ITERS; ++it) v[it] = inS[(unsigned)goff[it * 256]];
     };
     request(0);
 
@@ -357,8 +439,12 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_kloop64(DeepArgs a) {
     const int ocs = a.COUT / 8;
     f32x16_t acc[DC_NB];
     dc_seed32(a, qw, px, c0, ocs, LW, HP, acc);
+    int lb[DC_NB];  // this lane's window slots and row parities
+    unsigned rbits;
+    dc_low_bases(qw, px, LW, HP, p_first, PLANE, lb, rbits);
     const bf16x8_t* wbase = reinterpret_cast<const bf16x8_t*>(a.wpk) + (size_t)cb * 9 * KCT * 64 + lane;
 
+#pragma unroll 1
     for (int s = 0; s < S; ++s) {
       const bf16x8_t* wp = wbase + (size_t)(2 * s) * 64;  // fragment (tap, kc) of this slice at wp[(tap * KCT + kc) * 64]
       bf16x8_t wring[U_WDEPTH];
@@ -372,29 +458,30 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_kloop64(DeepArgs a) {
       asm volatile("" : "+v"(inside), "+v"(later));
       __syncthreads();  // every wave is done reading the previous slice's planes
 #pragma unroll
-      for (int it = 0; it < U_ITERS; ++it) {
+      for (int it = 0; it < ITERS; ++it) {
         f32x2_t shs[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) shs[k] = ((later >> it) & 1u) ? sh1[k] : sh[k];
         const uint4 o = conv_act8(v[it], sc, shs, 0u - ((inside >> it) & 1u));
         const int wp_ = pos0 + 64 * it;
-        if (wp_ < WIN) lds[pl * U_PLANE + wp_] = o;
+        if (wp_ < WIN) lds[pl * PLANE + wp_] = o;
       }
       __syncthreads();
 
       // ---- 2 k-steps x 9 taps x 7 blocks
-      const bf16x8_t* L = reinterpret_cast<const bf16x8_t*>(lds) + hh * U_PLANE + pg * DC_RUN + px;
-      const int row_off[3] = {0, LW, 2 * LW};
+      const bf16x8_t* L = reinterpret_cast<const bf16x8_t*>(lds) + hh * PLANE;
+      const int cbit = up_col_bit(px);  // (LW and the wave's first position are even: the column's parity is the lane's)
       constexpr int NF = U_NW * DC_NB;  // pixel fragments (= MFMAs) per slice
       bf16x8_t pring[DC_PDEPTH];
       auto pfrag = [&](int f) {
         const int i = f / DC_NB, b = f % DC_NB, kc = i / 9, tap = i % 9;
-        return L[2 * kc * U_PLANE + b * 32 + row_off[tap / 3] + tap % 3];
+        return L[2 * kc * PLANE + up_tap(lb[b], (rbits >> b) & 1u, cbit, LWI, tap / 3, tap % 3)];
       };
 #pragma unroll
       for (int f = 0; f < DC_PDEPTH - 1; ++f) pring[f] = pfrag(f);
       static_for<U_NW>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
+        if constexpr (i % 9 == 0) dc_fresh(lb);
         if constexpr (i + U_WDEPTH - 1 < U_NW) wring[(i + U_WDEPTH - 1) % U_WDEPTH] = wfrag(i + U_WDEPTH - 1);
         if constexpr (i == U_REQ_AT) {
           __builtin_amdgcn_sched_barrier(0);
@@ -841,6 +928,23 @@ static int deep_args(DeepArgs& a, aliby_ctx* ctx, const void* in, const void* wp
   return ALIBY_OK;
 }
 
+// UP forms: does the window image of `cap` low positions hold the window of every tile of this launch?  It does for every
+// even H, W within the kernels' width limits that has been tried; the walk over the tiles (remembered for the last shape) is what
+// makes that a checked fact for the launch at hand instead of a bound to be proven over all shapes.
+static bool up_win_fits(const DeepArgs& a, int run, int cap) {
+  thread_local int key[4] = {0, 0, 0, 0}, most = 0;
+  if (key[0] != run || key[1] != a.H || key[2] != a.W || key[3] != a.N) {
+    most = 0;
+    for (int t = 0; t < a.nruns; ++t) {
+      int lstart, count;
+      up_win_span(a.q_begin + t * run, run, a.LW, a.HP, lstart, count);
+      most = count > most ? count : most;
+    }
+    key[0] = run; key[1] = a.H; key[2] = a.W; key[3] = a.N;
+  }
+  return most <= cap;
+}
+
 static int deep_entry(aliby_ctx* ctx, const void* in, const void* wpk, void* out, const float* scale, const float* shift,
                       int shift_per_sample, const float* bias, const void* res, int res_up, int N, int H, int W, int CIN, int COUT,
                       int in_up, void* stream_, bool m16) {
@@ -861,6 +965,10 @@ static int deep_entry(aliby_ctx* ctx, const void* in, const void* wpk, void* out
   DeepArgs a;
   if (const int rc = deep_args(a, ctx, in, wpk, out, scale, shift, shift_per_sample, bias, res, res_up, N, H, W, CIN, COUT, DC_RUN, COUT / 128))
     return rc;
+  if (in_up && !m16 && !up_win_fits(a, DC_RUN, DCU_WIN_MAX)) {
+    aliby_set_error("conv3x3_deep: a tile of the upsampled %dx%d input needs more than %d window positions", H, W, DCU_WIN_MAX);
+    return ALIBY_ERR_UNSUPPORTED;
+  }
   static const int stagger = env_int("ALIBY_DEEP_STAGGER", 0);
   a.stagger = stagger;
   a.trace = g_deep_trace;
@@ -872,7 +980,7 @@ static int deep_entry(aliby_ctx* ctx, const void* in, const void* wpk, void* out
     constexpr bool U = decltype(up)::value;
     if (m16) return launch<k_conv3x3_deep16<C, U>, 256>(ctx, a, DC16_LDS_BYTES, 64, stream);
     if (ls) return launch<k_conv3x3_deep_ls<C, U>, 256 + DL_LT>(ctx, a, DL_LDS_BYTES, 32, stream);
-    return launch<k_conv3x3_deep<C, U>, 256>(ctx, a, DC_LDS_BYTES, slots, stream);
+    return launch<k_conv3x3_deep<C, U>, 256>(ctx, a, U ? DCU_LDS_BYTES : DC_LDS_BYTES, slots, stream);
   };
   auto by_up = [&](auto cin) { return in_up ? go(cin, std::true_type{}) : go(cin, std::false_type{}); };
   if (CIN == 64) return by_up(std::integral_constant<int, 64>{});
@@ -932,7 +1040,11 @@ extern "C" int aliby_nn_conv3x3_kloop64_bf16(aliby_ctx* ctx, const void* in, con
   DeepArgs a;
   if (const int rc = deep_args(a, ctx, in, wpk, out, scale, shift, shift_per_sample, bias, res, res_up, N, H, W, CIN, COUT, U_RUN, 1))
     return rc;
-  return launch<k_conv3x3_kloop64<128, true>, 256>(ctx, a, U_LDS_BYTES, 64, stream);  // 2 workgroups per CU, 32 CUs per XCD
+  if (!up_win_fits(a, U_RUN, UU_WIN_MAX)) {
+    aliby_set_error("conv3x3_kloop64: a tile of the upsampled %dx%d input needs more than %d window positions", H, W, UU_WIN_MAX);
+    return ALIBY_ERR_UNSUPPORTED;
+  }
+  return launch<k_conv3x3_kloop64<128, true>, 256>(ctx, a, UU_LDS_BYTES, 64, stream);  // 2 workgroups per CU, 32 CUs per XCD
 }
 
 extern "C" int aliby_nn_conv3x3_kloop_limits(int limits[4]) {
