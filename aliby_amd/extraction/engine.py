@@ -763,6 +763,29 @@ class FeatureEngine:
                                                           _ptr(out), _stream_ptr()))
         return out
 
+    def secondary_labels(self, primary, distance) -> torch.Tensor:
+        """primary uint16 [F,Y,X] on the device -> device uint16 [F,Y,X] (aliby_secondary_labels): CellProfiler's
+        IdentifySecondaryObjects, method "Distance - N" (skimage's expand_labels) — every object grows by up to `distance` pixels into
+        the background, each grown pixel taking the label of the nearest labelled pixel of its tile by exact integer squared distance,
+        ties to the smaller label (SciPy's choice on a tie follows its sweep order).  Labels keep the primary numbering, so a secondary
+        row joins its primary on the label; nothing crosses a tile edge.  `distance`: an integer in 1..64.  A tensor that is not
+        uint16 [F,Y,X] on the device, and a bad distance, are ValueErrors.  Integer arithmetic: the same bits whatever the batch and
+        the stream.  Uses no context scratch (its 4-bytes-per-pixel workspace is allocated here)."""
+        n = feat.secondary_distance(distance)
+        if not isinstance(primary, torch.Tensor) or primary.dtype != torch.uint16 or primary.dim() != 3 or not primary.is_cuda:
+            raise ValueError(f"secondary_labels: primary must be a uint16 [F,Y,X] tensor on the device, got "
+                             f"{(primary.dtype, tuple(primary.shape)) if isinstance(primary, torch.Tensor) else type(primary).__name__}")
+        primary = primary.contiguous()
+        F, Y, X = (int(v) for v in primary.shape)
+        out = torch.empty_like(primary)
+        if out.numel():
+            nbytes = int(self.lib.aliby_secondary_workspace_bytes(F, Y, X))
+            work = torch.empty(nbytes // 4, dtype=torch.int32, device=primary.device)
+            with self.timed("secondary"):
+                _lib.check(self.lib.aliby_secondary_labels(self.ctx.handle, _ptr(primary), F, Y, X, n, _ptr(work), nbytes, _ptr(out),
+                                                           _stream_ptr()))
+        return out
+
     def _relate3d_out(self, which: str, out, col0, rows: int):
         """The output window of one side of `relate3d`: a new NaN matrix [rows, 5], or columns col0..col0+4 of `out`."""
         if out is None:

@@ -358,6 +358,18 @@ def tertiary_masks(outer, inner, shrink_inner=True, who="tertiary"):
     return tiles if isinstance(outer, (list, tuple)) else tiles[0]
 
 
+def secondary_masks(primary, distance, who="secondary"):
+    """The secondary labels of one segment result (FeatureEngine.secondary_labels: every object of `primary` grown by up to `distance`
+    pixels, the cell around a nucleus) in the container `primary` came in: one [Y,X] uint16 image or a list of them, each with its
+    device copy attached (devcache, kind="labels"), so that an extract step after it measures them as it measures a segment step's."""
+    from aliby_amd.extraction.engine import FeatureEngine
+
+    dev = FeatureEngine().secondary_labels(_stack_masks(_tile_list(who, primary)), distance)
+    host = dev.cpu().numpy()
+    tiles = [devcache.attach(host[k], dev[k], kind="labels") for k in range(host.shape[0])]
+    return tiles if isinstance(primary, (list, tuple)) else tiles[0]
+
+
 def relate_masks(masks, others: dict, who="extractrelate"):
     """The rows of the objects of `masks` relative to every object set of `others` {name: its segment result}: returns
     (tileid_instructions, results) like process_tree_masks, with the single instruction RELATE_INSTRUCTION and the columns

@@ -176,6 +176,20 @@ def neighbors_names(distance=None) -> list[str]:
     return _neighbors_names("Adjacent" if distance is None else str(neighbors_distance(distance)))
 
 
+SECONDARY_MAX_DISTANCE = 64  # bounds the row scan of csrc/feat_secondary.hip; not a structural limit
+
+
+def secondary_distance(distance) -> int:
+    """The N of "Distance - N" (FeatureEngine.secondary_labels, a `secondary_<name>` step): an integer in 1..64, or a float that holds
+    one (5.0, as a settings file may spell it).  A bool, any other float, 0, 65 and anything that is not a number are ValueErrors.
+    Needs no device."""
+    ok = not isinstance(distance, bool) and (isinstance(distance, numbers.Integral)
+                                             or (isinstance(distance, numbers.Real) and float(distance).is_integer()))
+    if not ok or not 1 <= int(distance) <= SECONDARY_MAX_DISTANCE:
+        raise ValueError(f"secondary: distance must be an integer in 1..{SECONDARY_MAX_DISTANCE}, got {distance!r}")
+    return int(distance)
+
+
 def relate_names(other: str) -> list[str]:
     """Columns of `FeatureEngine.relate` for rows related to the object set `other` (csrc/feat_relate.hip): CellProfiler's
     RelateObjects — the parent in `other`, the overlap that chose it, the number of children in `other`, the distance between the

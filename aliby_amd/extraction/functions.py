@@ -116,6 +116,15 @@ def tertiary_objects(outer, inner, shrink_inner=True) -> np.ndarray:
     return eng.tertiary_labels(a, b, shrink_inner=shrink_inner)[0].cpu().numpy()
 
 
+def secondary_objects(primary_labels, distance) -> np.ndarray:
+    """One label image [Y, X] -> uint16 [Y, X]: every object grown by up to `distance` pixels (an integer in 1..64) into the
+    background, a grown pixel taking the label of the nearest labelled pixel, ties to the smaller label
+    (FeatureEngine.secondary_labels, csrc/feat_secondary.hip).  The cell around a nucleus is secondary_objects(nuclei, 10), and the
+    cytoplasm tertiary_objects(that, nuclei).  Not in the reference: CellProfiler's IdentifySecondaryObjects, method "Distance - N",
+    equal to scipy's distance_transform_edt index gather except on ties (include/aliby_hip.h)."""
+    return FeatureEngine().secondary_labels(_label_tile("primary_labels", primary_labels), distance)[0].cpu().numpy()
+
+
 def _label_stack(name: str, labels):
     labels = np.asarray(labels)
     if labels.ndim != 3:

@@ -29,14 +29,41 @@ def _create_extract_multich_tree(channels, extract_ncores, cp_measure_feature_kw
     return {"tree": tree, "kwargs": _step_kwargs(extract_ncores, cp_measure_feature_kwargs)}
 
 
-def _object_links(objects, relate, tertiary):
-    """The `relate` and `tertiary` keywords of build_pipeline_steps, checked against the object sets: ({obj: [partners]} in first-seen
-    order, {name: (outer, inner)})."""
+def _secondary_sets(objects, secondary):
+    """The `secondary` keyword of build_pipeline_steps, checked against the segmented object sets: {name: (primary, distance)}."""
+    from aliby_amd.extraction.features import relate_names, secondary_distance
+
+    if secondary is None:
+        return {}
+    if not isinstance(secondary, dict):
+        raise ValueError(f"secondary must be a dict {{name: (primary, distance)}}, got {secondary!r}")
+    checked = {}
+    for name, entry in secondary.items():
+        relate_names(name)  # (a name that a step name or a column name cannot carry)
+        if name in objects:
+            raise ValueError(f"secondary: '{name}' is already a segmented object set")
+        if not isinstance(entry, (tuple, list)) or len(entry) != 2:
+            raise ValueError(f"secondary['{name}'] must be (primary, distance), got {entry!r}")
+        if entry[0] not in objects:
+            raise ValueError(f"secondary['{name}']: the primary {entry[0]!r} is not a segmented object set of {objects}")
+        try:
+            checked[name] = (entry[0], secondary_distance(entry[1]))
+        except ValueError as e:
+            raise ValueError(f"secondary['{name}'] must be (primary, distance): {e}") from None
+    return checked
+
+
+def _object_links(objects, relate, tertiary, secondary=()):
+    """The `relate` and `tertiary` keywords of build_pipeline_steps, checked against the object sets — the segmented ones and the
+    names of `secondary`: ({obj: [partners]} in first-seen order, {name: (outer, inner)})."""
     from aliby_amd.extraction.features import relate_names
 
+    objects = [*objects, *secondary]
     tertiary = dict(tertiary or {})
     for name, pair in tertiary.items():
         relate_names(name)  # (a name that a step name or a column name cannot carry)
+        if name in secondary:
+            raise ValueError(f"tertiary: '{name}' is already a secondary object set")
         if name in objects:
             raise ValueError(f"tertiary: '{name}' is already a segmented object set")
         if not isinstance(pair, (tuple, list)) or len(pair) != 2 or pair[0] == pair[1] or any(o not in objects for o in pair):
@@ -70,6 +97,7 @@ def build_pipeline_steps(
     relate: Sequence[tuple[str, str]] | None = None,
     tertiary: dict[str, tuple[str, str]] | None = None,
     volume_relate: bool = False,
+    secondary: dict[str, tuple[str, int]] | None = None,
 ) -> dict:
     """Extension (not in the reference): `volume_features`, a sequence of per-channel volume family names
     (extraction.families.VOLUME: "intensity3d", "intensity3d_detail", "texture3d", "granularity3d"), makes every segment step
@@ -92,24 +120,44 @@ def build_pipeline_steps(
     (the tertiary volume of the two segment steps' kept volumes), a `volume_<name>` step that measures it with the shared volume tree,
     and a `volumerelate_<obj>` step per related object set (columns None/None/relate3d/Parent_<other>, ...).  Their rows go to
     profiles3d/: nuclei, cell and cytoplasm rows keyed by volume label, the relate3d columns joined onto the rows of their object set.
-    With the default False the dict is what it is without the keyword."""
+    With the default False the dict is what it is without the keyword.
+
+    Extension (not in the reference; CellProfiler's IdentifySecondaryObjects, method "Distance - N", csrc/feat_secondary.hip):
+    `secondary`, {name: (primary, distance)}, adds a `secondary_<name>` step {"distance": N} right after the segment steps and before
+    any tertiary step (the primary's labels grown by N pixels, N an integer in 1..64: {"cell": ("nuclei", 10)}), saved like them, and
+    `extract_<name>` / `extractmulti_<name>` steps with the shared specs: rows with metadata_object = <name> whose metadata_label is
+    the primary object's.  A secondary name may be the outer or inner set of a `tertiary` entry and a member of a `relate` pair:
+    secondary={"cell": ("nuclei", 10)}, tertiary={"cytoplasm": ("cell", "nuclei")} with channels_to_segment={"nuclei": 1} gives
+    nuclei, cell and cytoplasm rows from one network pass.  A name that is already an object set, a primary that is not a segmented
+    object set, a malformed entry, and a secondary name in an entry that `volume_relate=True` would take to the volume labels (there
+    is no volume form) are ValueErrors.  With the default None the dict is what it is without the keyword."""
     if channels_to_segment is None:
         channels_to_segment = {"nuclei": 1, "cell": 0}
     kind = "cellpose" if nahual_addresses is None else "nahual_cellpose"
     if channels_to_extract is None:
         channels_to_extract = list(channels_to_segment.values())
     objects = list(channels_to_segment)
-    related, tertiary = _object_links(objects, relate, tertiary)
+    secondary = _secondary_sets(objects, secondary)
+    related, tertiary = _object_links(objects, relate, tertiary, secondary)
     if not isinstance(volume_relate, bool):
         raise ValueError(f"volume_relate must be a bool, got {volume_relate!r}")
     if volume_relate and (volume_features is None or not (related or tertiary)):
         raise ValueError("volume_relate=True needs volume_features (the volume labels come from 3-D segment steps) and at least one "
                          "of relate / tertiary")
-    producer = {obj: f"segment_{obj}" for obj in objects} | {name: f"tertiary_{name}" for name in tertiary}
+    if volume_relate:
+        reached = [name for name in secondary if name in related or any(name in pair for pair in tertiary.values())]
+        if reached:
+            raise ValueError(f"volume_relate=True: the secondary object sets {reached} have no volume form (a 'secondary_' step grows "
+                             "2-D labels): keep them out of relate / tertiary, or leave volume_relate off")
+    producer = ({obj: f"segment_{obj}" for obj in objects} | {name: f"secondary_{name}" for name in secondary}
+                | {name: f"tertiary_{name}" for name in tertiary})
+    derived = (*secondary, *tertiary)  # object sets without a segment step of their own, in step order
 
     steps = {"tile": {"tile_size": None}}
     for obj, ch in channels_to_segment.items():
         steps[f"segment_{obj}"] = {"segmenter_kwargs": {"kind": kind}, "channel_to_segment": ch}
+    for name, (_, distance) in secondary.items():
+        steps[f"secondary_{name}"] = {"distance": distance}
     for name in tertiary:
         steps[f"tertiary_{name}"] = {"shrink_inner": True}
     if volume_relate:
@@ -125,7 +173,7 @@ def build_pipeline_steps(
     multi = _create_extract_multich_tree(channels_to_extract, extract_ncores, cp_measure_feature_kwargs)
     for prefix, spec in (("extract", mono), ("extractmulti", multi)):
         if len(spec):
-            for obj in (*objects, *tertiary):
+            for obj in (*objects, *derived):
                 steps[f"{prefix}_{obj}"] = spec
     for obj, others in related.items():
         steps[f"extractrelate_{obj}"] = {"others": others, "kwargs": _step_kwargs(extract_ncores, cp_measure_feature_kwargs)}
@@ -134,15 +182,17 @@ def build_pipeline_steps(
         "steps": steps,
         "passed_data": {
             f"extract{m}_{obj}": [("masks", producer[obj]), ("pixels", "tile")]
-            for obj in (*objects, *tertiary)
+            for obj in (*objects, *derived)
             for m in ("", "multi")
         },
         "passed_methods": {f"segment_{obj}": ("tile", "get_fczyx") for obj in objects},
-        "save": [producer[obj] for obj in (*objects, *tertiary)],
+        "save": [producer[obj] for obj in (*objects, *derived)],
         "save_interval": 1,
     }
+    for name, (primary, _) in secondary.items():
+        pipeline["passed_data"][f"secondary_{name}"] = [("masks", f"segment_{primary}", "primary")]
     for name, (outer, inner) in tertiary.items():
-        pipeline["passed_data"][f"tertiary_{name}"] = [("masks", f"segment_{outer}", "outer"), ("masks", f"segment_{inner}", "inner")]
+        pipeline["passed_data"][f"tertiary_{name}"] = [("masks", producer[outer], "outer"), ("masks", producer[inner], "inner")]
     for obj, others in related.items():
         pipeline["passed_data"][f"extractrelate_{obj}"] = [("masks", producer[obj])] + [("masks", producer[o], f"masks_{o}") for o in others]
     if volume_features is not None:

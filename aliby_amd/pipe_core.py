@@ -265,6 +265,33 @@ def _init_tertiary(step_name: str, parameters: dict) -> Callable:
     return tertiary_step
 
 
+def _init_secondary(step_name: str, parameters: dict) -> Callable:
+    """A `secondary_<name>` step: the labels of the `primary` object set grown by `distance` pixels (CellProfiler's
+    IdentifySecondaryObjects, method "Distance - N": the cell around a nucleus; extraction.extract.secondary_masks), in the container
+    the primary segment step returned, so that `extract_<name>` / `extractmulti_<name>` steps measure it like a segment step's labels
+    and a `tertiary_` step may take it as its outer set.  `distance` is required: an integer in 1..64."""
+    from aliby_amd.extraction.extract import secondary_masks
+    from aliby_amd.extraction.features import secondary_distance
+
+    unknown = set(parameters) - {"distance"}
+    if unknown:
+        raise ValueError(f"Step '{step_name}': unknown parameters {sorted(unknown)}.")
+    if "distance" not in parameters:
+        raise ValueError(f"Step '{step_name}' is missing required 'distance'.")
+    try:
+        distance = secondary_distance(parameters["distance"])
+    except ValueError as e:
+        raise ValueError(f"Step '{step_name}': {e}") from None
+
+    def secondary_step(primary=None):
+        if primary is None:
+            raise ValueError(f"Step '{step_name}': no input for ['primary']: 'passed_data' must hand it the masks of a segment step "
+                             "under the alias 'primary'.")
+        return secondary_masks(primary, distance, who=f"Step '{step_name}'")
+
+    return secondary_step
+
+
 def _check_volume_links(steps: dict) -> None:
     """The wiring of the volume steps of two object sets, before any timepoint: a `volumetertiary_` or `volumerelate_` step, and a
     `volume_` step fed by a `volumetertiary_` one, names steps of the pipeline that run before it and keep volume labels."""
@@ -299,6 +326,8 @@ def _check_object_links(steps: dict, passed_data: dict) -> None:
             wanted = ["masks"] + [f"masks_{o}" for o in _relate_others(name, params)]
         elif name.startswith("tertiary_"):
             wanted = ["outer", "inner"]
+        elif name.startswith("secondary_"):
+            wanted = ["primary"]
         else:
             continue
         have = {dep[2] if len(dep) > 2 else dep[0] for dep in passed_data.get(name, ())}

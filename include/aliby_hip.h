@@ -570,6 +570,31 @@ int aliby_features_relate(aliby_ctx* ctx, const uint16_t* labels_a, const uint16
  * algorithmic traffic per pixel; 16-byte accesses where X is a multiple of 8 and the three pointers are 16-byte aligned. */
 int aliby_tertiary_labels(aliby_ctx* ctx, const uint16_t* outer, const uint16_t* inner, int F, int Y, int X, int shrink_inner,
                           uint16_t* out, void* stream);
+/* "secondary": CellProfiler's IdentifySecondaryObjects, method "Distance - N" — every primary object grows by up to N pixels into the
+ * background, and the grown pixels carry its label, so a secondary row joins its primary on the label.  CellProfiler computes it as
+ * scipy.ndimage.distance_transform_edt(labels == 0, return_indices=True) and labels_out[dist <= N] = labels_in[i, j]
+ * (skimage.segmentation.expand_labels).  This is that function, except that where several labelled pixels are equally near SciPy's
+ * index depends on its sweep order and this library takes the smaller label (tests/secondary_ref.py restates the definition;
+ * tests/test_cpu_secondary_ref.py holds it against SciPy on every pixel that is not such a tie).
+ * Every tile f of primary [dev, F x Y x X uint16, 0 = background] is handled on its own.  For a pixel p:
+ *   primary[p] != 0: out[p] = primary[p]
+ *   else let m be the smallest integer |p - q|^2 over the pixels q of the same tile with primary[q] != 0:
+ *     no such q, or m > N^2: out[p] = 0      (sqrt(m) <= N and m <= N^2 are one test for an integer N)
+ *     else: out[p] = min{ primary[q] : |p - q|^2 = m }      (ties go to the smaller label: order-free)
+ * Labels keep the primary numbering and 65535 is a label like any other; nothing crosses a tile edge; everything is integer
+ * arithmetic, so a tile's output carries the same bits whatever the batch, the launch form and the stream.
+ * Worked examples, one row of 9 pixels and one tile of 6 x 6:
+ *   [7 0 0 0 3 0 0 0 0] with N = 2 -> [7 7 3 3 3 3 3 0 0]   (pixel 2 is 2 from either object: m = 4 for both, the smaller label 3)
+ *   a lone pixel of label 9 at (0, 0), N = 5: (3, 4) is 9 (m = 25 <= 25), (4, 4) is 0 (m = 32), (5, 0) is 9, (5, 1) is 0 (m = 26).
+ * distance = N in 1..64, else ALIBY_ERR_INVALID (the cap bounds the per-pixel scan; it is not a structural limit).  workspace [dev,
+ * 4-byte aligned]: the caller's, at least aliby_secondary_workspace_bytes(F, Y, X) = 4 F Y X bytes (one packed word per pixel: the
+ * vertical distance to the column's nearest labelled pixel and its label); a smaller one, and out == primary, are ALIBY_ERR_INVALID.
+ * F * Y * X == 0 is a successful no-op.  Uses no context scratch and does not wait for `stream`.  Two launches; 2 B read, 4 B + 4 B
+ * through the workspace and 2 B written per pixel; per-pixel work linear in N.  Not built: "Propagation", "Watershed",
+ * "Distance - B", a volume form, discarding objects on the border.  Kernels: csrc/feat_secondary.hip. */
+size_t aliby_secondary_workspace_bytes(int F, int Y, int X);
+int aliby_secondary_labels(aliby_ctx* ctx, const uint16_t* primary, int F, int Y, int X, int distance, void* workspace,
+                           size_t workspace_bytes, uint16_t* out, void* stream);
 /* trap.imBackground / trap.background_max5 (src/extraction/core/functions/trap.py:6-43): per tile, over the pixels of
  * `channel` under NO mask (labels == 0): out[f*2] = their median (numpy.median), out[f*2+1] = the mean of the five largest
  * (of all of them when fewer); NaN for a tile without background. */
