@@ -106,6 +106,13 @@ __global__ void k_pad_x(CropArgs a) {
 // ---------------------------------------------------------------------------------------------
 // reduce_z
 // ---------------------------------------------------------------------------------------------
+// np.maximum's step: does v replace the running maximum m?  A NaN replaces anything and, once held, is replaced by nothing
+// (v > NaN and v != v are both false), so it comes through from whichever plane it sits in.
+template <typename T>
+__device__ __forceinline__ bool max_takes(T v, T m) { return v > m; }
+template <>
+__device__ __forceinline__ bool max_takes<float>(float v, float m) { return v > m || v != v; }
+
 template <typename TI, typename TO, int OP>
 __global__ void k_reduce_z(const TI* __restrict__ in, size_t outer, int Z, size_t inner, TO* __restrict__ out) {
   const size_t total = outer * inner;
@@ -114,7 +121,7 @@ __global__ void k_reduce_z(const TI* __restrict__ in, size_t outer, int Z, size_
     const TI* p = in + o * (size_t)Z * inner + k;
     if (OP == ALIBY_RED_MAX) {
       TI m = p[0];
-      for (int z = 1; z < Z; ++z) { TI v = p[(size_t)z * inner]; m = v > m ? v : m; }
+      for (int z = 1; z < Z; ++z) { TI v = p[(size_t)z * inner]; m = max_takes(v, m) ? v : m; }
       out[i] = (TO)m;
     } else if (OP == ALIBY_RED_ADD) {
       // numpy: add.reduce upcasts small unsigned ints (no wrap); float32 stays float32 (left fold)
@@ -161,6 +168,15 @@ int aliby_crop_pad_u16(aliby_ctx* ctx, const uint16_t* stack, int C, int Z, int 
     const int pxb = x0 < 0 ? -x0 : 0, pxa = (x0 + w > X) ? (x0 + w - X) : 0;
     const bool nan = (pyb * 4 > h) || (pya * 4 > w) || (pxb * 4 > h) || (pxa * 4 > w);
     nan_flags_host[f] = nan ? 1 : 0;
+    // That rule lets through a window that misses the frame altogether when it lies wholly left of it with h >= 4w, or wholly
+    // below it with w >= 4h.  The reference has no tile for it (np.pad refuses the empty axis; further left than x0 = -w its
+    // negative slice stop cuts some other columns), and the pad kernels would take the median of an empty line: refuse it
+    // here, before anything is copied or launched.
+    if (!nan && (pyb + pya >= h || pxb + pxa >= w)) {
+      aliby_set_error("invalid argument: window %d (y0=%d, x0=%d, h=%d, w=%d) lies wholly outside the %d x %d frame and is not a "
+                      "NaN tile: nothing to take a median of", f, y0, x0, h, w, Y, X);
+      return ALIBY_ERR_INVALID;
+    }
     if (!nan) { any_y |= (pyb || pya); any_x |= (pxb || pxa); }
   }
   int rc = aliby_ensure_scratch(ctx, sizeof(int) * (size_t)F * 5);

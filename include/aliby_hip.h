@@ -84,7 +84,11 @@ int aliby_stream_sync(aliby_ctx* ctx, void* stream);
  * image coordinates and may leave the image.  out [dev] is [F,C,Z,h,w].
  * Partly outside -> np.pad(mode="median") semantics (per-line medians, rounded
  * for integers); more than 25% outside along an axis -> the tile is NaN and
- * flags[f] = 1 (out_f32 only).  All tiles share (h,w). */
+ * flags[f] = 1 (out_f32 only).  All tiles share (h,w).  A window that misses the
+ * image altogether and still escapes that rule (the reference pairs before-pads with h
+ * and after-pads with w: wholly left with h >= 4w, wholly below with w >= 4h) has no
+ * tile in the reference either (np.pad raises on the empty axis): ALIBY_ERR_INVALID,
+ * nothing launched. */
 int aliby_crop_pad_u16(aliby_ctx* ctx, const uint16_t* stack, int C, int Z, int Y, int X,
                        const int32_t* rects, int F, int h, int w, uint16_t* out,
                        int32_t* nan_flags_host, void* stream);
@@ -96,7 +100,8 @@ int aliby_crop_pad_u16(aliby_ctx* ctx, const uint16_t* stack, int C, int Z, int 
  * uint64 for add.reduce (small unsigned ints are promoted, no wrap) and float64 for
  * divide.reduce: out_dtype ALIBY_U64 / ALIBY_F64 give exactly those; out_dtype
  * ALIBY_F32 gives the same values narrowed to f32, which is what the feature kernels
- * consume (sums exact while < 2^24, i.e. Z <= 256).  f32 input: f32 left fold. */
+ * consume (sums exact while < 2^24, i.e. Z <= 256).  f32 input: f32 left fold; its max
+ * gives NaN wherever a plane holds one, as np.maximum does. */
 int aliby_reduce_z(aliby_ctx* ctx, const void* in, int dtype, size_t outer, int Z, size_t inner,
                    int op, void* out, int out_dtype, void* stream);
 
