@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
 import numpy as np
 import torch
@@ -80,6 +80,12 @@ class ObjectTable:
     max_area: int
     max_h: int
     max_w: int
+    # what the engine computes once per table (mec, _offsets_dev, radial_geometry: key -> code map, rank_planes: key -> entry);
+    # None = nothing yet, which is also what an instance reads after its attribute was removed
+    _mec: torch.Tensor | None = field(default=None, repr=False, compare=False)
+    _offsets_dev: torch.Tensor | None = field(default=None, repr=False, compare=False)
+    _binmaps: dict | None = field(default=None, repr=False, compare=False)
+    _ranks: dict | None = field(default=None, repr=False, compare=False)
 
     @property
     def lds_resident(self) -> bool:
@@ -156,6 +162,17 @@ class FeatureEngine:
         self.profile_sample = {}  # group name -> n: bracket only every n-th launch of that group
         self._sample_count = {}
 
+    # ---------------------------------------------------------------- the launch path
+    def _launch(self, group, entry: str, *args) -> None:
+        """Calls the C entry `entry`(context, *args, stream) of the calling thread's context on torch's current stream and raises
+        what its status code stands for; bracketed as profile group `group` unless that is None."""
+        with _NO_TIMER if group is None else self.timed(group):
+            _lib.check(getattr(self.lib, entry)(self.ctx.handle, *args, _stream_ptr()))
+
+    def call(self, entry: str, *args, group=None) -> None:
+        """`_launch` for the package's other modules (segment/, tile/): they reach the library through an engine, not on their own."""
+        self._launch(group, entry, *args)
+
     # ---------------------------------------------------------------- host transfer
     def to_host(self, t: torch.Tensor, copy: bool = True) -> np.ndarray:
         """Device tensor -> NumPy through a reused pinned staging buffer (pageable copies run at ~12 GB/s,
@@ -172,7 +189,7 @@ class FeatureEngine:
             pool[key] = buf
         view = buf[:need].view(t.shape)
         view.copy_(t.contiguous(), non_blocking=True)
-        _lib.check(self.lib.aliby_stream_sync(self.ctx.handle, _stream_ptr()))  # polls an event: no late wake-up
+        self._launch(None, "aliby_stream_sync")  # polls an event: no late wake-up
         return view.numpy().copy() if copy else view.numpy()
 
     def to_host_async(self, tensors, slot: int = 0, alloc=None):
@@ -238,9 +255,7 @@ class FeatureEngine:
         float32 planes (`in_dtype`), written as `out_dtype` (U16, F32, or NumPy's own U64 / F64; aliby_reduce_z)."""
         *lead, Z, Y, X = t.shape
         out = torch.empty((*lead, Y, X), dtype=self._REDUCED[out_dtype], device=t.device)
-        with self.timed("reduce_z"):
-            _lib.check(self.lib.aliby_reduce_z(self.ctx.handle, _ptr(t), in_dtype, math.prod(lead), Z, Y * X, op, _ptr(out), out_dtype,
-                                               _stream_ptr()))
+        self._launch("reduce_z", "aliby_reduce_z", _ptr(t), in_dtype, math.prod(lead), Z, Y * X, op, _ptr(out), out_dtype)
         return out
 
     # ------------------------------------------------------------------ objects
@@ -248,7 +263,6 @@ class FeatureEngine:
         """max_labels: the largest label of every frame when the caller knows it (the segmenter's object counts: its labels are
         1..n) — saves the pass over the label block that finds it and the host synchronisation behind that pass."""
         F, Y, X = labels.shape
-        lib, h = self.lib, self.ctx.handle
         from aliby_amd import trace
 
         trace.mark("object_table:call")
@@ -258,18 +272,14 @@ class FeatureEngine:
                 raise ValueError(f"max_labels must hold one non-negative count per frame ({F}), got shape {mx.shape}")
         else:
             mx = np.zeros(F, np.int32)
-            with self.timed("object_table"):
-                _lib.check(lib.aliby_label_max(h, _ptr(labels), F, Y, X, _ptr(mx), _stream_ptr()))
+            self._launch("object_table", "aliby_label_max", _ptr(labels), F, Y, X, _ptr(mx))
         offsets = np.zeros(F + 1, np.int32)
         np.cumsum(mx, out=offsets[1:])
         n_obj = int(offsets[-1])
         host = np.zeros(n_obj, _lib.OBJECT_DTYPE)
         dev = torch.empty(max(n_obj, 1) * 32, dtype=torch.uint8, device=labels.device)
         if n_obj:
-            with self.timed("object_table"):
-                _lib.check(
-                    lib.aliby_object_table(h, _ptr(labels), F, Y, X, _ptr(offsets), _ptr(dev), _ptr(host), _stream_ptr())
-                )
+            self._launch("object_table", "aliby_object_table", _ptr(labels), F, Y, X, _ptr(offsets), _ptr(dev), _ptr(host))
         present = host["area"] > 0
         if present.any():
             hh = (host["y1"] - host["y0"])[present]
@@ -288,11 +298,8 @@ class FeatureEngine:
         tracked = torch.zeros(max(cur_table.n_obj, 1), dtype=torch.int32, device=cur.device)
         mx_in = None if max_label is None else np.ascontiguousarray(max_label, dtype=np.int32)
         mx_out = np.zeros(F, np.int32)
-        with self.timed("track_stitch"):
-            _lib.check(self.lib.aliby_track_stitch(
-                self.ctx.handle, _ptr(prev), _ptr(cur), F, Y, X, _ptr(cur_table.dev), _ptr(cur_table.offsets), _ptr(prev_table.dev),
-                _ptr(prev_table.offsets), _ptr(prev_tracked) if prev_tracked is not None else 0, _ptr(mx_in) if mx_in is not None else 0,
-                float(threshold), _ptr(tracked), _ptr(mx_out), _stream_ptr()))
+        self._launch("track_stitch", "aliby_track_stitch", _ptr(prev), _ptr(cur), F, Y, X, _ptr(cur_table.dev), _ptr(cur_table.offsets),
+                     _ptr(prev_table.dev), _ptr(prev_table.offsets), _ptr(prev_tracked), _ptr(mx_in), float(threshold), _ptr(tracked), _ptr(mx_out))
         return tracked[: cur_table.n_obj], mx_out
 
     # ----------------------------------------------------------------- Z-stacks as volumes (round 3 extension, BASELINE config 5)
@@ -324,15 +331,13 @@ class FeatureEngine:
             cur_rows, cur_off, lo, hi = rows(z)
             tracked = lut[lo: max(hi, lo + 1)]
             mx_out = np.zeros(F, np.int32)
-            _lib.check(self.lib.aliby_track_stitch(
-                self.ctx.handle, _ptr(zf[z - 1]), _ptr(zf[z]), F, Y, X, _ptr(cur_rows), _ptr(cur_off), _ptr(prev_rows), _ptr(prev_off),
-                _ptr(lut[prev_lo: max(prev_hi, prev_lo + 1)]), _ptr(np.ascontiguousarray(mx)), float(threshold), _ptr(tracked), _ptr(mx_out),
-                _stream_ptr()))
+            self._launch(None, "aliby_track_stitch", _ptr(zf[z - 1]), _ptr(zf[z]), F, Y, X, _ptr(cur_rows), _ptr(cur_off), _ptr(prev_rows),
+                         _ptr(prev_off), _ptr(lut[prev_lo: max(prev_hi, prev_lo + 1)]), _ptr(np.ascontiguousarray(mx)), float(threshold),
+                         _ptr(tracked), _ptr(mx_out))
             mx = mx_out
             prev_rows, prev_off, prev_lo, prev_hi = cur_rows, cur_off, lo, hi
         out = torch.empty_like(zf)
-        _lib.check(self.lib.aliby_labels_apply_lut(self.ctx.handle, _ptr(zf), Z * F, Y, X, _ptr(np.ascontiguousarray(off)), _ptr(lut), _ptr(out),
-                                                   _stream_ptr()))
+        self._launch(None, "aliby_labels_apply_lut", _ptr(zf), Z * F, Y, X, _ptr(np.ascontiguousarray(off)), _ptr(lut), _ptr(out))
         return out.permute(1, 0, 2, 3).contiguous(), mx
 
     @staticmethod
@@ -390,28 +395,33 @@ class FeatureEngine:
         """dtype code of the pixels of a volume method (uint16 or float32: _volume_inputs)."""
         return _lib.U16 if pixels.dtype == torch.uint16 else _lib.F32
 
+    def _out_window(self, out, col0, rows: int, cols: int, what: str = "out", col0_name: str = "col0"):
+        """-> (matrix, col0) to write a [rows, cols] result into: a new NaN matrix and 0, or the caller's `out` (float64
+        [rows, >= col0 + cols] on the device, rows contiguous) and its col0 once they are checked (`what` names it in the refusal)."""
+        if out is None:
+            return self.new_output(rows, cols), 0
+        col0 = self._integer(col0_name, col0)
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or not out.is_cuda or out.dim() != 2:
+            raise TypeError(f"{what} must be a float64 [rows, columns] tensor on the device")
+        if out.shape[0] != rows or col0 < 0 or col0 + cols > out.shape[1] or (rows and out.stride(1) != 1):
+            raise ValueError(f"{what} must hold {rows} rows and columns {col0}..{col0 + cols - 1} with unit column stride, got "
+                             f"{tuple(out.shape)} with strides {tuple(out.stride())}")
+        return out, col0
+
     def _volume_block(self, rows: int, cols: int, *launches, out=None, col0: int = 0) -> torch.Tensor:
-        """The result of a volume method: a NaN block [rows, cols], handed to call(out, col0) of every (profile group, call) of
-        `launches` in turn.  Stacks without any object: the empty block and no launch (found by tests/fuzz/fuzz_volume.py — the C
-        entries refuse a NULL output).  With `out` (float64 [rows, >= col0 + cols] on the device, rows contiguous) the calls write
-        out[:, col0 : col0 + cols] in place through the C entries' (out, stride, col0), and that view is returned: what
+        """The result of a volume method: a NaN block [rows, cols], written by every (profile group, entry, arguments) of `launches`
+        in turn, where arguments((out, stride, col0)) gives the entry's arguments with that window in its place.  Stacks without any
+        object: the empty block and no launch (found by tests/fuzz/fuzz_volume.py — the C entries refuse a NULL output).  With `out`
+        (`_out_window`) the launches write out[:, col0 : col0 + cols] in place, and that view is returned: what
         extraction.families.evaluate_volume assembles its matrix with, instead of one block per family and a torch.cat.  Allocate
         `out` with `new_output` (NaN-filled): a family may leave the cells of a label without voxels as it found them."""
-        if out is None:
-            out, col0, view = self.new_output(rows, cols), 0, None
-        else:
-            col0 = self._integer("col0", col0)
-            if not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or not out.is_cuda or out.dim() != 2:
-                raise TypeError("out must be a float64 [rows, columns] tensor on the device")
-            if out.shape[0] != rows or col0 < 0 or col0 + cols > out.shape[1] or (rows and out.stride(1) != 1):
-                raise ValueError(f"out must hold {rows} rows and columns {col0}..{col0 + cols - 1} with unit column stride, got "
-                                 f"{tuple(out.shape)} with strides {tuple(out.stride())}")
-            view = out[:, col0: col0 + cols]
+        given = out is not None
+        out, col0 = self._out_window(out, col0, rows, cols)
         if rows:
-            for name, call in launches:
-                with self.timed(name):
-                    _lib.check(call(out, col0))
-        return out if view is None else view
+            for group, entry, arguments in launches:
+                with self.timed(group):  # around the arguments too: a copy to contiguous is part of the family's time
+                    self._launch(None, entry, *arguments((_ptr(out), out.stride(0), col0)))
+        return out[:, col0: col0 + cols] if given else out
 
     def intensity3d(self, volume: torch.Tensor, pixels: torch.Tensor, channel: int, counts, out=None, col0: int = 0) -> torch.Tensor:
         """Volume labels uint16 [F,Z,Y,X] (1..counts[f] per stack), pixels uint16 [F,C,Z,Y,X] -> float64 [sum counts, 12]
@@ -423,9 +433,8 @@ class FeatureEngine:
         if pixels.dtype != torch.uint16:
             raise TypeError(f"intensity3d: pixels must be uint16 (the family has no float form), got {pixels.dtype}")
         channel = self._channel(channel, Cn)
-        return self._volume_block(int(offsets[-1]), 12, ("intensity3d", lambda out, c0: self.lib.aliby_features_intensity3d(
-            self.ctx.handle, _ptr(volume.contiguous()), _ptr(pixels.contiguous()), F, Cn, Z, Y, X, channel, _ptr(offsets), _ptr(out), out.stride(0), c0,
-            _stream_ptr())), out=out, col0=col0)
+        return self._volume_block(int(offsets[-1]), 12, ("intensity3d", "aliby_features_intensity3d", lambda o: (
+            _ptr(volume.contiguous()), _ptr(pixels.contiguous()), F, Cn, Z, Y, X, channel, _ptr(offsets), *o)), out=out, col0=col0)
 
     @property
     def intensity3d_detail_lds_voxels(self) -> int:
@@ -448,9 +457,9 @@ class FeatureEngine:
         F, Cn, Z, Y, X, offsets = self._volume_inputs("intensity3d_detail", volume, pixels, counts)
         names = feat.intensity3d_detail_names(edge_measurements)  # (refuses a flag that is not a bool, before the channel's range)
         channel = self._channel(channel, Cn)
-        return self._volume_block(int(offsets[-1]), len(names), ("intensity3d_detail", lambda out, c0: self.lib.aliby_features_intensity3d_detail(
-            self.ctx.handle, _ptr(volume.contiguous()), _ptr(pixels.contiguous()), self._pixel_code(pixels), F, Cn, Z, Y, X, channel, _ptr(offsets),
-            int(edge_measurements), _ptr(out), out.stride(0), c0, _stream_ptr())), out=out, col0=col0)
+        return self._volume_block(int(offsets[-1]), len(names), ("intensity3d_detail", "aliby_features_intensity3d_detail", lambda o: (
+            _ptr(volume.contiguous()), _ptr(pixels.contiguous()), self._pixel_code(pixels), F, Cn, Z, Y, X, channel, _ptr(offsets),
+            int(edge_measurements), *o)), out=out, col0=col0)
 
     @staticmethod
     def _spacing3d(spacing) -> np.ndarray:
@@ -490,12 +499,10 @@ class FeatureEngine:
         offsets = self._volume_offsets("sizeshape3d", F, counts)
         volume = volume.contiguous()
 
-        def launch(fn, col):
-            return lambda out, c0: fn(self.ctx.handle, _ptr(volume), F, Z, Y, X, _ptr(offsets), _ptr(sp), _ptr(out), out.stride(0), c0 + col, _stream_ptr())
+        def launch(name, col):
+            return name, "aliby_features_" + name, lambda o: (_ptr(volume), F, Z, Y, X, _ptr(offsets), _ptr(sp), o[0], o[1], o[2] + col)
 
-        launches = [("sizeshape3d", launch(self.lib.aliby_features_sizeshape3d, 0))]
-        if surface_area:
-            launches.append(("surface3d", launch(self.lib.aliby_features_surface3d, 19)))
+        launches = [launch("sizeshape3d", 0)] + ([launch("surface3d", 19)] if surface_area else [])
         return self._volume_block(int(offsets[-1]), 20 if surface_area else 19, *launches, out=out, col0=col0)
 
     @property
@@ -520,10 +527,10 @@ class FeatureEngine:
         if not (np.isfinite(thr) and np.isfinite(scale_max) and scale_max > 0):
             raise ValueError(f"thr must be finite and scale_max positive and finite, got {thr!r}, {scale_max!r}")
         col = {m: 2 * k for k, m in enumerate(metrics)}
-        return self._volume_block(int(offsets[-1]), len(names), ("coloc3d", lambda out, c0: self.lib.aliby_features_coloc3d(
-            self.ctx.handle, _ptr(volume.contiguous()), _ptr(pixels.contiguous()), self._pixel_code(pixels), F, Cn, Z, Y, X, _ptr(pr), len(pr),
-            _ptr(offsets), _ptr(out), out.stride(0), c0, 2 * len(metrics), col.get("pearson", -1), col.get("manders_fold", -1), col.get("rwc", -1),
-            col.get("costes", -1), thr, scale_max, _stream_ptr())), out=out, col0=col0)
+        return self._volume_block(int(offsets[-1]), len(names), ("coloc3d", "aliby_features_coloc3d", lambda o: (
+            _ptr(volume.contiguous()), _ptr(pixels.contiguous()), self._pixel_code(pixels), F, Cn, Z, Y, X, _ptr(pr), len(pr), _ptr(offsets), *o,
+            2 * len(metrics), col.get("pearson", -1), col.get("manders_fold", -1), col.get("rwc", -1), col.get("costes", -1), thr, scale_max)),
+            out=out, col0=col0)
 
     @property
     def texture3d_lds_voxels(self) -> int:
@@ -542,9 +549,9 @@ class FeatureEngine:
         if scale < 1 or not 2 <= gray_levels <= 256:
             raise ValueError(f"texture3d needs scale >= 1 and 2 <= gray_levels <= 256, got {scale}, {gray_levels}")
         cols = len(feat.texture3d_names(scale, gray_levels))
-        return self._volume_block(int(offsets[-1]), cols, ("texture3d", lambda out, c0: self.lib.aliby_features_texture3d(
-            self.ctx.handle, _ptr(volume.contiguous()), _ptr(pixels.contiguous()), self._pixel_code(pixels), F, Cn, Z, Y, X, channel, _ptr(offsets),
-            scale, gray_levels, _ptr(out), out.stride(0), c0, _stream_ptr())), out=out, col0=col0)
+        return self._volume_block(int(offsets[-1]), cols, ("texture3d", "aliby_features_texture3d", lambda o: (
+            _ptr(volume.contiguous()), _ptr(pixels.contiguous()), self._pixel_code(pixels), F, Cn, Z, Y, X, channel, _ptr(offsets), scale, gray_levels,
+            *o)), out=out, col0=col0)
 
     def neighbors3d(self, volume: torch.Tensor, counts, distance=None, out=None, col0: int = 0) -> torch.Tensor:
         """Volume labels uint16 [F,Z,Y,X] (1..counts[f] per stack) -> float64 [sum counts, 7] (features.neighbors3d_names(distance);
@@ -560,8 +567,8 @@ class FeatureEngine:
         F, Z, Y, X = self._volume_labels("neighbors3d", volume)
         offsets = self._volume_offsets("neighbors3d", F, counts)
         centres = torch.empty((int(offsets[-1]), 3), dtype=torch.float64, device=volume.device)
-        return self._volume_block(int(offsets[-1]), 7, ("neighbors3d", lambda out, c0: self.lib.aliby_features_neighbors3d(
-            self.ctx.handle, _ptr(volume.contiguous()), F, Z, Y, X, _ptr(offsets), d, _ptr(centres), _ptr(out), out.stride(0), c0, _stream_ptr())), out=out, col0=col0)
+        return self._volume_block(int(offsets[-1]), 7, ("neighbors3d", "aliby_features_neighbors3d", lambda o: (
+            _ptr(volume.contiguous()), F, Z, Y, X, _ptr(offsets), d, _ptr(centres), *o)), out=out, col0=col0)
 
     @staticmethod
     def _granularity3d_shapes(Z: int, Y: int, X: int, subsample_size: float, image_sample_size: float):
@@ -603,15 +610,13 @@ class FeatureEngine:
         rows = int(offsets[-1])
         sweeps = np.zeros(L, np.int32)
 
-        def launch(out, c0):
+        def arguments(o):
             need = int(self.lib.aliby_granularity3d_workspace_bytes(F, Z, Y, X, rows, sizes[0], sizes[1]))
             work = torch.empty((need + 7) // 8, dtype=torch.float64, device=volume.device)
-            return self.lib.aliby_features_granularity3d(
-                self.ctx.handle, _ptr(volume.contiguous()), _ptr(pixels.contiguous()), self._pixel_code(pixels), F, Cn, Z, Y, X, channel,
-                _ptr(offsets), sizes[0], sizes[1], element_size, L, _ptr(work), work.numel() * 8, _ptr(sweeps), _ptr(out), out.stride(0), c0,
-                _stream_ptr())
+            return (_ptr(volume.contiguous()), _ptr(pixels.contiguous()), self._pixel_code(pixels), F, Cn, Z, Y, X, channel, _ptr(offsets),
+                    sizes[0], sizes[1], element_size, L, _ptr(work), work.numel() * 8, _ptr(sweeps), *o)
 
-        block = self._volume_block(rows, len(names), ("granularity3d", launch), out=out, col0=col0)
+        block = self._volume_block(rows, len(names), ("granularity3d", "aliby_features_granularity3d", arguments), out=out, col0=col0)
         self.granularity3d_sweeps = sweeps.tolist()
         return block
 
@@ -628,66 +633,69 @@ class FeatureEngine:
         csrc/object_launch.h).  Integers and one division: bitwise independent of run and batch."""
         F, Z, Y, X = self._volume_labels("projection3d", volume)
         offsets = self._volume_offsets("projection3d", F, counts)
-        return self._volume_block(int(offsets[-1]), 4, ("projection3d", lambda out, c0: self.lib.aliby_features_projection3d(
-            self.ctx.handle, _ptr(volume.contiguous()), F, Z, Y, X, _ptr(offsets), _ptr(out), out.stride(0), c0, _stream_ptr())),
-            out=out, col0=col0)
+        return self._volume_block(int(offsets[-1]), 4, ("projection3d", "aliby_features_projection3d", lambda o: (
+            _ptr(volume.contiguous()), F, Z, Y, X, _ptr(offsets), *o)), out=out, col0=col0)
 
     def relabel_sequential(self, labels: torch.Tensor) -> np.ndarray:
         F, Y, X = labels.shape
         n = np.zeros(F, np.int32)
-        _lib.check(self.lib.aliby_relabel_sequential(self.ctx.handle, _ptr(labels), F, Y, X, _ptr(n), _stream_ptr()))
+        self._launch(None, "aliby_relabel_sequential", _ptr(labels), F, Y, X, _ptr(n))
         return n
 
     # ----------------------------------------------------------------- features
     def new_output(self, n_obj: int, n_cols: int) -> torch.Tensor:
         return torch.full((max(n_obj, 1), max(n_cols, 1)), float("nan"), dtype=torch.float64, device=f"cuda:{self.device}")[:n_obj]
 
+    @staticmethod
+    def _head(labels, planes, dtype, channel, raw_code: bool = False, pixels: bool = True) -> tuple:
+        """(labels, planes, dtype code, F, Cn, Y, X, channel): how the per-channel entries begin.  F, Y, X are the planes' [F,C,Y,X],
+        and the labels' where there are none (planes=None: a null pointer, no channels, channel 0).  raw_code: the code as the
+        caller gave it, U8W included (texture alone tells it from U16: `_kdt`).  pixels=False: the mask-only form, where the
+        planes are there but not looked at (null pointer, code 0, channel 0)."""
+        if planes is None:
+            (F, Y, X), Cn = labels.shape, 0
+        else:
+            F, Cn, Y, X = planes.shape
+        if not pixels:
+            return _ptr(labels), 0, 0, F, Cn, Y, X, 0
+        code = dtype if raw_code or dtype != _lib.U8W else _lib.U16  # (`_kdt`, spelled out: this runs once per launch)
+        return _ptr(labels), _ptr(planes), code, F, Cn, Y, X, 0 if planes is None else int(channel)
+
+    @staticmethod
+    def _row_stride(out, rows: int, col0: int, cols: int) -> int:
+        """The row stride handed to C for columns col0..col0+cols-1 of `out`: a matrix without rows has none of its own."""
+        return out.stride(0) if rows else max(col0 + cols, 1)
+
+    @staticmethod
+    def _relate_out(out, rows: int) -> tuple:
+        """(pointer, row stride) of one side of `relate` / `relate3d`: a side without rows is handed over as (NULL, 5)."""
+        return (_ptr(out), out.stride(0)) if rows else (0, 5)
+
     def intensity(self, labels, planes, dtype, channel, table: ObjectTable, out, col0, edge_measurements=True):
-        F, Cn, Y, X = planes.shape
-        with self.timed("intensity"):
-          _lib.check(
-            self.lib.aliby_features_intensity(
-                self.ctx.handle, _ptr(labels), _ptr(planes), _kdt(dtype), F, Cn, Y, X, int(channel), _ptr(table.dev),
-                table.n_obj, table.max_area, 1 if edge_measurements else 0, _ptr(out), out.stride(0), col0,
-                _stream_ptr(),
-            )
-          )
+        self._launch("intensity", "aliby_features_intensity", *self._head(labels, planes, dtype, channel), _ptr(table.dev), table.n_obj,
+                     table.max_area, 1 if edge_measurements else 0, _ptr(out), out.stride(0), col0)
         return len(feat.intensity_names(edge_measurements))
 
     def sizeshape(self, labels, table: ObjectTable, out, col0):
         F, Y, X = labels.shape
-        with self.timed("sizeshape"):
-          _lib.check(
-            self.lib.aliby_features_sizeshape(
-                self.ctx.handle, _ptr(labels), F, Y, X, _ptr(table.dev), table.n_obj, table.max_h, table.max_w,
-                table.max_area, _ptr(out), out.stride(0), col0, _stream_ptr(),
-            )
-          )
+        self._launch("sizeshape", "aliby_features_sizeshape", _ptr(labels), F, Y, X, _ptr(table.dev), table.n_obj, table.max_h, table.max_w,
+                     table.max_area, _ptr(out), out.stride(0), col0)
         return 78
 
     def feret(self, labels, table: ObjectTable, out, col0):
         F, Y, X = labels.shape
-        with self.timed("feret"):
-          _lib.check(
-            self.lib.aliby_features_feret(
-                self.ctx.handle, _ptr(labels), F, Y, X, _ptr(table.dev), table.n_obj, table.max_h, _ptr(out),
-                out.stride(0), col0, _stream_ptr(),
-            )
-          )
+        self._launch("feret", "aliby_features_feret", _ptr(labels), F, Y, X, _ptr(table.dev), table.n_obj, table.max_h, _ptr(out),
+                     out.stride(0), col0)
         return 2
 
     def mec(self, labels, table: ObjectTable) -> torch.Tensor:
         """Minimum enclosing circles [n_obj,4], computed once per object table."""
-        cached = getattr(table, "_mec", None)
-        if cached is not None:
-            return cached
-        F, Y, X = labels.shape
-        mec = torch.empty((max(table.n_obj, 1), 4), dtype=torch.float64, device=labels.device)
-        with self.timed("mec"):
-            _lib.check(self.lib.aliby_object_mec(self.ctx.handle, _ptr(labels), F, Y, X, _ptr(table.dev), table.n_obj,
-                                                 table.max_h, _ptr(mec), _stream_ptr()))
-        table._mec = mec
-        return mec
+        if table._mec is None:
+            F, Y, X = labels.shape
+            mec = torch.empty((max(table.n_obj, 1), 4), dtype=torch.float64, device=labels.device)
+            self._launch("mec", "aliby_object_mec", _ptr(labels), F, Y, X, _ptr(table.dev), table.n_obj, table.max_h, _ptr(mec))
+            table._mec = mec
+        return table._mec
 
     def neighbors(self, labels, table: ObjectTable, out, col0, distance=None):
         """Columns col0..col0+6 of out [n_obj, .]: the `neighbors` family (features.neighbors_names(distance);
@@ -700,22 +708,33 @@ class FeatureEngine:
         F, Y, X = labels.shape
         if table.n_obj == 0:
             return 7
-        offsets_dev = getattr(table, "_offsets_dev", None)
-        if offsets_dev is None:
-            offsets_dev = table._offsets_dev = torch.from_numpy(np.ascontiguousarray(table.offsets, dtype=np.int32)).to(labels.device)
         centres = torch.empty((table.n_obj, 2), dtype=torch.float64, device=labels.device)
-        with self.timed("neighbors"):
-            _lib.check(self.lib.aliby_features_neighbors(
-                self.ctx.handle, _ptr(labels), F, Y, X, _ptr(table.dev), table.n_obj, table.max_h, table.max_w, _ptr(offsets_dev),
-                int(np.diff(table.offsets).max()), d, _ptr(centres), _ptr(out), out.stride(0), col0, _stream_ptr()))
+        self._launch("neighbors", "aliby_features_neighbors", _ptr(labels), F, Y, X, _ptr(table.dev), table.n_obj, table.max_h, table.max_w,
+                     _ptr(self._offsets_dev(table, labels.device)), int(np.diff(table.offsets).max()), d, _ptr(centres), _ptr(out),
+                     out.stride(0), col0)
         return 7
 
     @staticmethod
     def _offsets_dev(table: ObjectTable, device) -> torch.Tensor:
-        offsets_dev = getattr(table, "_offsets_dev", None)
-        if offsets_dev is None:
-            offsets_dev = table._offsets_dev = torch.from_numpy(np.ascontiguousarray(table.offsets, dtype=np.int32)).to(device)
-        return offsets_dev
+        """The table's row offsets int32 [F + 1] on the device, copied there once per table."""
+        if table._offsets_dev is None:
+            table._offsets_dev = torch.from_numpy(np.ascontiguousarray(table.offsets, dtype=np.int32)).to(device)
+        return table._offsets_dev
+
+    @staticmethod
+    def _label_blocks(who: str, dims: str, blocks: dict, together: str | None = None, typed: bool = True, got: bool = True) -> tuple:
+        """Checks the label blocks {name: tensor} of a relate, tertiary or secondary method -> their shape.  typed: each is a uint16
+        [dims] tensor on the device (`got`: the refusal says what came instead); `together` (how the refusal names them): all have
+        one shape of that rank.  Every refusal is a ValueError (`_volume_labels`, the feature families' check, raises TypeError)."""
+        rank = dims.count(",") + 1
+        for name, v in blocks.items() if typed else ():
+            if not isinstance(v, torch.Tensor) or v.dtype != torch.uint16 or v.dim() != rank or not v.is_cuda:
+                what = f", got {(v.dtype, tuple(v.shape)) if isinstance(v, torch.Tensor) else type(v).__name__}" if got else ""
+                raise ValueError(f"{who}: {name} must be a uint16 [{dims}] tensor on the device{what}")
+        first, *rest = blocks.values()
+        if any(tuple(v.shape) != tuple(first.shape) for v in rest) or first.ndim != rank:
+            raise ValueError(f"{who}: {together} must share one shape [{dims}], got {' and '.join(str(tuple(v.shape)) for v in blocks.values())}")
+        return tuple(int(n) for n in first.shape)
 
     def relate(self, labels_a, table_a: ObjectTable, labels_b, table_b: ObjectTable, out_a=None, col0_a=0, out_b=None, col0_b=0):
         """Two label blocks uint16 [F,Y,X] of one shape with their object tables -> (matrix_a, matrix_b), float64 [n, 5] each: the rows
@@ -725,9 +744,7 @@ class FeatureEngine:
         write columns col0..col0+4 of instead of new ones (the returned matrix is then that window).  Differing F, Y or X is a
         ValueError.  PARITY UNPINNED; the definition and what is not built are in include/aliby_hip.h.  May use the context's scratch
         (tiles of more than 8191 labels)."""
-        if tuple(labels_a.shape) != tuple(labels_b.shape) or labels_a.ndim != 3:
-            raise ValueError(f"relate: the two label blocks must share one shape [F,Y,X], got {tuple(labels_a.shape)} and {tuple(labels_b.shape)}")
-        F, Y, X = labels_a.shape
+        F, Y, X = self._label_blocks("relate", "F,Y,X", {"labels_a": labels_a, "labels_b": labels_b}, "the two label blocks", typed=False)
         if len(table_a.offsets) != F + 1 or len(table_b.offsets) != F + 1:
             raise ValueError(f"relate: the object tables are not those of {F} tiles")
         if out_a is None:
@@ -738,14 +755,11 @@ class FeatureEngine:
             # (a multiple of 8 bytes; float64 elements keep it 8-byte aligned)
             work = torch.empty(int(self.lib.aliby_relate_workspace_bytes(table_a.n_obj, table_b.n_obj)) // 8, dtype=torch.float64,
                                device=labels_a.device)
-            with self.timed("relate"):
-                _lib.check(self.lib.aliby_features_relate(
-                    self.ctx.handle, _ptr(labels_a), _ptr(labels_b), F, Y, X,
-                    _ptr(table_a.dev), table_a.n_obj, table_a.max_h, table_a.max_w, _ptr(table_b.dev), table_b.n_obj, table_b.max_h, table_b.max_w,
-                    _ptr(self._offsets_dev(table_a, labels_a.device)), int(np.diff(table_a.offsets).max()),
-                    _ptr(self._offsets_dev(table_b, labels_b.device)), int(np.diff(table_b.offsets).max()), _ptr(work),
-                    _ptr(out_a) if table_a.n_obj else 0, out_a.stride(0) if table_a.n_obj else 5, col0_a,
-                    _ptr(out_b) if table_b.n_obj else 0, out_b.stride(0) if table_b.n_obj else 5, col0_b, _stream_ptr()))
+            self._launch("relate", "aliby_features_relate", _ptr(labels_a), _ptr(labels_b), F, Y, X,
+                         _ptr(table_a.dev), table_a.n_obj, table_a.max_h, table_a.max_w, _ptr(table_b.dev), table_b.n_obj, table_b.max_h, table_b.max_w,
+                         _ptr(self._offsets_dev(table_a, labels_a.device)), int(np.diff(table_a.offsets).max()),
+                         _ptr(self._offsets_dev(table_b, labels_b.device)), int(np.diff(table_b.offsets).max()), _ptr(work),
+                         *self._relate_out(out_a, table_a.n_obj), col0_a, *self._relate_out(out_b, table_b.n_obj), col0_b)
         return out_a[:, col0_a:col0_a + 5], out_b[:, col0_b:col0_b + 5]
 
     def tertiary_labels(self, outer, inner, shrink_inner: bool = True) -> torch.Tensor:
@@ -753,14 +767,10 @@ class FeatureEngine:
         or, with shrink_inner, on the outline of an inner object; 0 elsewhere — CellProfiler's IdentifyTertiaryObjects (the cytoplasm
         = cell minus nucleus).  Labels keep outer's numbering; one that loses every pixel is absent.  PARITY UNPINNED
         (include/aliby_hip.h)."""
-        if tuple(outer.shape) != tuple(inner.shape) or outer.ndim != 3:
-            raise ValueError(f"tertiary_labels: outer and inner must share one shape [F,Y,X], got {tuple(outer.shape)} and {tuple(inner.shape)}")
-        F, Y, X = outer.shape
+        F, Y, X = self._label_blocks("tertiary_labels", "F,Y,X", {"outer": outer, "inner": inner}, "outer and inner", typed=False)
         out = torch.empty_like(outer)
         if out.numel():
-            with self.timed("tertiary"):
-                _lib.check(self.lib.aliby_tertiary_labels(self.ctx.handle, _ptr(outer), _ptr(inner), F, Y, X, 1 if shrink_inner else 0,
-                                                          _ptr(out), _stream_ptr()))
+            self._launch("tertiary", "aliby_tertiary_labels", _ptr(outer), _ptr(inner), F, Y, X, 1 if shrink_inner else 0, _ptr(out))
         return out
 
     def secondary_labels(self, primary, distance) -> torch.Tensor:
@@ -772,31 +782,14 @@ class FeatureEngine:
         uint16 [F,Y,X] on the device, and a bad distance, are ValueErrors.  Integer arithmetic: the same bits whatever the batch and
         the stream.  Uses no context scratch (its 4-bytes-per-pixel workspace is allocated here)."""
         n = feat.secondary_distance(distance)
-        if not isinstance(primary, torch.Tensor) or primary.dtype != torch.uint16 or primary.dim() != 3 or not primary.is_cuda:
-            raise ValueError(f"secondary_labels: primary must be a uint16 [F,Y,X] tensor on the device, got "
-                             f"{(primary.dtype, tuple(primary.shape)) if isinstance(primary, torch.Tensor) else type(primary).__name__}")
+        F, Y, X = self._label_blocks("secondary_labels", "F,Y,X", {"primary": primary})
         primary = primary.contiguous()
-        F, Y, X = (int(v) for v in primary.shape)
         out = torch.empty_like(primary)
         if out.numel():
             nbytes = int(self.lib.aliby_secondary_workspace_bytes(F, Y, X))
             work = torch.empty(nbytes // 4, dtype=torch.int32, device=primary.device)
-            with self.timed("secondary"):
-                _lib.check(self.lib.aliby_secondary_labels(self.ctx.handle, _ptr(primary), F, Y, X, n, _ptr(work), nbytes, _ptr(out),
-                                                           _stream_ptr()))
+            self._launch("secondary", "aliby_secondary_labels", _ptr(primary), F, Y, X, n, _ptr(work), nbytes, _ptr(out))
         return out
-
-    def _relate3d_out(self, which: str, out, col0, rows: int):
-        """The output window of one side of `relate3d`: a new NaN matrix [rows, 5], or columns col0..col0+4 of `out`."""
-        if out is None:
-            return self.new_output(rows, 5), 0
-        col0 = self._integer(f"col0_{which}", col0)
-        if not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or not out.is_cuda or out.dim() != 2:
-            raise TypeError(f"relate3d: out_{which} must be a float64 [rows, columns] tensor on the device")
-        if out.shape[0] != rows or col0 < 0 or col0 + 5 > out.shape[1] or (rows and out.stride(1) != 1):
-            raise ValueError(f"relate3d: out_{which} must hold {rows} rows and columns {col0}..{col0 + 4} with unit column stride, got "
-                             f"{tuple(out.shape)} with strides {tuple(out.stride())}")
-        return out, col0
 
     def relate3d(self, volume_a, counts_a, volume_b, counts_b, spacing=(1.0, 1.0, 1.0), out_a=None, col0_a=0, out_b=None, col0_b=0):
         """Two sets of volume labels uint16 [F,Z,Y,X] of one shape (1..counts_*[f] per stack) -> (matrix_a, matrix_b), float64
@@ -809,25 +802,16 @@ class FeatureEngine:
         the other side's rows then have no parent and no children.  Volumes that are not uint16 [F,Z,Y,X] of one shape, counts of
         the wrong length and a bad spacing are ValueErrors.  PARITY UNPINNED; the definition is in include/aliby_hip.h.  The object
         tables and the counters live in the context's scratch: a main-stream call.  Bitwise independent of run, batch and launch form."""
-        for name, v in (("volume_a", volume_a), ("volume_b", volume_b)):
-            if not isinstance(v, torch.Tensor) or v.dtype != torch.uint16 or v.dim() != 4 or not v.is_cuda:
-                raise ValueError(f"relate3d: {name} must be a uint16 [F,Z,Y,X] tensor on the device, got "
-                                 f"{(v.dtype, tuple(v.shape)) if isinstance(v, torch.Tensor) else type(v).__name__}")
-        if tuple(volume_a.shape) != tuple(volume_b.shape):
-            raise ValueError(f"relate3d: the two volumes must share one shape [F,Z,Y,X], got {tuple(volume_a.shape)} and {tuple(volume_b.shape)}")
-        F, Z, Y, X = (int(v) for v in volume_a.shape)
+        F, Z, Y, X = self._label_blocks("relate3d", "F,Z,Y,X", {"volume_a": volume_a, "volume_b": volume_b}, "the two volumes")
         sp = self._spacing3d(spacing)
         off_a, off_b = self._volume_offsets("relate3d (counts_a)", F, counts_a), self._volume_offsets("relate3d (counts_b)", F, counts_b)
         n_a, n_b = int(off_a[-1]), int(off_b[-1])
-        out_a, col0_a = self._relate3d_out("a", out_a, col0_a, n_a)
-        out_b, col0_b = self._relate3d_out("b", out_b, col0_b, n_b)
+        out_a, col0_a = self._out_window(out_a, col0_a, n_a, 5, "relate3d: out_a", "col0_a")
+        out_b, col0_b = self._out_window(out_b, col0_b, n_b, 5, "relate3d: out_b", "col0_b")
         if (n_a or n_b) and volume_a.numel():
             va, vb = volume_a.contiguous(), volume_b.contiguous()
-            with self.timed("relate3d"):
-                _lib.check(self.lib.aliby_features_relate3d(
-                    self.ctx.handle, _ptr(va), _ptr(vb), F, Z, Y, X, _ptr(off_a), _ptr(off_b), _ptr(sp),
-                    _ptr(out_a) if n_a else 0, out_a.stride(0) if n_a else 5, col0_a,
-                    _ptr(out_b) if n_b else 0, out_b.stride(0) if n_b else 5, col0_b, _stream_ptr()))
+            self._launch("relate3d", "aliby_features_relate3d", _ptr(va), _ptr(vb), F, Z, Y, X, _ptr(off_a), _ptr(off_b), _ptr(sp),
+                         *self._relate_out(out_a, n_a), col0_a, *self._relate_out(out_b, n_b), col0_b)
         return out_a[:, col0_a:col0_a + 5], out_b[:, col0_b:col0_b + 5]
 
     def tertiary_volume(self, outer, inner, shrink_inner: bool = True) -> torch.Tensor:
@@ -836,33 +820,20 @@ class FeatureEngine:
         (aliby_tertiary_labels on the [F Z, Y, X] view: the outline of a volume is taken plane by plane, so no other kernel is
         needed).  It keeps outer's labels and counts; a label that loses every voxel is absent.  At a nucleus's top and bottom caps
         only the cap's in-plane rim is kept.  PARITY UNPINNED (include/aliby_hip.h)."""
-        for name, v in (("outer", outer), ("inner", inner)):
-            if not isinstance(v, torch.Tensor) or v.dtype != torch.uint16 or v.dim() != 4 or not v.is_cuda:
-                raise ValueError(f"tertiary_volume: {name} must be a uint16 [F,Z,Y,X] tensor on the device")
-        if tuple(outer.shape) != tuple(inner.shape):
-            raise ValueError(f"tertiary_volume: outer and inner must share one shape [F,Z,Y,X], got {tuple(outer.shape)} and {tuple(inner.shape)}")
-        F, Z, Y, X = (int(v) for v in outer.shape)
+        F, Z, Y, X = self._label_blocks("tertiary_volume", "F,Z,Y,X", {"outer": outer, "inner": inner}, "outer and inner", got=False)
         planes = self.tertiary_labels(outer.contiguous().view(F * Z, Y, X), inner.contiguous().view(F * Z, Y, X), shrink_inner=shrink_inner)
         return planes.view(F, Z, Y, X)
 
     def zernike(self, labels, planes, dtype, channel, table: ObjectTable, out, col0, weighted: bool):
-        F, Y, X = labels.shape
-        Cn = planes.shape[1] if planes is not None else 0
         mec = self.mec(labels, table)
-        with self.timed("radial_zernikes" if weighted else "zernike"):
-            _lib.check(
-                self.lib.aliby_features_zernike(
-                    self.ctx.handle, _ptr(labels), _ptr(planes) if weighted else 0, _kdt(dtype) if weighted else 0, F, Cn, Y, X,
-                    int(channel) if weighted else 0, _ptr(table.dev), table.n_obj, _ptr(mec), 1 if weighted else 0,
-                    _ptr(out), out.stride(0), col0, _stream_ptr(),
-                )
-            )
+        self._launch("radial_zernikes" if weighted else "zernike", "aliby_features_zernike",
+                     *self._head(labels, planes, dtype, channel, pixels=weighted), _ptr(table.dev), table.n_obj, _ptr(mec),
+                     1 if weighted else 0, _ptr(out), out.stride(0), col0)
         return 60 if weighted else 30
 
     def radial_zernikes_multi(self, labels, planes, dtype, channels, table: ObjectTable, out, col0s):
         """radial_zernikes of several channels of one plane block: launches of up to five channels share the channel-independent
         basis (aliby_features_radial_zernikes_multi); a channel left alone goes through `zernike(weighted=True)`."""
-        F, Cn, Y, X = planes.shape
         mec = self.mec(labels, table)
         channels, col0s = list(map(int, channels)), list(map(int, col0s))
         k = 0
@@ -875,57 +846,39 @@ class FeatureEngine:
             else:
                 ch = (C.c_int * n)(*channels[k : k + n])
                 c0 = (C.c_int * n)(*col0s[k : k + n])
-                with self.timed("radial_zernikes"):
-                    _lib.check(self.lib.aliby_features_radial_zernikes_multi(
-                        self.ctx.handle, _ptr(labels), _ptr(planes), _kdt(dtype), F, Cn, Y, X, ch, c0, n, _ptr(table.dev), table.n_obj,
-                        _ptr(mec), _ptr(out), out.stride(0), _stream_ptr()))
+                self._launch("radial_zernikes", "aliby_features_radial_zernikes_multi", *self._head(labels, planes, dtype, 0)[:7], ch, c0, n,
+                             _ptr(table.dev), table.n_obj, _ptr(mec), _ptr(out), out.stride(0))
             k += n
         return 60
 
     def texture(self, labels, planes, dtype, channel, table: ObjectTable, out, col0, scale=3, gray_levels=256):
-        F, Cn, Y, X = planes.shape
-        with self.timed("texture"):
-            _lib.check(
-                self.lib.aliby_features_texture(
-                    self.ctx.handle, _ptr(labels), _ptr(planes), dtype, F, Cn, Y, X, int(channel), _ptr(table.dev),
-                    table.n_obj, table.max_h, table.max_w, table.max_area, int(scale), int(gray_levels), _ptr(out),
-                    out.stride(0), col0, _stream_ptr(),
-                )
-            )
+        self._launch("texture", "aliby_features_texture", *self._head(labels, planes, dtype, channel, raw_code=True), _ptr(table.dev),
+                     table.n_obj, table.max_h, table.max_w, table.max_area, int(scale), int(gray_levels), _ptr(out), out.stride(0), col0)
         return 52
 
     def radial_geometry(self, labels, table: ObjectTable, bin_count: int, maximum_radius: float | None = None) -> torch.Tensor:
         """Ring/wedge code map [F,Y,X] uint8, computed once per (object table, bin_count, maximum_radius).
         maximum_radius=None: scaled rings; a number: unscaled rings of maximum_radius / bin_count pixels + overflow ring."""
-        cache = getattr(table, "_binmaps", None)
-        if cache is None:
-            cache = table._binmaps = {}
         key = bin_count if maximum_radius is None else (bin_count, float(maximum_radius))
-        if key in cache:
-            return cache[key]
-        F, Y, X = labels.shape
-        binmap = torch.zeros((F, Y, X), dtype=torch.uint8, device=labels.device)
-        with self.timed("radial_geometry"):
-            _lib.check(self.lib.aliby_radial_geometry_unscaled(
-                self.ctx.handle, _ptr(labels), F, Y, X, _ptr(table.dev), table.n_obj, table.max_h, table.max_w, int(bin_count),
-                0.0 if maximum_radius is None else float(maximum_radius), _ptr(binmap), _stream_ptr()))
-        cache[key] = binmap
-        return binmap
+        if table._binmaps is None:
+            table._binmaps = {}
+        if key not in table._binmaps:
+            F, Y, X = labels.shape
+            binmap = torch.zeros((F, Y, X), dtype=torch.uint8, device=labels.device)
+            self._launch("radial_geometry", "aliby_radial_geometry_unscaled", _ptr(labels), F, Y, X, _ptr(table.dev), table.n_obj, table.max_h,
+                         table.max_w, int(bin_count), 0.0 if maximum_radius is None else float(maximum_radius), _ptr(binmap))
+            table._binmaps[key] = binmap
+        return table._binmaps[key]
 
     def radial_distribution(self, labels, planes, dtype, channel, table: ObjectTable, out, col0, bin_count=4,
                             scaled=True, maximum_radius=100):
         if not scaled and not maximum_radius > 0:
             raise ValueError("radial_distribution(scaled=False) needs maximum_radius > 0")
-        F, Cn, Y, X = planes.shape
         binmap = self.radial_geometry(labels, table, bin_count, None if scaled else maximum_radius)
         rings = bin_count if scaled else bin_count + 1
-        with self.timed("radial_distribution"):
-            _lib.check(
-                self.lib.aliby_features_radial_distribution_rings(
-                    self.ctx.handle, _ptr(labels), _ptr(binmap), _ptr(planes), _kdt(dtype), F, Cn, Y, X, int(channel),
-                    _ptr(table.dev), table.n_obj, int(bin_count), rings, _ptr(out), out.stride(0), col0, _stream_ptr(),
-                )
-            )
+        lab, *rest = self._head(labels, planes, dtype, channel)
+        self._launch("radial_distribution", "aliby_features_radial_distribution_rings", lab, _ptr(binmap), *rest, _ptr(table.dev), table.n_obj,
+                     int(bin_count), rings, _ptr(out), out.stride(0), col0)
         return 3 * rings
 
     def granularity(self, labels, planes, dtype, channel, table: ObjectTable, out, col0, subsample_size=0.25,
@@ -941,14 +894,9 @@ class FeatureEngine:
         L = int(granular_spectrum_length)
         need = int(self.lib.aliby_granularity_workspace_bytes(F, Y, X, table.n_obj, float(subsample_size), float(image_sample_size)))
         work = torch.empty((need + 7) // 8, dtype=torch.float64, device=labels.device)
-        with self.timed("granularity"):
-            _lib.check(
-                self.lib.aliby_features_granularity(
-                    self.ctx.handle, _ptr(labels), _ptr(planes), _kdt(dtype), F, Cn, Y, X, int(channel), _ptr(table.dev), table.n_obj,
-                    float(subsample_size), float(image_sample_size), int(element_size), L, 1 if image_mask == "objects" else 0,
-                    _ptr(work), work.numel() * 8, _ptr(out), out.stride(0) if table.n_obj else max(L + col0, 1), col0, _stream_ptr(),
-                )
-            )
+        self._launch("granularity", "aliby_features_granularity", *self._head(labels, planes, dtype, channel), _ptr(table.dev), table.n_obj,
+                     float(subsample_size), float(image_sample_size), int(element_size), L, 1 if image_mask == "objects" else 0,
+                     _ptr(work), work.numel() * 8, _ptr(out), self._row_stride(out, table.n_obj, col0, L), col0)
         return L
 
     CELL_COLUMNS = ("area", "centroid_x", "centroid_y", "conical_volume", "eccentricity", "spherical_volume", "volume",
@@ -957,17 +905,9 @@ class FeatureEngine:
 
     def cell_metrics(self, labels, planes, dtype, channel, table: ObjectTable) -> torch.Tensor:
         """[n_obj, 17] block of the reference's cell.py metrics (planes may be None: mask-only columns)."""
-        F, Y, X = labels.shape
-        Cn = planes.shape[1] if planes is not None else 0
         out = self.new_output(table.n_obj, 17)
-        with self.timed("cell_metrics"):
-            _lib.check(
-                self.lib.aliby_features_cell(
-                    self.ctx.handle, _ptr(labels), _ptr(planes) if planes is not None else 0, _kdt(dtype), F, Cn, Y, X,
-                    int(channel) if planes is not None else 0, _ptr(table.dev), table.n_obj, table.max_h, table.max_w,
-                    table.max_area, _ptr(out), out.stride(0) if table.n_obj else 17, 0, _stream_ptr(),
-                )
-            )
+        self._launch("cell_metrics", "aliby_features_cell", *self._head(labels, planes, dtype, channel), _ptr(table.dev), table.n_obj,
+                     table.max_h, table.max_w, table.max_area, _ptr(out), self._row_stride(out, table.n_obj, 0, 17), 0)
         return out
 
     def nuc_est_conv(self, labels, planes, dtype, channel, table: ObjectTable, out, col0, alpha=0.95, object_radius_estimation=0.085,
@@ -976,7 +916,6 @@ class FeatureEngine:
         [F,C,Y,X].  alpha / object_radius_estimation None: the defaults, as there; gaussian_sigma None: derived per object.
         `median`: the objects' medians, float64 [n_obj] on the device (column `median` of cell_metrics, which is where they are
         taken from when not given)."""
-        F, Cn, Y, X = planes.shape
         alpha = 0.95 if alpha is None else float(alpha)
         ore = 0.085 if object_radius_estimation is None else float(object_radius_estimation)
         if gaussian_sigma is not None and not (float(gaussian_sigma) > 0.0 and np.isfinite(float(gaussian_sigma))):
@@ -986,15 +925,9 @@ class FeatureEngine:
         median = median.contiguous()
         if median.dtype != torch.float64 or median.numel() < table.n_obj:
             raise ValueError("median must hold one float64 per object")
-        with self.timed("nuc_est_conv"):
-            _lib.check(
-                self.lib.aliby_features_nuc_est_conv(
-                    self.ctx.handle, _ptr(labels), _ptr(planes), _kdt(dtype), F, Cn, Y, X, int(channel), _ptr(table.dev), table.n_obj,
-                    table.max_h, table.max_w, table.max_area, _ptr(median), alpha, ore,
-                    0.0 if gaussian_sigma is None else float(gaussian_sigma), _ptr(out), out.stride(0) if table.n_obj else max(col0 + 1, 1),
-                    col0, _stream_ptr(),
-                )
-            )
+        self._launch("nuc_est_conv", "aliby_features_nuc_est_conv", *self._head(labels, planes, dtype, channel), _ptr(table.dev), table.n_obj,
+                     table.max_h, table.max_w, table.max_area, _ptr(median), alpha, ore, 0.0 if gaussian_sigma is None else float(gaussian_sigma),
+                     _ptr(out), self._row_stride(out, table.n_obj, col0, 1), col0)
         return 1
 
     def nuc_conv_3d(self, labels, stack, dtype, channel, table: ObjectTable, out, col0, pixel_size=0.23, z_spacing=0.6):
@@ -1006,59 +939,52 @@ class FeatureEngine:
         F, Cn, Z, Y, X = stack.shape
         if tuple(labels.shape) != (F, Y, X):
             raise ValueError(f"labels {tuple(labels.shape)} do not match the stack's [F,Y,X] = {(F, Y, X)}")
-        with self.timed("nuc_conv_3d"):
-            _lib.check(
-                self.lib.aliby_features_nuc_conv_3d(
-                    self.ctx.handle, _ptr(labels), _ptr(stack), _kdt(dtype), F, Cn, Z, Y, X, int(channel), _ptr(table.dev), table.n_obj,
-                    table.max_h, table.max_w, table.max_area, float(pixel_size), float(z_spacing), _ptr(out),
-                    out.stride(0) if table.n_obj else max(col0 + 1, 1), col0, _stream_ptr(),
-                )
-            )
+        self._launch("nuc_conv_3d", "aliby_features_nuc_conv_3d", _ptr(labels), _ptr(stack), _kdt(dtype), F, Cn, Z, Y, X, int(channel),
+                     _ptr(table.dev), table.n_obj, table.max_h, table.max_w, table.max_area, float(pixel_size), float(z_spacing), _ptr(out),
+                     self._row_stride(out, table.n_obj, col0, 1), col0)
         return 1
 
     def cell_ratio(self, labels, planes, dtype, ch0, ch1, table: ObjectTable) -> torch.Tensor:
         """[n_obj] float64: cell.ratio of the reference (cell.py:268-279) for the channel pair (ch0, ch1) of planes [F,C,Y,X]."""
-        F, Cn, Y, X = planes.shape
         out = torch.full((max(table.n_obj, 1),), float("nan"), dtype=torch.float64, device=labels.device)
-        with self.timed("cell_metrics"):
-            _lib.check(self.lib.aliby_features_cell_ratio(self.ctx.handle, _ptr(labels), _ptr(planes), _kdt(dtype), F, Cn, Y, X, int(ch0), int(ch1),
-                                                          _ptr(table.dev), table.n_obj, table.max_area, _ptr(out), _stream_ptr()))
+        self._launch("cell_metrics", "aliby_features_cell_ratio", *self._head(labels, planes, dtype, ch0), int(ch1), _ptr(table.dev),
+                     table.n_obj, table.max_area, _ptr(out))
         return out[: table.n_obj]
 
     def trap_background(self, labels, planes, dtype, channel) -> torch.Tensor:
         """[F, 2] float64: (trap.imBackground, trap.background_max5) of every tile (trap.py:6-43): median / mean of the five
         largest of the pixels of `channel` that lie under no mask."""
-        F, Cn, Y, X = planes.shape
-        out = torch.empty((F, 2), dtype=torch.float64, device=labels.device)
-        with self.timed("trap_background"):
-            _lib.check(self.lib.aliby_features_trap_background(self.ctx.handle, _ptr(labels), _ptr(planes), _kdt(dtype), F, Cn, Y, X, int(channel),
-                                                               _ptr(out), _stream_ptr()))
+        out = torch.empty((planes.shape[0], 2), dtype=torch.float64, device=labels.device)
+        self._launch("trap_background", "aliby_features_trap_background", *self._head(labels, planes, dtype, channel), _ptr(out))
         return out
 
     def rank_planes(self, labels, planes, dtype, table: ObjectTable, channels):
         """uint32 [F,C,Y,X] dense ranks + int32 [n_obj,C] maxima for `channels`, cached on the table per plane tensor."""
         F, Cn, Y, X = planes.shape
         key = ("ranks", planes.data_ptr())
-        cache = table.__dict__.setdefault("_ranks", {})
-        if key not in cache:
-            cache[key] = dict(ranks=torch.empty((F, Cn, Y, X), dtype=torch.int32, device=planes.device),
-                              rmax=torch.zeros((max(table.n_obj, 1), Cn), dtype=torch.int32, device=planes.device), done=set())
-        e = cache[key]
+        if table._ranks is None:
+            table._ranks = {}
+        if key not in table._ranks:
+            table._ranks[key] = dict(ranks=torch.empty((F, Cn, Y, X), dtype=torch.int32, device=planes.device),
+                                     rmax=torch.zeros((max(table.n_obj, 1), Cn), dtype=torch.int32, device=planes.device), done=set())
+        e = table._ranks[key]
         for ch in channels:
             if ch in e["done"]:
                 continue
-            with self.timed("ranks"):
-                _lib.check(self.lib.aliby_object_ranks(self.ctx.handle, _ptr(labels), _ptr(planes), _kdt(dtype), F, Cn, Y, X, int(ch),
-                                                       _ptr(table.dev), table.n_obj, table.max_area, _ptr(e["ranks"]),
-                                                       _ptr(e["rmax"]), _stream_ptr()))
+            self._launch("ranks", "aliby_object_ranks", *self._head(labels, planes, dtype, ch), _ptr(table.dev), table.n_obj, table.max_area,
+                         _ptr(e["ranks"]), _ptr(e["rmax"]))
             e["done"].add(ch)
         return e["ranks"], e["rmax"]
+
+    @staticmethod
+    def _coloc_columns(cols: dict) -> tuple:
+        """cols of `coloc` -> the columns of (pearson, manders_fold, rwc, costes) as C takes them: -1 for a metric that is not asked for."""
+        return tuple(-1 if cols.get(k) is None else int(cols[k]) for k in ("pearson", "manders_fold", "rwc", "costes"))
 
     def coloc_pairs(self, labels, planes, dtype, pairs, table: ObjectTable, out, thr=15.0, scale_max=255.0) -> bool:
         """All channel pairs in one launch (aliby_features_coloc_pairs).  pairs = [((ch0, ch1), cols), ...] with cols as in
         `coloc`.  False (nothing launched) when the objects' pixel lists do not fit the kernel's LDS budget or there are more
         pairs / channels than one launch takes: the caller then goes pair by pair."""
-        F, Cn, Y, X = planes.shape
         chans = sorted({c for (pair, _) in pairs for c in pair})
         any_rwc = any(cols.get("rwc") is not None for _, cols in pairs)
         cap = 64
@@ -1069,33 +995,16 @@ class FeatureEngine:
         ranks = rmax = None
         if any_rwc:
             ranks, rmax = self.rank_planes(labels, planes, dtype, table, tuple(chans))
-        c = lambda cols, k: -1 if cols.get(k) is None else int(cols[k])  # noqa: E731
-        spec = np.asarray([[ch0, ch1, c(cols, "pearson"), c(cols, "manders_fold"), c(cols, "rwc"), c(cols, "costes")]
-                           for (ch0, ch1), cols in pairs], dtype=np.int32)
-        with self.timed("coloc"):
-            _lib.check(
-                self.lib.aliby_features_coloc_pairs(
-                    self.ctx.handle, _ptr(labels), _ptr(planes), _kdt(dtype), F, Cn, Y, X, spec.ctypes.data, len(pairs), _ptr(table.dev),
-                    table.n_obj, table.max_area, _ptr(out), out.stride(0), float(thr), float(scale_max),
-                    _ptr(ranks) if ranks is not None else 0, _ptr(rmax) if rmax is not None else 0, _stream_ptr(),
-                )
-            )
+        spec = np.asarray([[ch0, ch1, *self._coloc_columns(cols)] for (ch0, ch1), cols in pairs], dtype=np.int32)
+        self._launch("coloc", "aliby_features_coloc_pairs", *self._head(labels, planes, dtype, 0)[:7], spec.ctypes.data, len(pairs),
+                     _ptr(table.dev), table.n_obj, table.max_area, _ptr(out), out.stride(0), float(thr), float(scale_max), _ptr(ranks), _ptr(rmax))
         return True
 
     def coloc(self, labels, planes, dtype, ch0, ch1, table: ObjectTable, out, cols, thr=15.0, scale_max=255.0):
         """cols = dict(pearson=col|None, manders_fold=..., rwc=..., costes=...)."""
-        F, Cn, Y, X = planes.shape
-        c = lambda k: -1 if cols.get(k) is None else int(cols[k])  # noqa: E731
         ranks = rmax = None
         if cols.get("rwc") is not None:
             ranks, rmax = self.rank_planes(labels, planes, dtype, table, (ch0, ch1))
-        with self.timed("coloc"):
-            _lib.check(
-                self.lib.aliby_features_coloc(
-                    self.ctx.handle, _ptr(labels), _ptr(planes), _kdt(dtype), F, Cn, Y, X, int(ch0), int(ch1),
-                    _ptr(table.dev), table.n_obj, table.max_area, _ptr(out), out.stride(0), c("pearson"),
-                    c("manders_fold"), c("rwc"), c("costes"), float(thr), float(scale_max),
-                    _ptr(ranks) if ranks is not None else 0, _ptr(rmax) if rmax is not None else 0, _stream_ptr(),
-                )
-            )
+        self._launch("coloc", "aliby_features_coloc", *self._head(labels, planes, dtype, ch0), int(ch1), _ptr(table.dev), table.n_obj,
+                     table.max_area, _ptr(out), out.stride(0), *self._coloc_columns(cols), float(thr), float(scale_max), _ptr(ranks), _ptr(rmax))
 

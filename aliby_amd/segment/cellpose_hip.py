@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from aliby_amd import _lib
-from aliby_amd.extraction.engine import FeatureEngine, _ptr, _stream_ptr
+from aliby_amd.extraction.engine import FeatureEngine, _ptr
 from aliby_amd.segment import dynamics
 
 
@@ -168,27 +168,21 @@ class CellposeModel:
             dev = dev.to(torch.float32)
             return (dev[:, int(channel)].amax(dim=1) if Z > 1 else dev[:, int(channel), 0]).contiguous()
         out = torch.empty((F, Y, X), dtype=torch.uint16, device=self.device)
-        with self.eng.timed("select_project"):
-            _lib.check(self.eng.lib.aliby_select_project_u16(self.eng.ctx.handle, _ptr(dev), F, C, Z, Y, X, int(channel),
-                                                             _ptr(out), _stream_ptr()))
+        self.eng.call("aliby_select_project_u16", _ptr(dev), F, C, Z, Y, X, int(channel), _ptr(out), group="select_project")
         return out
 
     def max_project_and_relabel(self, labels: torch.Tensor) -> torch.Tensor:
         """labels [F,Y,X] -> [Y,X]: max over axis 0 then relabel_sequential (dispatch.py:218-223)."""
         F, Y, X = labels.shape
         out = torch.empty((1, Y, X), dtype=torch.uint16, device=labels.device)
-        from aliby_amd import _lib as L
-
-        _lib.check(self.eng.lib.aliby_reduce_z(self.eng.ctx.handle, _ptr(labels.contiguous()), L.U16, 1, F, Y * X, L.RED_MAX,
-                                               _ptr(out), L.U16, _stream_ptr()))
+        self.eng.call("aliby_reduce_z", _ptr(labels.contiguous()), _lib.U16, 1, F, Y * X, _lib.RED_MAX, _ptr(out), _lib.U16)
         self.eng.relabel_sequential(out)
         return out[0]
 
     def count_labels(self, labels: torch.Tensor) -> int:
         mx = np.zeros(1, np.int32)
         lab = labels.reshape(1, -1, labels.shape[-1])
-        _lib.check(self.eng.lib.aliby_label_max(self.eng.ctx.handle, _ptr(lab), 1, lab.shape[1], lab.shape[2], _ptr(mx),
-                                                _stream_ptr()))
+        self.eng.call("aliby_label_max", _ptr(lab), 1, lab.shape[1], lab.shape[2], _ptr(mx))
         return int(mx[0])
 
     # ------------------------------------------------------------------------------ network leg
@@ -214,9 +208,7 @@ class CellposeModel:
             return self._normalize_float(img_u16)
         out = torch.empty((F, Y, X), dtype=torch.float32, device=self.device)
         pct = torch.empty((F, 2), dtype=torch.float64, device=self.device)
-        with self.eng.timed("normalize99"):
-            _lib.check(self.eng.lib.aliby_normalize99_u16(self.eng.ctx.handle, _ptr(img_u16), F, Y, X, 1.0, 99.0, _ptr(out),
-                                                          _ptr(pct), _stream_ptr()))
+        self.eng.call("aliby_normalize99_u16", _ptr(img_u16), F, Y, X, 1.0, 99.0, _ptr(out), _ptr(pct), group="normalize99")
         return out
 
     def _normalize_float(self, img: torch.Tensor) -> torch.Tensor:
@@ -257,23 +249,18 @@ class CellposeModel:
         F, Y, X = img_u16.shape
         g = self._geometry(Y, X, bsize, tile_overlap)
         batch_size = self.batch_size if batch_size is None else max(1, int(batch_size))
-        lib, h = self.eng.lib, self.eng.ctx.handle
         # normalize=False: the raw values go to the network as float32, as cellpose does with its `normalize` switch off
         norm = self.normalize(img_u16) if normalize else (
             img_u16.to(torch.int32).to(torch.float32) if img_u16.dtype == torch.uint16 else img_u16.to(torch.float32)).contiguous()
         ntiles = F * g["ny"] * g["nx"]
         tiles = torch.empty((ntiles, 2, g["by"], g["bx"]), dtype=torch.float32, device=self.device)
-        with self.eng.timed("make_tiles"):
-            _lib.check(lib.aliby_make_tiles(h, _ptr(norm), F, Y, X, g["ypad1"], g["xpad1"], g["Ly"], g["Lx"], g["by"],
-                                            g["bx"], g["ny"], g["nx"], _ptr(g["ys"]), _ptr(g["xs"]), 2, _ptr(tiles),
-                                            _stream_ptr()))
+        self.eng.call("aliby_make_tiles", _ptr(norm), F, Y, X, g["ypad1"], g["xpad1"], g["Ly"], g["Lx"], g["by"], g["bx"], g["ny"], g["nx"],
+                      _ptr(g["ys"]), _ptr(g["xs"]), 2, _ptr(tiles), group="make_tiles")
         yt = self._forward_tiles(tiles, g, batch_size)
         dP = torch.empty((F, 2, Y, X), dtype=torch.float32, device=self.device)
         prob = torch.empty((F, Y, X), dtype=torch.float32, device=self.device)
-        with self.eng.timed("average_tiles"):
-            _lib.check(lib.aliby_average_tiles(h, _ptr(yt), F, Y, X, g["ypad1"], g["xpad1"], g["Ly"], g["Lx"], g["by"],
-                                               g["bx"], g["ny"], g["nx"], _ptr(g["ys"]), _ptr(g["xs"]), _ptr(g["taper"]),
-                                               _ptr(dP), _ptr(prob), _stream_ptr()))
+        self.eng.call("aliby_average_tiles", _ptr(yt), F, Y, X, g["ypad1"], g["xpad1"], g["Ly"], g["Lx"], g["by"], g["bx"], g["ny"], g["nx"],
+                      _ptr(g["ys"]), _ptr(g["xs"]), _ptr(g["taper"]), _ptr(dP), _ptr(prob), group="average_tiles")
         return dP, prob
 
     # cellpose's run_3D: the 2-D network over the YX, ZY and ZX slices of the volume.  Per pass: (slice axis, image rows, image
@@ -288,7 +275,6 @@ class CellposeModel:
         vol = vol.to(torch.float32).contiguous()
         F, Z, Y, X = vol.shape
         batch_size = self.batch_size if batch_size is None else max(1, int(batch_size))
-        lib, h = self.eng.lib, self.eng.ctx.handle
         V = Z * Y * X
         dP = torch.empty((F, 3, Z, Y, X), dtype=torch.float32, device=self.device)
         prob = torch.empty((F, Z, Y, X), dtype=torch.float32, device=self.device)
@@ -298,17 +284,14 @@ class CellposeModel:
             g = self._geometry(rows, cols, bsize, tile_overlap)
             N = F * S
             tiles = torch.empty((N * g["ny"] * g["nx"], 2, g["by"], g["bx"]), dtype=torch.float32, device=self.device)
-            with self.eng.timed("make_tiles"):
-                _lib.check(lib.aliby_make_tiles_strided(h, _ptr(vol), N, S, V, strides[sa], strides[ra], strides[ca], rows, cols,
-                                                        g["ypad1"], g["xpad1"], g["Ly"], g["Lx"], g["by"], g["bx"], g["ny"], g["nx"],
-                                                        _ptr(g["ys"]), _ptr(g["xs"]), 2, _ptr(tiles), _stream_ptr()))
+            self.eng.call("aliby_make_tiles_strided", _ptr(vol), N, S, V, strides[sa], strides[ra], strides[ca], rows, cols, g["ypad1"],
+                          g["xpad1"], g["Ly"], g["Lx"], g["by"], g["bx"], g["ny"], g["nx"], _ptr(g["ys"]), _ptr(g["xs"]), 2, _ptr(tiles),
+                          group="make_tiles")
             yt = self._forward_tiles(tiles, g, batch_size)
             del tiles
-            with self.eng.timed("average_tiles"):
-                _lib.check(lib.aliby_average_tiles_strided(h, _ptr(yt), N, S, 3 * V, V, strides[sa], strides[ra], strides[ca], V, c0,
-                                                           c1, add, rows, cols, g["ypad1"], g["xpad1"], g["Ly"], g["Lx"], g["by"],
-                                                           g["bx"], g["ny"], g["nx"], _ptr(g["ys"]), _ptr(g["xs"]), _ptr(g["taper"]),
-                                                           _ptr(dP), _ptr(prob), _stream_ptr()))
+            self.eng.call("aliby_average_tiles_strided", _ptr(yt), N, S, 3 * V, V, strides[sa], strides[ra], strides[ca], V, c0, c1, add,
+                          rows, cols, g["ypad1"], g["xpad1"], g["Ly"], g["Lx"], g["by"], g["bx"], g["ny"], g["nx"], _ptr(g["ys"]), _ptr(g["xs"]),
+                          _ptr(g["taper"]), _ptr(dP), _ptr(prob), group="average_tiles")
         return dP, prob
 
     def normalize_3d(self, vol: torch.Tensor, norm3D: bool) -> torch.Tensor:

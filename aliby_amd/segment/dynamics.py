@@ -10,8 +10,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from aliby_amd import _lib
-from aliby_amd.extraction.engine import _ptr, _stream_ptr
+from aliby_amd.extraction.engine import _ptr
 
 _workspaces: dict = {}
 
@@ -32,10 +31,10 @@ def _workspace(need, device):
     return ws
 
 
-def _masks(eng, group, fn, workspace_bytes, ndim, dP, cellprob, niter, params, return_endpoints):
+def _masks(eng, group, entry, workspace_bytes, ndim, dP, cellprob, niter, params, return_endpoints):
     """dP float32 [F,ndim,*frame] (one flow component per axis of a frame), cellprob float32 [F,*frame] (device) ->
     (labels uint16 [F,*frame] device, counts[F], end points [F,ndim,*frame] if return_endpoints) through the library's
-    fn(ctx, dP, cellprob, F, *frame, niter, *params, workspace, bytes, labels, counts, end points, stream)."""
+    `entry`(ctx, dP, cellprob, F, *frame, niter, *params, workspace, bytes, labels, counts, end points, stream)."""
     assert dP.dtype == torch.float32 and cellprob.dtype == torch.float32
     dP = dP.contiguous()
     cellprob = cellprob.contiguous()
@@ -46,9 +45,7 @@ def _masks(eng, group, fn, workspace_bytes, ndim, dP, cellprob, niter, params, r
     need = int(workspace_bytes(F, *frame))
     ws = _workspace(need, dP.device)
     pf = torch.zeros_like(dP) if return_endpoints else None
-    with eng.timed(group):
-        _lib.check(fn(eng.ctx.handle, _ptr(dP), _ptr(cellprob), F, *frame, int(niter), *params, _ptr(ws), need, _ptr(labels),
-                      _ptr(n), _ptr(pf) if pf is not None else 0, _stream_ptr()))
+    eng.call(entry, _ptr(dP), _ptr(cellprob), F, *frame, int(niter), *params, _ptr(ws), need, _ptr(labels), _ptr(n), _ptr(pf), group=group)
     if return_endpoints:
         return labels, n[:F], pf
     return labels, n[:F]
@@ -63,7 +60,7 @@ def masks_from_flows(eng, dP, cellprob, niter=200, cellprob_threshold=0.0, flow_
     trace.about_to_block()  # (the call below waits for everything queued so far: ~100 ms for a 64-position batch)
     params = (float(cellprob_threshold), float(flow_threshold if flow_threshold is not None else 0.0), int(min_size),
               float(max_size_fraction))
-    out = _masks(eng, "dynamics", eng.lib.aliby_masks_from_flows, eng.lib.aliby_masks_workspace_bytes, 2, dP, cellprob, niter,
+    out = _masks(eng, "dynamics", "aliby_masks_from_flows", eng.lib.aliby_masks_workspace_bytes, 2, dP, cellprob, niter,
                  params, return_endpoints)
     _mark("dynamics:returned")
     return out
@@ -74,5 +71,5 @@ def masks_from_flows_3d(eng, dP, cellprob, niter=200, cellprob_threshold=0.0, mi
     """dP float32 [F,3,Z,Y,X] (dZ,dY,dX), cellprob float32 [F,Z,Y,X] (device) -> (labels uint16 [F,Z,Y,X] device, counts[F]).
     cellpose's 3-D compute_masks; there is no flow-error QC in 3-D."""
     params = (float(cellprob_threshold), int(min_size), float(max_size_fraction))
-    return _masks(eng, "dynamics3d", eng.lib.aliby_masks_from_flows_3d, eng.lib.aliby_masks3d_workspace_bytes, 3, dP, cellprob,
+    return _masks(eng, "dynamics3d", "aliby_masks_from_flows_3d", eng.lib.aliby_masks3d_workspace_bytes, 3, dP, cellprob,
                   niter, params, return_endpoints)

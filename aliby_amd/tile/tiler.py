@@ -305,8 +305,7 @@ class Tiler(DeviceStacks):
         """(device uint16 [F,C,Z,h,w], nan_flags[F]) — crop + median pad on the GPU."""
         import torch
 
-        from aliby_amd import _lib
-        from aliby_amd.extraction.engine import FeatureEngine, _ptr, _stream_ptr
+        from aliby_amd.extraction.engine import FeatureEngine, _ptr
 
         if self._engine is None:
             self._engine = FeatureEngine()
@@ -330,12 +329,7 @@ class Tiler(DeviceStacks):
                                       "stack goes through as ONE tile: tile_size=None)")
         out = torch.empty((F, C, Z, h, w), dtype=torch.uint16, device=stack.device)
         if F:
-            _lib.check(
-                self._engine.lib.aliby_crop_pad_u16(
-                    self._engine.ctx.handle, _ptr(stack), C, Z, Y, X, _ptr(rects), F, h, w, _ptr(out), _ptr(flags),
-                    _stream_ptr(),
-                )
-            )
+            self._engine.call("aliby_crop_pad_u16", _ptr(stack), C, Z, Y, X, _ptr(rects), F, h, w, _ptr(out), _ptr(flags))
         self._crop_cache = (key, out, flags[:F])
         return out, flags[:F]
 
@@ -423,11 +417,10 @@ class CropTiler(DeviceStacks):
         import torch
 
         from aliby_amd import _lib
-        from aliby_amd.extraction.engine import FeatureEngine, _ptr, _stream_ptr
+        from aliby_amd.extraction.engine import FeatureEngine, _ptr
 
         if self._engine is None:
             self._engine = FeatureEngine()
-        lib, ctx = self._engine.lib, self._engine.ctx.handle
         stack = self._device_stack(tp)
         C, Z, Y, X = stack.shape
         ts, flags = int(self.tile_size), self.flags
@@ -438,16 +431,15 @@ class CropTiler(DeviceStacks):
             dev = torch.empty(shape, dtype=torch.float32 if self.float_source else torch.uint16, device=stack.device)
             stats = torch.empty((C, 4), dtype=torch.float64, device=stack.device) if flags & (_lib.CROP_CLIP | _lib.CROP_STD) else None
             if shape[0]:
-                _lib.check(lib.aliby_crop_tiles_u16(ctx, _ptr(stack), C, Z, Y, X, ts, flags, self.CLIP_PERCENT, _ptr(dev),
-                                                    _lib.F32 if self.float_source else _lib.U16, _ptr(stats), _stream_ptr()))
+                self._engine.call("aliby_crop_tiles_u16", _ptr(stack), C, Z, Y, X, ts, flags, self.CLIP_PERCENT, _ptr(dev),
+                                  _lib.F32 if self.float_source else _lib.U16, _ptr(stats))
             self._tiles = (tp, dev, None, stats)
         if want_f64 and self._tiles[2] is None:
             _, dev, _, stats = self._tiles
             if self.float_source:
                 wide = torch.empty(shape, dtype=torch.float64, device=stack.device)
                 if shape[0]:
-                    _lib.check(lib.aliby_crop_cut_u16(ctx, _ptr(stack), C, Z, Y, X, ts, flags, _ptr(stats), _ptr(wide), _lib.F64,
-                                                      _stream_ptr()))
+                    self._engine.call("aliby_crop_cut_u16", _ptr(stack), C, Z, Y, X, ts, flags, _ptr(stats), _ptr(wide), _lib.F64)
                 host = wide.cpu().numpy()
             else:
                 host = dev.cpu().numpy()

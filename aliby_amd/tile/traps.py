@@ -18,8 +18,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from aliby_amd import _lib
-from aliby_amd.extraction.engine import FeatureEngine, _ptr, _stream_ptr
+from aliby_amd.extraction.engine import FeatureEngine, _ptr
 
 REFERENCE_TILE_SIZE = 117  # imaging_specifications["tile_size"], global_settings.py:18
 
@@ -34,8 +33,7 @@ def _eng():
 
 
 def _call(name, *args):
-    eng = _eng()
-    _lib.check(getattr(eng.lib, name)(eng.ctx.handle, *args, _stream_ptr()))
+    _eng().call(name, *args)
 
 
 def _f64(x):
