@@ -332,8 +332,10 @@ def test_fused_unet_at_other_tile_sizes(engine, n, h, w):
 
 
 def test_dynamics_large_mask_uses_global_scratch(engine):
-    """A mask whose padded bounding box (13k cells x 17 bytes = 224 KB) cannot live in LDS: the heat-diffusion QC and the hole
-    filling take their grid-strided global-scratch variants; labels stay bit-exact against the CPU restatement."""
+    """A mask whose padded bounding box (13k cells x 17 bytes = 224 KB) cannot live in LDS: the heat-diffusion QC takes its
+    grid-strided global-scratch variant; labels stay bit-exact against the CPU restatement.  (The hole fill keeps a byte per
+    cell and stays in LDS up to 131 072 cells: its global-scratch variant, and slabs walked by several masks, are in
+    tests/test_gpu_dynamics_crowded.py.)"""
     import torch
     from aliby_amd.segment.dynamics import masks_from_flows
     from oracle import cellpose_restated as cr
