@@ -791,6 +791,26 @@ class FeatureEngine:
             self._launch("secondary", "aliby_secondary_labels", _ptr(primary), F, Y, X, n, _ptr(work), nbytes, _ptr(out))
         return out
 
+    def secondary_volume(self, primary, distance, spacing=(1, 1, 1)) -> torch.Tensor:
+        """primary uint16 [F,Z,Y,X] on the device -> device uint16 [F,Z,Y,X] (aliby_secondary_volume): `secondary_labels` on volume
+        labels — every object of a stack grows by up to `distance` into the background, a grown voxel taking the label of the nearest
+        labelled voxel of its stack by the exact integer squared distance (sz dz)^2 + (sy dy)^2 + (sx dx)^2, ties to the smaller label
+        (scipy's distance_transform_edt with sampling=spacing and its index gather, except on ties).  `distance`: an integer in 1..255
+        in the units of `spacing` = (sz, sy, sx), three integers in 1..255, with distance // s at most 64 on every axis
+        (features.secondary_volume_args).  Labels keep the primary numbering and the counts: no object can vanish.  With Z == 1 and
+        unit spacing it carries the bits of `secondary_labels`.  A tensor that is not uint16 [F,Z,Y,X] on the device, a bad distance
+        and a bad spacing are ValueErrors.  Integer arithmetic: the same bits whatever the batch and the stream.  Uses no context
+        scratch (its 8-bytes-per-voxel workspace is allocated here)."""
+        n, (sz, sy, sx) = feat.secondary_volume_args(distance, spacing)
+        F, Z, Y, X = self._label_blocks("secondary_volume", "F,Z,Y,X", {"primary": primary})
+        primary = primary.contiguous()
+        out = torch.empty_like(primary)
+        if out.numel():
+            nbytes = int(self.lib.aliby_secondary_volume_workspace_bytes(F, Z, Y, X))
+            work = torch.empty(nbytes // 4, dtype=torch.int32, device=primary.device)
+            self._launch("secondary3d", "aliby_secondary_volume", _ptr(primary), F, Z, Y, X, n, sz, sy, sx, _ptr(work), nbytes, _ptr(out))
+        return out
+
     def relate3d(self, volume_a, counts_a, volume_b, counts_b, spacing=(1.0, 1.0, 1.0), out_a=None, col0_a=0, out_b=None, col0_b=0):
         """Two sets of volume labels uint16 [F,Z,Y,X] of one shape (1..counts_*[f] per stack) -> (matrix_a, matrix_b), float64
         [sum counts, 5] each, rows in (stack, label) order: the rows of A relative to B and of B relative to A

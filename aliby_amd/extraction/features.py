@@ -190,6 +190,35 @@ def secondary_distance(distance) -> int:
     return int(distance)
 
 
+SECONDARY3D_MAX_DISTANCE = 255  # N^2 fits the 16-bit distance field of csrc/feat_secondary3d.hip's packed key
+SECONDARY3D_MAX_REACH = 64  # voxels along one axis: bounds the scans of csrc/feat_secondary3d.hip; not a structural limit
+
+
+def secondary_volume_args(distance, spacing=(1, 1, 1)) -> tuple:
+    """(N, (sz, sy, sx)) of FeatureEngine.secondary_volume and a `volumesecondary_<name>` step, checked.  N: an integer in 1..255 in
+    the units of the lattice, or a float that holds one (as `secondary_distance` takes 5.0).  spacing: three integers in 1..255 — a
+    float spacing is refused, also one that holds integers: with integer steps every distance is an exact integer (13 : 5 : 5 stands
+    for 0.6 um per plane over 0.23 um per pixel).  The reach N // s must be at most 64 voxels on every axis.  A bool, a str, None and
+    anything else are ValueErrors.  Needs no device."""
+    ok = not isinstance(distance, bool) and (isinstance(distance, numbers.Integral)
+                                             or (isinstance(distance, numbers.Real) and float(distance).is_integer()))
+    if not ok or not 1 <= int(distance) <= SECONDARY3D_MAX_DISTANCE:
+        raise ValueError(f"secondary_volume: distance must be an integer in 1..{SECONDARY3D_MAX_DISTANCE}, got {distance!r}")
+    n = int(distance)
+    try:
+        steps = None if isinstance(spacing, (str, bytes)) else tuple(spacing)
+    except TypeError:
+        steps = None
+    if steps is None or len(steps) != 3 or any(isinstance(s, bool) or not isinstance(s, numbers.Integral) or not 1 <= int(s) <= 255
+                                               for s in steps):
+        raise ValueError(f"secondary_volume: spacing must be three integers (sz, sy, sx) in 1..255 (no float spacing), got {spacing!r}")
+    steps = tuple(int(s) for s in steps)
+    if any(n // s > SECONDARY3D_MAX_REACH for s in steps):
+        raise ValueError(f"secondary_volume: distance {n} over spacing {steps} reaches more than {SECONDARY3D_MAX_REACH} voxels along "
+                         "an axis")
+    return n, steps
+
+
 def relate_names(other: str) -> list[str]:
     """Columns of `FeatureEngine.relate` for rows related to the object set `other` (csrc/feat_relate.hip): CellProfiler's
     RelateObjects — the parent in `other`, the overlap that chose it, the number of children in `other`, the distance between the

@@ -154,6 +154,16 @@ def tertiary_objects_3d(outer, inner, shrink_inner=True) -> np.ndarray:
     return FeatureEngine().tertiary_volume(a, b, shrink_inner=shrink_inner)[0].cpu().numpy()
 
 
+def secondary_objects_3d(volume_labels, distance, spacing=(1, 1, 1)) -> np.ndarray:
+    """One label stack [Z, Y, X] -> uint16 [Z, Y, X]: every object grown by up to `distance` into the background on the integer
+    lattice `spacing` = (sz, sy, sx), a grown voxel taking the label of the nearest labelled voxel, ties to the smaller label
+    (FeatureEngine.secondary_volume, csrc/feat_secondary3d.hip; the limits: features.secondary_volume_args).  The cell around a
+    nucleus of a stack is secondary_objects_3d(nuclei, 10), and its cytoplasm tertiary_objects_3d(that, nuclei).  Not in the
+    reference: the volume form of `secondary_objects`, equal to scipy's distance_transform_edt(sampling=) index gather except on ties
+    (include/aliby_hip.h)."""
+    return FeatureEngine().secondary_volume(_label_stack("volume_labels", volume_labels)[0], distance, spacing)[0].cpu().numpy()
+
+
 def _background(cell_masks, trap_image):
     trap_image = _as_pixels(trap_image)
     if not len(cell_masks):

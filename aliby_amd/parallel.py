@@ -92,7 +92,7 @@ def refuse_volume_pipelines(pipelines) -> None:
 
 def refuse_object_link_pipelines(pipelines) -> None:
     """The batched runner knows no step that reads two object sets together (`tertiary_`, `extractrelate_`, and their volume forms
-    `volumetertiary_`, `volumerelate_`) or derives one from another (`secondary_`): a pipeline with one is refused up front, before any
+    `volumetertiary_`, `volumerelate_`) or derives one from another (`secondary_`, `volumesecondary_`): a pipeline with one is refused up front, before any
     position is read."""
     for pipeline in pipelines:
         for name in (pipeline.get("steps", {}) if isinstance(pipeline, dict) else {}):
@@ -105,6 +105,9 @@ def refuse_object_link_pipelines(pipelines) -> None:
             if name.startswith(("volumetertiary_", "volumerelate_")):
                 raise NotImplementedError(f"run_positions has no batched form of step '{name}' (a 'volumetertiary_' or 'volumerelate_' "
                                           "step): run such a pipeline position by position with aliby_amd.pipe.run_pipeline_and_post")
+            if name.startswith("volumesecondary_"):
+                raise NotImplementedError(f"run_positions has no batched form of step '{name}' (a 'volumesecondary_' step): "
+                                          "run such a pipeline position by position with aliby_amd.pipe.run_pipeline_and_post")
 
 
 def run_positions(pipelines, names, output_path, **kwargs):

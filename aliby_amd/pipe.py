@@ -51,6 +51,9 @@ _PREFIXES = (
     # starts with "extract" or "volume_": the table code tells the steps apart by those.)
     ("volumetertiary_", lambda name, params, done: core._VolumeTertiary(name, params, done)),
     ("volumerelate_", lambda name, params, done: core._init_volume_relate(name, params, done)),
+    # one volume object set grown into another (csrc/feat_secondary3d.hip), from the volume labels the step it names kept: the cell
+    # around a nucleus of a stack, which volume_, volumetertiary_ and volumerelate_ steps read like a segment step's volume
+    ("volumesecondary_", lambda name, params, done: core._VolumeSecondary(name, params, done)),
     ("nahual_embed", lambda name, params, done: core._init_nahual(name, params)),
     ("nahual_track", lambda name, params, done: core._init_nahual(name, params)),
 )

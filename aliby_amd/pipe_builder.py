@@ -53,6 +53,34 @@ def _secondary_sets(objects, secondary):
     return checked
 
 
+def _volume_secondary_sets(secondary, volume_secondary, volume_features):
+    """The `volume_secondary` keyword of build_pipeline_steps against the checked `secondary` sets: {name: (distance, (sz, sy, sx))}
+    in the units of the integer lattice, {} for False.  True: unit spacing and the entry's N.  (p, q), two integers: a plane step is
+    p/q pixels, so the lattice is (p, q, q) and the distance q N."""
+    from aliby_amd.extraction.features import secondary_volume_args
+
+    if volume_secondary is False:
+        return {}
+    if volume_secondary is True:
+        p, q = 1, 1
+    elif (isinstance(volume_secondary, (tuple, list)) and len(volume_secondary) == 2
+          and all(isinstance(v, int) and not isinstance(v, bool) and v >= 1 for v in volume_secondary)):
+        p, q = volume_secondary
+    else:
+        raise ValueError("volume_secondary must be False, True (unit spacing) or a pair of positive integers (p, q), a plane step of "
+                         f"p/q pixels, got {volume_secondary!r}")
+    if volume_features is None or not secondary:
+        raise ValueError("volume_secondary needs volume_features (the volume labels come from 3-D segment steps) and at least one "
+                         "secondary entry")
+    grown = {}
+    for name, (_, distance) in secondary.items():
+        try:
+            grown[name] = secondary_volume_args(q * distance, (p, q, q))
+        except ValueError as e:
+            raise ValueError(f"volume_secondary={volume_secondary!r}, secondary['{name}']: {e}") from None
+    return grown
+
+
 def _object_links(objects, relate, tertiary, secondary=()):
     """The `relate` and `tertiary` keywords of build_pipeline_steps, checked against the object sets — the segmented ones and the
     names of `secondary`: ({obj: [partners]} in first-seen order, {name: (outer, inner)})."""
@@ -98,6 +126,7 @@ def build_pipeline_steps(
     tertiary: dict[str, tuple[str, str]] | None = None,
     volume_relate: bool = False,
     secondary: dict[str, tuple[str, int]] | None = None,
+    volume_secondary: bool | tuple[int, int] = False,
 ) -> dict:
     """Extension (not in the reference): `volume_features`, a sequence of per-channel volume family names
     (extraction.families.VOLUME: "intensity3d", "intensity3d_detail", "texture3d", "granularity3d"), makes every segment step
@@ -129,8 +158,21 @@ def build_pipeline_steps(
     the primary object's.  A secondary name may be the outer or inner set of a `tertiary` entry and a member of a `relate` pair:
     secondary={"cell": ("nuclei", 10)}, tertiary={"cytoplasm": ("cell", "nuclei")} with channels_to_segment={"nuclei": 1} gives
     nuclei, cell and cytoplasm rows from one network pass.  A name that is already an object set, a primary that is not a segmented
-    object set, a malformed entry, and a secondary name in an entry that `volume_relate=True` would take to the volume labels (there
-    is no volume form) are ValueErrors.  With the default None the dict is what it is without the keyword."""
+    object set, a malformed entry, and — without `volume_secondary` — a secondary name in an entry that `volume_relate=True` would
+    take to the volume labels (a `secondary_` step grows the collapsed 2-D labels) are ValueErrors.  With the default None the dict is
+    what it is without the keyword.
+
+    `volume_secondary` (with `volume_features` and at least one `secondary` entry, else a ValueError) takes the secondary sets to the
+    volume labels (csrc/feat_secondary3d.hip): a `volumesecondary_<name>` step {"primary": "segment_<primary>", "distance", "spacing"}
+    per secondary entry, after the tertiary steps and before any `volumetertiary_` step (the primary's kept volume grown on an integer
+    lattice), and a `volume_<name>` step that measures it with the shared volume tree.  True: spacing (1, 1, 1) and the entry's N.  A
+    pair of integers (p, q): a plane step is p/q pixels, so the spacing is (p, q, q) and the distance q N — N stays in pixels; (13, 5)
+    stands for 0.6 um per plane over 0.23 um per pixel.  q N above 255 and a reach above 64 voxels along an axis are ValueErrors
+    (features.secondary_volume_args), and so is any other value.  Under `volume_relate=True` the secondary names may then stand in
+    `relate` / `tertiary`, their volumes coming from the `volumesecondary_` steps: secondary={"cell": ("nuclei", 10)},
+    tertiary={"cytoplasm": ("cell", "nuclei")}, volume_features=(...), volume_relate=True, volume_secondary=True with only nuclei
+    segmented puts nuclei, cell and cytoplasm rows into profiles3d/, joined on the volume label.  With the default False the dict and
+    every refusal are what they are without the keyword."""
     if channels_to_segment is None:
         channels_to_segment = {"nuclei": 1, "cell": 0}
     kind = "cellpose" if nahual_addresses is None else "nahual_cellpose"
@@ -144,7 +186,8 @@ def build_pipeline_steps(
     if volume_relate and (volume_features is None or not (related or tertiary)):
         raise ValueError("volume_relate=True needs volume_features (the volume labels come from 3-D segment steps) and at least one "
                          "of relate / tertiary")
-    if volume_relate:
+    grown = _volume_secondary_sets(secondary, volume_secondary, volume_features)
+    if volume_relate and not grown:
         reached = [name for name in secondary if name in related or any(name in pair for pair in tertiary.values())]
         if reached:
             raise ValueError(f"volume_relate=True: the secondary object sets {reached} have no volume form (a 'secondary_' step grows "
@@ -160,9 +203,14 @@ def build_pipeline_steps(
         steps[f"secondary_{name}"] = {"distance": distance}
     for name in tertiary:
         steps[f"tertiary_{name}"] = {"shrink_inner": True}
+    # the steps that keep the volume labels of an object set (a tertiary name: only under volume_relate)
+    volume_producer = ({obj: f"segment_{obj}" for obj in objects} | {name: f"volumesecondary_{name}" for name in grown}
+                       | {name: f"volumetertiary_{name}" for name in tertiary})
+    for name, (distance, spacing) in grown.items():
+        steps[f"volumesecondary_{name}"] = {"primary": f"segment_{secondary[name][0]}", "distance": distance, "spacing": spacing}
     if volume_relate:
         for name, (outer, inner) in tertiary.items():
-            steps[f"volumetertiary_{name}"] = {"outer": f"segment_{outer}", "inner": f"segment_{inner}", "shrink_inner": True}
+            steps[f"volumetertiary_{name}"] = {"outer": volume_producer[outer], "inner": volume_producer[inner], "shrink_inner": True}
 
     # the single-channel spec is shared by every object set (as in the reference, where both
     # extract_<obj> entries point at the same dict)
@@ -207,14 +255,13 @@ def build_pipeline_steps(
             steps[f"volume_{obj}"] = {"tree": tree, "volume_from": f"segment_{obj}",
                                       "kwargs": _step_kwargs(extract_ncores, cp_measure_feature_kwargs)}
             pipeline["passed_data"][f"volume_{obj}"] = [("pixels", "tile")]
+        # (the volumesecondary, volumetertiary and volumerelate steps read the kept volumes through the initialised steps, as a
+        # volume step does: they have no passed_data entry)
+        for name in (*grown, *(tertiary if volume_relate else ())):
+            steps[f"volume_{name}"] = {"tree": tree, "volume_from": volume_producer[name],
+                                       "kwargs": _step_kwargs(extract_ncores, cp_measure_feature_kwargs)}
+            pipeline["passed_data"][f"volume_{name}"] = [("pixels", "tile")]
         if volume_relate:
-            # (the volumetertiary and volumerelate steps read the kept volumes through the initialised steps, as a volume step
-            # does: they have no passed_data entry)
-            volume_producer = {obj: f"segment_{obj}" for obj in objects} | {name: f"volumetertiary_{name}" for name in tertiary}
-            for name in tertiary:
-                steps[f"volume_{name}"] = {"tree": tree, "volume_from": f"volumetertiary_{name}",
-                                           "kwargs": _step_kwargs(extract_ncores, cp_measure_feature_kwargs)}
-                pipeline["passed_data"][f"volume_{name}"] = [("pixels", "tile")]
             for obj, others in related.items():
                 steps[f"volumerelate_{obj}"] = {"volume_from": volume_producer[obj], "others": {o: volume_producer[o] for o in others},
                                                 "spacing": (1.0, 1.0, 1.0)}

@@ -84,7 +84,7 @@ def _init_extract_multi(step_name: str, parameters: dict) -> Callable:
     return partial(process_tree_masks, measure_fn=extract_tree_multi, tree=tree, **parameters.get("kwargs", {}))
 
 
-_VOLUME_SOURCES = ("segment", "volumetertiary_")  # the steps that keep volume labels in `last_volume`
+_VOLUME_SOURCES = ("segment", "volumetertiary_", "volumesecondary_")  # the steps that keep volume labels in `last_volume`
 
 
 def _kept_volume(step_name: str, key: str, source: str, other_steps: dict):
@@ -161,6 +161,39 @@ class _VolumeTertiary:
             raise ValueError(f"Step '{self.step_name}': the volume labels of '{self.outer}' are {tuple(outer.shape)} [F,Z,Y,X], those of "
                              f"'{self.inner}' {tuple(inner.shape)}: they do not match.")
         volume = FeatureEngine().tertiary_volume(outer, inner, shrink_inner=self.shrink)
+        self.last_volume = (volume, counts)
+        host = volume.cpu().numpy()
+        return host[0] if host.shape[0] == 1 else [host[f] for f in range(host.shape[0])]
+
+
+class _VolumeSecondary:
+    """A `volumesecondary_<name>` step: the kept volume labels of the `primary` step grown by `distance` on the integer lattice
+    `spacing` = (sz, sy, sx), default (1, 1, 1) (FeatureEngine.secondary_volume: CellProfiler's IdentifySecondaryObjects, method
+    "Distance - N", on a stack; the cell around a nucleus).  It keeps `last_volume` = (the grown volume on the device, the primary's
+    counts) — the numbering is kept and no object can vanish — for the `volume_<name>`, `volumetertiary_` and `volumerelate_` steps
+    after it, and returns the labels on the host in `_VolumeTertiary`'s container: listed under `save` they are written like a
+    segment step's masks."""
+
+    def __init__(self, step_name: str, parameters: dict, other_steps: dict):
+        from aliby_amd.extraction.features import secondary_volume_args
+
+        unknown = set(parameters) - {"primary", "distance", "spacing"}
+        if unknown:
+            raise ValueError(f"Step '{step_name}': unknown parameters {sorted(unknown)}.")
+        self.step_name, self.other_steps = step_name, other_steps
+        self.primary = _volume_source(step_name, parameters, "primary")
+        try:
+            self.distance, self.spacing = secondary_volume_args(_need(parameters, "distance", step_name), parameters.get("spacing", (1, 1, 1)))
+        except ValueError as e:
+            raise ValueError(str(e) if str(e).startswith("Step ") else f"Step '{step_name}': {e}") from None
+        self.last_volume = None
+
+    def __call__(self):
+        from aliby_amd.extraction.engine import FeatureEngine
+
+        self.last_volume = None
+        primary, counts = _kept_volume(self.step_name, "primary", self.primary, self.other_steps)
+        volume = FeatureEngine().secondary_volume(primary, self.distance, self.spacing)
         self.last_volume = (volume, counts)
         host = volume.cpu().numpy()
         return host[0] if host.shape[0] == 1 else [host[f] for f in range(host.shape[0])]
@@ -293,18 +326,22 @@ def _init_secondary(step_name: str, parameters: dict) -> Callable:
 
 
 def _check_volume_links(steps: dict) -> None:
-    """The wiring of the volume steps of two object sets, before any timepoint: a `volumetertiary_` or `volumerelate_` step, and a
-    `volume_` step fed by a `volumetertiary_` one, names steps of the pipeline that run before it and keep volume labels."""
+    """The wiring of the volume steps that read another step's kept volume, before any timepoint: a `volumetertiary_`,
+    `volumesecondary_` or `volumerelate_` step, and a `volume_` step fed by a `volumetertiary_` or `volumesecondary_` one, names steps
+    of the pipeline that run before it and keep volume labels."""
     order = {name: k for k, name in enumerate(steps)}
     for name, params in steps.items():
         if not isinstance(params, dict):
             continue
         if name.startswith("volumetertiary_"):
             wanted = {"outer": params.get("outer"), "inner": params.get("inner")}
+        elif name.startswith("volumesecondary_"):
+            wanted = {"primary": params.get("primary")}
         elif name.startswith("volumerelate_"):
             wanted = {"volume_from": params.get("volume_from")}
             wanted.update({f"others[{o!r}]": src for o, src in _volume_relate_others(name, params).items()})
-        elif name.startswith("volume_") and isinstance(params.get("volume_from"), str) and params["volume_from"].startswith("volumetertiary_"):
+        elif name.startswith("volume_") and isinstance(params.get("volume_from"), str) and params["volume_from"].startswith(
+                ("volumetertiary_", "volumesecondary_")):
             wanted = {"volume_from": params["volume_from"]}
         else:
             continue

@@ -596,10 +596,44 @@ int aliby_tertiary_labels(aliby_ctx* ctx, const uint16_t* outer, const uint16_t*
  * vertical distance to the column's nearest labelled pixel and its label); a smaller one, and out == primary, are ALIBY_ERR_INVALID.
  * F * Y * X == 0 is a successful no-op.  Uses no context scratch and does not wait for `stream`.  Two launches; 2 B read, 4 B + 4 B
  * through the workspace and 2 B written per pixel; per-pixel work linear in N.  Not built: "Propagation", "Watershed",
- * "Distance - B", a volume form, discarding objects on the border.  Kernels: csrc/feat_secondary.hip. */
+ * "Distance - B", discarding objects on the border.  (Volume labels: aliby_secondary_volume.)  Kernels: csrc/feat_secondary.hip. */
 size_t aliby_secondary_workspace_bytes(int F, int Y, int X);
 int aliby_secondary_labels(aliby_ctx* ctx, const uint16_t* primary, int F, int Y, int X, int distance, void* workspace,
                            size_t workspace_bytes, uint16_t* out, void* stream);
+/* "secondary" on volume labels: the same function one dimension up, on an integer lattice.  It is
+ * scipy.ndimage.distance_transform_edt(vol == 0, sampling=(sz, sy, sx), return_indices=True) and out[dist <= N] = vol[idx]
+ * (skimage.segmentation.expand_labels(..., spacing=)), with the same tie rule as above: the smaller label (tests/secondary3d_ref.py
+ * restates the definition; tests/test_cpu_secondary3d_ref.py holds it against SciPy on every voxel that is not a tie).
+ * Every stack f of primary [dev, F x Z x Y x X uint16, 0 = background] is handled on its own.  With the integer spacing (sz, sy, sx)
+ * and d2(p, q) = (sz dz)^2 + (sy dy)^2 + (sx dx)^2, an integer, for a voxel p:
+ *   primary[p] != 0: out[p] = primary[p]
+ *   else let m be the smallest d2(p, q) over the voxels q of the same stack with primary[q] != 0:
+ *     no such q, or m > N^2: out[p] = 0
+ *     else: out[p] = min{ primary[q] : d2(p, q) = m }
+ * Labels keep the primary numbering, so no object can vanish and a grown row joins its primary on the label; 65535 is a label like any
+ * other; nothing crosses a stack edge; everything is integer arithmetic, so a stack's output carries the same bits whatever the batch,
+ * the launch form and the stream.  With Z == 1, spacing (1, 1, 1) and N <= 64 it is aliby_secondary_labels on the one plane, bit for
+ * bit.  Worked examples ((z, y, x) coordinates):
+ *   labels 9 at (1, 2, 2) and 4 at (3, 0, 0), unit spacing, N = 3: (0, 0, 0) is 4 (m = 9 for both: 1 + 4 + 4 = 9 + 0 + 0, the smaller
+ *     label); with N = 2 it is 0.
+ *   spacing (3, 1, 1), N = 3, labels 7 at (0, 5, 5) and 2 at (1, 5, 8): (1, 5, 5) is 2 (one plane = 3 = three pixels); (0, 5, 8) is 2
+ *     (the same tie seen from the other side); (1, 5, 4) is 0 (9 + 1 = 10 > 9 through the plane, 16 > 9 along the row: neither
+ *     reaches); (0, 5, 2) is 7 (m = 9), (2, 5, 8) is 2 (m = 9), (3, 5, 8) is 0 (m = 36).
+ *   spacing (13, 5, 5), N = 25: a voxel grows 5 pixels in its plane (m = 625) and one plane up or down (m = 169), and from the
+ *     neighbouring plane 4 pixels (169 + 400 = 569) but not 5 (169 + 625 = 794 > 625).
+ * distance = N in 1..255 and every spacing component in 1..255 (N^2 <= 65025 fits the 16-bit field of the packed key
+ * (d2 << 16) | label below the 0xffffffff sentinel), and the reach N / s_a at most 64 voxels on every axis (it bounds the scans; not a
+ * structural limit); else ALIBY_ERR_INVALID.  A float spacing is not offered: real stacks are anisotropic in small ratios (0.6 um per
+ * plane over 0.23 um per pixel is about 13 : 5 : 5), and with integer steps every distance is an exact integer.  workspace [dev,
+ * 4-byte aligned]: the caller's, at least aliby_secondary_volume_workspace_bytes(F, Z, Y, X) = 8 F Z Y X bytes (two packed words per
+ * voxel: the z pass's and the y pass's); a smaller one, and out == primary, are ALIBY_ERR_INVALID, and no refused call writes
+ * anything.  F * Z * Y * X == 0 is a successful no-op that needs no buffers.  Uses no context scratch and does not wait for `stream`.
+ * Three launches (a z walk, a y scan, an x scan); 2 B read, 4 B + 4 B and 4 B + 4 B through the workspace and 2 B written per voxel
+ * (20 B); per-voxel work linear in the reach.  Not built: "Propagation", "Watershed", "Distance - B", a float spacing, "Expand until
+ * adjacent", discarding objects on the border.  Kernels: csrc/feat_secondary3d.hip. */
+size_t aliby_secondary_volume_workspace_bytes(int F, int Z, int Y, int X);
+int aliby_secondary_volume(aliby_ctx* ctx, const uint16_t* primary, int F, int Z, int Y, int X, int distance, int sz, int sy, int sx,
+                           void* workspace, size_t workspace_bytes, uint16_t* out, void* stream);
 /* trap.imBackground / trap.background_max5 (src/extraction/core/functions/trap.py:6-43): per tile, over the pixels of
  * `channel` under NO mask (labels == 0): out[f*2] = their median (numpy.median), out[f*2+1] = the mean of the five largest
  * (of all of them when fewer); NaN for a tile without background. */
