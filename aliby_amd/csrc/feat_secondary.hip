@@ -12,7 +12,8 @@
 //     else                               out[p] = min{ labels[q] : |p - q|^2 = m }
 // N in 1..64.  Labels keep the primary numbering (65535 is a label like any other), nothing crosses a tile edge, and every step is
 // integer arithmetic: a tile carries the same bits whatever the batch, the launch form and the stream.
-// Not built: "Propagation", "Watershed", "Distance - B", discarding objects that touch the border.  (Volume labels: feat_secondary3d.hip.)
+// Not built: "Watershed", discarding objects that touch the border.  ("Propagation", "Distance - B": feat_propagate.hip; volume labels:
+// feat_secondary3d.hip.)
 //
 // The exact separable form, two launches and one 4-byte-per-pixel intermediate (the caller's workspace):
 // k_secondary_columns  a lane owns one column x of a segment of SECONDARY_SEG rows of one tile.  It walks down from N rows above the

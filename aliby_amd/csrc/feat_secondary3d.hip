@@ -15,7 +15,7 @@
 // on every axis (it bounds the scans; not a structural limit).  65535 is a label like any other, nothing crosses a stack edge, and
 // every step is integer arithmetic: a stack carries the same bits whatever the batch, the launch form and the stream.  With Z == 1
 // and unit spacing it is feat_secondary.hip's function on the one plane, bit for bit.
-// Not built: "Propagation", "Watershed", "Distance - B", a float spacing, discarding objects that touch the border.
+// Not built: "Propagation" and "Distance - B" on volumes (2-D: feat_propagate.hip), "Watershed", a float spacing, discarding objects that touch the border.
 //
 // The exact separable form: the lexicographic minimum of (distance, label) decomposes over the axes, so three passes equal the brute
 // force.  Three launches and two 4-byte-per-voxel intermediates (the caller's workspace):

@@ -161,6 +161,7 @@ class FeatureEngine:
         self.profile = None  # set to {} to time kernel groups with HIP events on the launch stream
         self.profile_sample = {}  # group name -> n: bracket only every n-th launch of that group
         self._sample_count = {}
+        self.propagate_stats = None  # (rounds that changed a key, flag reads) of the last propagate_labels call
 
     # ---------------------------------------------------------------- the launch path
     def _launch(self, group, entry: str, *args) -> None:
@@ -810,6 +811,38 @@ class FeatureEngine:
             work = torch.empty(nbytes // 4, dtype=torch.int32, device=primary.device)
             self._launch("secondary3d", "aliby_secondary_volume", _ptr(primary), F, Z, Y, X, n, sz, sy, sx, _ptr(work), nbytes, _ptr(out))
         return out
+
+    def propagate_labels(self, primary, image, threshold=0, regularization=0.05, distance=None, image_max=65535, return_distances=False):
+        """primary, image uint16 [F,Y,X] on the device -> device uint16 [F,Y,X] (aliby_propagate_labels), with return_distances
+        (labels, D uint64 [F,Y,X]): CellProfiler's IdentifySecondaryObjects, method "Propagation" — the primary labels grow along the
+        stain `image`.  A pixel is passable if it is labelled, or image >= threshold and (with `distance`) within that many pixels
+        of a labelled pixel; a step between 8-neighbours costs isqrt(256 (P^2 + m lambda2)) sixteenths of a grey level, P the summed
+        absolute differences of the two 3 x 3 neighbourhoods (coordinates clamped to the tile), m = 1 straight and 2 diagonal; a pixel
+        takes the label of the cheapest path, ties to the smaller label, 0 (and D = 2^64 - 1) where none arrives.  The arguments are
+        those of features.propagate_args; "Distance - B" is threshold=0 with a distance.  Labels keep the primary numbering; nothing
+        crosses a tile edge; a tile may hold at most 2^23 pixels.  Tensors that are not uint16 [F,Y,X] on the device and of one
+        shape are ValueErrors; a float32 image is refused by name.  Exact integers: the same bits whatever the batch and the stream.
+        PARITY UNPINNED (include/aliby_hip.h).  Waits on the stream between chunks of rounds; `propagate_stats` keeps the last call's
+        (rounds that changed a key, flag reads).  Uses no context scratch (its 32-bytes-per-pixel workspace is allocated here)."""
+        args = feat.propagate_args(threshold, regularization, distance, image_max)
+        thr, n, lambda2 = args.threshold, args.distance, args.lambda2
+        if isinstance(image, torch.Tensor) and image.dtype == torch.float32:
+            raise ValueError("propagate_labels: a float32 image is not built (the metric is an exact integer on uint16 grey levels): "
+                             "pass the uint16 pixels")
+        F, Y, X = self._label_blocks("propagate_labels", "F,Y,X", {"primary": primary, "image": image}, "primary and image")
+        if Y * X > 1 << 23:
+            raise ValueError(f"propagate_labels: a tile may hold at most 2^23 pixels, got {Y} x {X}")
+        primary, image = primary.contiguous(), image.contiguous()
+        out = torch.empty_like(primary)
+        dist = torch.empty(primary.shape, dtype=torch.uint64, device=primary.device) if return_distances else None
+        stats = np.zeros(2, np.int32)
+        if out.numel():
+            nbytes = int(self.lib.aliby_propagate_workspace_bytes(F, Y, X))
+            work = torch.empty(nbytes // 8, dtype=torch.int64, device=primary.device)
+            self._launch("propagate", "aliby_propagate_labels", _ptr(primary), _ptr(image), F, Y, X, thr, lambda2, n or 0, _ptr(work), nbytes,
+                         _ptr(out), _ptr(dist) if dist is not None else None, _ptr(stats))
+        self.propagate_stats = (int(stats[0]), int(stats[1]))
+        return (out, dist) if return_distances else out
 
     def relate3d(self, volume_a, counts_a, volume_b, counts_b, spacing=(1.0, 1.0, 1.0), out_a=None, col0_a=0, out_b=None, col0_b=0):
         """Two sets of volume labels uint16 [F,Z,Y,X] of one shape (1..counts_*[f] per stack) -> (matrix_a, matrix_b), float64

@@ -370,6 +370,37 @@ def secondary_masks(primary, distance, who="secondary"):
     return tiles if isinstance(primary, (list, tuple)) else tiles[0]
 
 
+def propagate_masks(primary, pixels, channel, threshold=0, regularization=0.05, distance=None, image_max=65535, who="propagate"):
+    """The propagated labels of one segment result along a stain (FeatureEngine.propagate_labels: CellProfiler's "Propagation", the
+    cell around a nucleus where the cell channel says it ends) in the container `primary` came in: one [Y,X] uint16 image or a list
+    of them, each with its device copy attached (devcache, kind="labels"), so that an extract step after it measures them as it
+    measures a segment step's.  `pixels` is the tile step's [F,C,Z,Y,X] block; the stain is its channel `channel`, max-projected
+    over Z on the device (engine.reduce_z): the image the "max" reducer measures.  float32 pixels, a channel that is not one of
+    the block's, a tile count or shape that does not match `primary`, and bad parameters are ValueErrors."""
+    from aliby_amd import _lib
+    from aliby_amd.extraction.engine import FeatureEngine
+    from aliby_amd.extraction.features import propagate_args
+
+    propagate_args(threshold, regularization, distance, image_max)
+    labels = _stack_masks(_tile_list(who, primary))
+    if not hasattr(pixels, "ndim") or pixels.ndim != 5:
+        raise ValueError(f"{who}: pixels must be the tile step's [F,C,Z,Y,X] block, got {getattr(pixels, 'shape', type(pixels).__name__)}")
+    dev, dtype = _device_pixels(pixels)
+    if dtype == _lib.F32:
+        raise ValueError(f"{who}: float32 pixels are not built (the metric is an exact integer on uint16 grey levels)")
+    C = int(dev.shape[1])
+    if isinstance(channel, bool) or not isinstance(channel, (int, np.integer)) or not 0 <= int(channel) < C:
+        raise ValueError(f"{who}: channel must be an integer in 0..{C - 1} (the pixels hold {C} channels), got {channel!r}")
+    engine = FeatureEngine()
+    image = engine.reduce_z(dev[:, int(channel)].contiguous(), _lib.RED_MAX, _lib.U16, _lib.U16)
+    if tuple(image.shape) != tuple(labels.shape):
+        raise ValueError(f"{who}: 'primary' is {tuple(labels.shape)} [F,Y,X], the pixels give {tuple(image.shape)}: they do not match")
+    out = engine.propagate_labels(labels, image, threshold, regularization, distance, image_max)
+    host = out.cpu().numpy()
+    tiles = [devcache.attach(host[k], out[k], kind="labels") for k in range(host.shape[0])]
+    return tiles if isinstance(primary, (list, tuple)) else tiles[0]
+
+
 def relate_masks(masks, others: dict, who="extractrelate"):
     """The rows of the objects of `masks` relative to every object set of `others` {name: its segment result}: returns
     (tileid_instructions, results) like process_tree_masks, with the single instruction RELATE_INSTRUCTION and the columns

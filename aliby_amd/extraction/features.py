@@ -10,7 +10,9 @@ identity 4 + 6*S + 5*I + 10*P = 632 quoted at examples/01:156-158 is reproduced 
 
 from __future__ import annotations
 
+import math
 import numbers
+from typing import NamedTuple
 
 INTENSITY_CORE = [
     "Intensity_IntegratedIntensity",
@@ -217,6 +219,61 @@ def secondary_volume_args(distance, spacing=(1, 1, 1)) -> tuple:
         raise ValueError(f"secondary_volume: distance {n} over spacing {steps} reaches more than {SECONDARY3D_MAX_REACH} voxels along "
                          "an axis")
     return n, steps
+
+
+PROPAGATE_MAX_SCALED_LAMBDA = 1 << 20  # regularization * image_max: its square fits the weights of csrc/feat_propagate.hip
+
+
+def _whole_number(value) -> bool:
+    return not isinstance(value, bool) and (isinstance(value, numbers.Integral)
+                                            or (isinstance(value, numbers.Real) and float(value).is_integer()))
+
+
+PROPAGATE_OPTIONS = ("threshold", "regularization", "distance", "image_max")  # what a `propagate_<name>` step takes beside `channel`
+
+
+class PropagateArgs(NamedTuple):
+    threshold: int
+    regularization: float
+    distance: int | None
+    image_max: int
+    lambda2: int
+
+    def options(self, given=PROPAGATE_OPTIONS) -> dict:
+        """The checked values of the options named in `given`, by name."""
+        return {key: getattr(self, key) for key in PROPAGATE_OPTIONS if key in given}
+
+
+def propagate_channel(channel) -> int:
+    """The stain channel of a `propagate_<name>` step: a non-negative integer (no bool, no float), else a ValueError."""
+    if isinstance(channel, bool) or not isinstance(channel, numbers.Integral) or channel < 0:
+        raise ValueError(f"propagate: channel must be a non-negative integer, got {channel!r}")
+    return int(channel)
+
+
+def propagate_args(threshold=0, regularization=0.05, distance=None, image_max=65535) -> PropagateArgs:
+    """(threshold, regularization, distance, image_max, lambda2) of FeatureEngine.propagate_labels and a `propagate_<name>` step,
+    checked, as a named tuple.  threshold: an integer in 0..65535 (a grey level of the uint16 image; pixels at or above it are passable).
+    regularization: a finite float >= 0 (CellProfiler's, 0.05 by default).  distance: None, or an integer in 1..64 that keeps the
+    objects within that many pixels of their seeds ("Distance - B" is threshold 0 with a distance).  image_max: an integer in
+    1..65535, the grey level that CellProfiler's 0..1 scale maps to 1.  Integers may come as floats that hold one (400.0).
+    lambda2 = round((regularization * image_max)^2) in float64, half to even, the integer the kernels add per step;
+    regularization * image_max must be at most 2^20.  A bool, a str, a non-finite value and anything out of range are ValueErrors
+    that say what is allowed.  Needs no device."""
+    if not _whole_number(threshold) or not 0 <= int(threshold) <= 65535:
+        raise ValueError(f"propagate: threshold must be an integer in 0..65535, got {threshold!r}")
+    if isinstance(regularization, bool) or not isinstance(regularization, numbers.Real) or not math.isfinite(float(regularization)) \
+            or float(regularization) < 0:
+        raise ValueError(f"propagate: regularization must be a finite number >= 0, got {regularization!r}")
+    if distance is not None and (not _whole_number(distance) or not 1 <= int(distance) <= SECONDARY_MAX_DISTANCE):
+        raise ValueError(f"propagate: distance must be None or an integer in 1..{SECONDARY_MAX_DISTANCE}, got {distance!r}")
+    if not _whole_number(image_max) or not 1 <= int(image_max) <= 65535:
+        raise ValueError(f"propagate: image_max must be an integer in 1..65535, got {image_max!r}")
+    scaled = float(regularization) * float(int(image_max))
+    if scaled > PROPAGATE_MAX_SCALED_LAMBDA:
+        raise ValueError(f"propagate: regularization * image_max must be at most 2^20, got {regularization!r} * {image_max!r}")
+    return PropagateArgs(int(threshold), float(regularization), None if distance is None else int(distance), int(image_max),
+                         int(round(scaled * scaled)))
 
 
 def relate_names(other: str) -> list[str]:

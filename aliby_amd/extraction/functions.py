@@ -125,6 +125,20 @@ def secondary_objects(primary_labels, distance) -> np.ndarray:
     return FeatureEngine().secondary_labels(_label_tile("primary_labels", primary_labels), distance)[0].cpu().numpy()
 
 
+def propagate_objects(primary_labels, image, threshold=0, regularization=0.05, distance=None, image_max=65535) -> np.ndarray:
+    """One label image [Y, X] and one uint16 stain image [Y, X] -> uint16 [Y, X]: the labels grown along the stain, every passable
+    pixel (labelled, or image >= threshold and, with `distance`, within that many pixels of a labelled one) taking the label of the
+    cheapest path over the integer metric of include/aliby_hip.h, ties to the smaller label (FeatureEngine.propagate_labels,
+    csrc/feat_propagate.hip).  The cell around a nucleus is propagate_objects(nuclei, cell_stain, threshold=t), and the cytoplasm
+    tertiary_objects(that, nuclei).  Not in the reference: CellProfiler's IdentifySecondaryObjects, method "Propagation" (with a
+    distance and threshold 0: "Distance - B"), PARITY UNPINNED."""
+    image = np.asarray(image)
+    if image.dtype != np.uint16 or image.ndim != 2:
+        raise ValueError(f"image must be one uint16 [Y, X] image (float32 images are not built), got {image.dtype} {image.shape}")
+    return FeatureEngine().propagate_labels(_label_tile("primary_labels", primary_labels), to_device_u16(image[None]), threshold, regularization,
+                                            distance, image_max)[0].cpu().numpy()
+
+
 def _label_stack(name: str, labels):
     labels = np.asarray(labels)
     if labels.ndim != 3:

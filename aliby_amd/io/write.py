@@ -187,9 +187,9 @@ def write_ndarray(result, steps_dir, subpath, tp: int) -> None:
 
 
 def dispatch_write_fn(step_name: str):
-    # (a secondary or tertiary step's result is label images, like a segment step's; a volumetertiary or volumesecondary step's is
-    # label stacks)
-    if step_name.startswith(("segment", "tile", "secondary", "tertiary", "volumetertiary", "volumesecondary")):
+    # (a secondary, propagate or tertiary step's result is label images, like a segment step's; a volumetertiary or volumesecondary
+    # step's is label stacks)
+    if step_name.startswith(("segment", "tile", "secondary", "propagate", "tertiary", "volumetertiary", "volumesecondary")):
         return write_ndarray
     if step_name.startswith("nahual_trackastra"):
         return write_parquet

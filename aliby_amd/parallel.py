@@ -92,8 +92,8 @@ def refuse_volume_pipelines(pipelines) -> None:
 
 def refuse_object_link_pipelines(pipelines) -> None:
     """The batched runner knows no step that reads two object sets together (`tertiary_`, `extractrelate_`, and their volume forms
-    `volumetertiary_`, `volumerelate_`) or derives one from another (`secondary_`, `volumesecondary_`): a pipeline with one is refused up front, before any
-    position is read."""
+    `volumetertiary_`, `volumerelate_`) or derives one from another (`secondary_`, `propagate_`, `volumesecondary_`): a pipeline with
+    one is refused up front, before any position is read."""
     for pipeline in pipelines:
         for name in (pipeline.get("steps", {}) if isinstance(pipeline, dict) else {}):
             if name.startswith(("tertiary_", "extractrelate_")):
@@ -101,6 +101,9 @@ def refuse_object_link_pipelines(pipelines) -> None:
                                           "run such a pipeline position by position with aliby_amd.pipe.run_pipeline_and_post")
             if name.startswith("secondary_"):
                 raise NotImplementedError(f"run_positions has no batched form of step '{name}' (a 'secondary_' step): "
+                                          "run such a pipeline position by position with aliby_amd.pipe.run_pipeline_and_post")
+            if name.startswith("propagate_"):
+                raise NotImplementedError(f"run_positions has no batched form of step '{name}' (a 'propagate_' step): "
                                           "run such a pipeline position by position with aliby_amd.pipe.run_pipeline_and_post")
             if name.startswith(("volumetertiary_", "volumerelate_")):
                 raise NotImplementedError(f"run_positions has no batched form of step '{name}' (a 'volumetertiary_' or 'volumerelate_' "

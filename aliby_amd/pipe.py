@@ -43,6 +43,8 @@ _PREFIXES = (
     ("extractrelate_", lambda name, params, done: core._init_relate(name, params)),
     # one object set grown into another (extension; csrc/feat_secondary.hip): the cell around a nucleus, N pixels out
     ("secondary_", lambda name, params, done: core._init_secondary(name, params)),
+    # ... or grown along a stain (extension; csrc/feat_propagate.hip): the cell around a nucleus as far as the cell channel carries it
+    ("propagate_", lambda name, params, done: core._init_propagate(name, params)),
     # (not an "extract" prefix: every step that starts with "extract" is joined to the 2-D rows on metadata_label, which would pair
     # volume label k with 2-D label k; the volume rows get their own table, profiles3d/)
     ("volume_", lambda name, params, done: core._init_volume(name, params, done)),

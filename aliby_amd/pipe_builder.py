@@ -81,17 +81,50 @@ def _volume_secondary_sets(secondary, volume_secondary, volume_features):
     return grown
 
 
-def _object_links(objects, relate, tertiary, secondary=()):
+def _propagate_sets(objects, secondary, propagate):
+    """The `propagate` keyword of build_pipeline_steps, checked against the segmented and the secondary object sets:
+    {name: (primary, channel, {option: checked value})}."""
+    from aliby_amd.extraction.features import PROPAGATE_OPTIONS, propagate_args, propagate_channel, relate_names
+
+    if propagate is None:
+        return {}
+    if not isinstance(propagate, dict):
+        raise ValueError(f"propagate must be a dict {{name: (primary, channel)}} or {{name: (primary, channel, options)}}, got {propagate!r}")
+    checked = {}
+    for name, entry in propagate.items():
+        relate_names(name)  # (a name that a step name or a column name cannot carry)
+        if name in objects:
+            raise ValueError(f"propagate: '{name}' is already a segmented object set")
+        if name in secondary:
+            raise ValueError(f"propagate: '{name}' is already a secondary object set")
+        if not isinstance(entry, (tuple, list)) or len(entry) not in (2, 3):
+            raise ValueError(f"propagate['{name}'] must be (primary, channel) or (primary, channel, options), got {entry!r}")
+        primary, channel, options = (*entry, {})[:3]
+        if primary not in objects:
+            raise ValueError(f"propagate['{name}']: the primary {primary!r} is not a segmented object set of {objects}")
+        if not isinstance(options, dict) or set(options) - set(PROPAGATE_OPTIONS):
+            raise ValueError(f"propagate['{name}']: the options must be a dict with keys of {list(PROPAGATE_OPTIONS)}, got {options!r}")
+        try:
+            values = propagate_args(**options).options()
+            checked[name] = (primary, propagate_channel(channel), {key: values[key] for key in options})  # (in the entry's order)
+        except ValueError as e:
+            raise ValueError(f"propagate['{name}']: {e}") from None
+    return checked
+
+
+def _object_links(objects, relate, tertiary, secondary=(), propagate=()):
     """The `relate` and `tertiary` keywords of build_pipeline_steps, checked against the object sets — the segmented ones and the
-    names of `secondary`: ({obj: [partners]} in first-seen order, {name: (outer, inner)})."""
+    names of `secondary` and `propagate`: ({obj: [partners]} in first-seen order, {name: (outer, inner)})."""
     from aliby_amd.extraction.features import relate_names
 
-    objects = [*objects, *secondary]
+    objects = [*objects, *secondary, *propagate]
     tertiary = dict(tertiary or {})
     for name, pair in tertiary.items():
         relate_names(name)  # (a name that a step name or a column name cannot carry)
         if name in secondary:
             raise ValueError(f"tertiary: '{name}' is already a secondary object set")
+        if name in propagate:
+            raise ValueError(f"tertiary: '{name}' is already a propagated object set")
         if name in objects:
             raise ValueError(f"tertiary: '{name}' is already a segmented object set")
         if not isinstance(pair, (tuple, list)) or len(pair) != 2 or pair[0] == pair[1] or any(o not in objects for o in pair):
@@ -127,6 +160,7 @@ def build_pipeline_steps(
     volume_relate: bool = False,
     secondary: dict[str, tuple[str, int]] | None = None,
     volume_secondary: bool | tuple[int, int] = False,
+    propagate: dict[str, tuple] | None = None,
 ) -> dict:
     """Extension (not in the reference): `volume_features`, a sequence of per-channel volume family names
     (extraction.families.VOLUME: "intensity3d", "intensity3d_detail", "texture3d", "granularity3d"), makes every segment step
@@ -172,7 +206,20 @@ def build_pipeline_steps(
     `relate` / `tertiary`, their volumes coming from the `volumesecondary_` steps: secondary={"cell": ("nuclei", 10)},
     tertiary={"cytoplasm": ("cell", "nuclei")}, volume_features=(...), volume_relate=True, volume_secondary=True with only nuclei
     segmented puts nuclei, cell and cytoplasm rows into profiles3d/, joined on the volume label.  With the default False the dict and
-    every refusal are what they are without the keyword."""
+    every refusal are what they are without the keyword.
+
+    Extension (not in the reference; CellProfiler's IdentifySecondaryObjects, method "Propagation", csrc/feat_propagate.hip):
+    `propagate`, {name: (primary, channel)} or {name: (primary, channel, options)}, adds a `propagate_<name>` step
+    {"channel": c, **options} right after the secondary steps and before any tertiary step: the primary's labels grown along the stain
+    in channel c of the tile's pixels, max-projected over Z.  options: "threshold", "regularization", "distance", "image_max"
+    (features.propagate_args; {"distance": N} alone is "Distance - B").  The step is saved like a segment step, its passed_data are
+    [("masks", "segment_<primary>", "primary"), ("pixels", "tile")], and `extract_<name>` / `extractmulti_<name>` steps with the
+    shared specs measure it: rows with metadata_object = <name> whose metadata_label is the primary object's.  A propagated name may
+    be the outer or inner set of a `tertiary` entry and a member of a `relate` pair: propagate={"cell": ("nuclei", 0, {"threshold":
+    400})}, tertiary={"cytoplasm": ("cell", "nuclei")}.  A name that is already a segmented, secondary or tertiary object set, a
+    primary that is not a segmented object set, a malformed entry or option, and a propagated name in an entry that
+    `volume_relate=True` takes to the volume labels (there is no volume form) are ValueErrors.  With the default None the dict is
+    what it is without the keyword."""
     if channels_to_segment is None:
         channels_to_segment = {"nuclei": 1, "cell": 0}
     kind = "cellpose" if nahual_addresses is None else "nahual_cellpose"
@@ -180,7 +227,8 @@ def build_pipeline_steps(
         channels_to_extract = list(channels_to_segment.values())
     objects = list(channels_to_segment)
     secondary = _secondary_sets(objects, secondary)
-    related, tertiary = _object_links(objects, relate, tertiary, secondary)
+    propagate = _propagate_sets(objects, secondary, propagate)
+    related, tertiary = _object_links(objects, relate, tertiary, secondary, propagate)
     if not isinstance(volume_relate, bool):
         raise ValueError(f"volume_relate must be a bool, got {volume_relate!r}")
     if volume_relate and (volume_features is None or not (related or tertiary)):
@@ -192,15 +240,22 @@ def build_pipeline_steps(
         if reached:
             raise ValueError(f"volume_relate=True: the secondary object sets {reached} have no volume form (a 'secondary_' step grows "
                              "2-D labels): keep them out of relate / tertiary, or leave volume_relate off")
+    if volume_relate:
+        reached = [name for name in propagate if name in related or any(name in pair for pair in tertiary.values())]
+        if reached:
+            raise ValueError(f"volume_relate=True: the propagated object sets {reached} have no volume form (a 'propagate_' step grows "
+                             "2-D labels): keep them out of relate / tertiary, or leave volume_relate off")
     producer = ({obj: f"segment_{obj}" for obj in objects} | {name: f"secondary_{name}" for name in secondary}
-                | {name: f"tertiary_{name}" for name in tertiary})
-    derived = (*secondary, *tertiary)  # object sets without a segment step of their own, in step order
+                | {name: f"propagate_{name}" for name in propagate} | {name: f"tertiary_{name}" for name in tertiary})
+    derived = (*secondary, *propagate, *tertiary)  # object sets without a segment step of their own, in step order
 
     steps = {"tile": {"tile_size": None}}
     for obj, ch in channels_to_segment.items():
         steps[f"segment_{obj}"] = {"segmenter_kwargs": {"kind": kind}, "channel_to_segment": ch}
     for name, (_, distance) in secondary.items():
         steps[f"secondary_{name}"] = {"distance": distance}
+    for name, (_, channel, options) in propagate.items():
+        steps[f"propagate_{name}"] = {"channel": channel, **options}
     for name in tertiary:
         steps[f"tertiary_{name}"] = {"shrink_inner": True}
     # the steps that keep the volume labels of an object set (a tertiary name: only under volume_relate)
@@ -239,6 +294,8 @@ def build_pipeline_steps(
     }
     for name, (primary, _) in secondary.items():
         pipeline["passed_data"][f"secondary_{name}"] = [("masks", f"segment_{primary}", "primary")]
+    for name, (primary, _, _) in propagate.items():
+        pipeline["passed_data"][f"propagate_{name}"] = [("masks", f"segment_{primary}", "primary"), ("pixels", "tile")]
     for name, (outer, inner) in tertiary.items():
         pipeline["passed_data"][f"tertiary_{name}"] = [("masks", producer[outer], "outer"), ("masks", producer[inner], "inner")]
     for obj, others in related.items():

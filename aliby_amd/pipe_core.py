@@ -325,6 +325,37 @@ def _init_secondary(step_name: str, parameters: dict) -> Callable:
     return secondary_step
 
 
+def _init_propagate(step_name: str, parameters: dict) -> Callable:
+    """A `propagate_<name>` step: the labels of the `primary` object set grown along the stain in channel `channel` of the tile step's
+    pixels, max-projected over Z (CellProfiler's IdentifySecondaryObjects, method "Propagation": the cell around a nucleus where the
+    cell stain says it ends; extraction.extract.propagate_masks), in the container the primary segment step returned, so that
+    `extract_<name>` / `extractmulti_<name>` steps measure it like a segment step's labels and a `tertiary_` step may take it as its
+    outer set.  `channel` is required: a non-negative integer.  Optional: `threshold`, `regularization`, `distance`, `image_max`
+    (features.propagate_args; a `distance` alone is "Distance - B")."""
+    from aliby_amd.extraction.extract import propagate_masks
+    from aliby_amd.extraction.features import PROPAGATE_OPTIONS, propagate_args, propagate_channel
+
+    unknown = set(parameters) - {"channel", *PROPAGATE_OPTIONS}
+    if unknown:
+        raise ValueError(f"Step '{step_name}': unknown parameters {sorted(unknown)}.")
+    if "channel" not in parameters:
+        raise ValueError(f"Step '{step_name}' is missing required 'channel'.")
+    try:
+        channel = propagate_channel(parameters["channel"])
+        checked = propagate_args(**{key: parameters[key] for key in PROPAGATE_OPTIONS if key in parameters}).options()
+    except ValueError as e:
+        raise ValueError(f"Step '{step_name}': {e}") from None
+
+    def propagate_step(primary=None, pixels=None):
+        missing = [key for key, value in (("primary", primary), ("pixels", pixels)) if value is None]
+        if missing:
+            raise ValueError(f"Step '{step_name}': no input for {missing}: 'passed_data' must hand it the masks of a segment step under "
+                             "the alias 'primary' and the pixels of the tile step.")
+        return propagate_masks(primary, pixels, channel, **checked, who=f"Step '{step_name}'")
+
+    return propagate_step
+
+
 def _check_volume_links(steps: dict) -> None:
     """The wiring of the volume steps that read another step's kept volume, before any timepoint: a `volumetertiary_`,
     `volumesecondary_` or `volumerelate_` step, and a `volume_` step fed by a `volumetertiary_` or `volumesecondary_` one, names steps
@@ -365,6 +396,8 @@ def _check_object_links(steps: dict, passed_data: dict) -> None:
             wanted = ["outer", "inner"]
         elif name.startswith("secondary_"):
             wanted = ["primary"]
+        elif name.startswith("propagate_"):
+            wanted = ["primary", "pixels"]
         else:
             continue
         have = {dep[2] if len(dep) > 2 else dep[0] for dep in passed_data.get(name, ())}

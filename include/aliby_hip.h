@@ -595,8 +595,9 @@ int aliby_tertiary_labels(aliby_ctx* ctx, const uint16_t* outer, const uint16_t*
  * 4-byte aligned]: the caller's, at least aliby_secondary_workspace_bytes(F, Y, X) = 4 F Y X bytes (one packed word per pixel: the
  * vertical distance to the column's nearest labelled pixel and its label); a smaller one, and out == primary, are ALIBY_ERR_INVALID.
  * F * Y * X == 0 is a successful no-op.  Uses no context scratch and does not wait for `stream`.  Two launches; 2 B read, 4 B + 4 B
- * through the workspace and 2 B written per pixel; per-pixel work linear in N.  Not built: "Propagation", "Watershed",
- * "Distance - B", discarding objects on the border.  (Volume labels: aliby_secondary_volume.)  Kernels: csrc/feat_secondary.hip. */
+ * through the workspace and 2 B written per pixel; per-pixel work linear in N.  Not built: "Watershed", discarding objects on the
+ * border.  ("Propagation" and "Distance - B": aliby_propagate_labels.  Volume labels: aliby_secondary_volume.)  Kernels:
+ * csrc/feat_secondary.hip. */
 size_t aliby_secondary_workspace_bytes(int F, int Y, int X);
 int aliby_secondary_labels(aliby_ctx* ctx, const uint16_t* primary, int F, int Y, int X, int distance, void* workspace,
                            size_t workspace_bytes, uint16_t* out, void* stream);
@@ -629,11 +630,57 @@ int aliby_secondary_labels(aliby_ctx* ctx, const uint16_t* primary, int F, int Y
  * voxel: the z pass's and the y pass's); a smaller one, and out == primary, are ALIBY_ERR_INVALID, and no refused call writes
  * anything.  F * Z * Y * X == 0 is a successful no-op that needs no buffers.  Uses no context scratch and does not wait for `stream`.
  * Three launches (a z walk, a y scan, an x scan); 2 B read, 4 B + 4 B and 4 B + 4 B through the workspace and 2 B written per voxel
- * (20 B); per-voxel work linear in the reach.  Not built: "Propagation", "Watershed", "Distance - B", a float spacing, "Expand until
- * adjacent", discarding objects on the border.  Kernels: csrc/feat_secondary3d.hip. */
+ * (20 B); per-voxel work linear in the reach.  Not built: "Propagation" and "Distance - B" on volumes (2-D: aliby_propagate_labels),
+ * "Watershed", a float spacing, "Expand until adjacent", discarding objects on the border.  Kernels: csrc/feat_secondary3d.hip. */
 size_t aliby_secondary_volume_workspace_bytes(int F, int Z, int Y, int X);
 int aliby_secondary_volume(aliby_ctx* ctx, const uint16_t* primary, int F, int Z, int Y, int X, int distance, int sz, int sy, int sx,
                            void* workspace, size_t workspace_bytes, uint16_t* out, void* stream);
+/* "propagate": CellProfiler's IdentifySecondaryObjects, method "Propagation" (its default) — the primary labels grow along a stain:
+ * a pixel takes the label of the seed it reaches most cheaply over a metric that charges for grey-level differences, and a threshold
+ * on the stain says where the cells end.  centrosome's `propagate` works in float64 with a priority queue: its result on ties follows
+ * the queue order, and float sums follow the order of relaxation.  Here the metric is an exact integer, so every relaxation order
+ * reaches the same unique fixed point and a tile carries the same bits whatever the batch, the launch form and the stream
+ * (tests/propagate_ref.py restates the definition as a heap Dijkstra in Python integers and as a Jacobi iteration).  PARITY UNPINNED:
+ * the 1/16-grey-level quantisation, ties to the smaller label and >= for the threshold are this library's.
+ * Every tile f of primary [dev, F x Y x X uint16, 0 = background] and image [dev, F x Y x X uint16] is handled on its own.
+ *   lambda2 = L = llrint((regularization * image_max)^2), computed by the caller in float64 (features.propagate_args); at most 2^40.
+ *   A pixel p is passable iff primary[p] != 0, or image[p] >= threshold and (distance == 0, or some labelled pixel of the tile lies
+ *     within `distance` of p: aliby_secondary_labels(primary, distance)[p] != 0).
+ *   Passable pixels are joined to their passable 8-neighbours of the same tile.  For neighbours p, q:
+ *     P(p,q) = sum over o in {-1,0,1}^2 of |image[clamp(p+o)] - image[clamp(q+o)]|, each coordinate clamped to the tile on its own
+ *       (centrosome's clamped_fetch); an integer <= 9 * 65535.
+ *     m = |dy| + |dx|, 1 or 2.
+ *     W(p,q) = isqrt(256 (P^2 + m L)), the floor of the exact root: CellProfiler's sqrt(P^2 + m lambda^2) in sixteenths of a grey
+ *       level.  W is symmetric.
+ *   D[p] = the minimum over paths from any labelled pixel to p of the sum of W; 0 on labelled pixels.
+ *   out[p] = the smallest label among the seeds that reach p at exactly D[p].  Labelled pixels keep their label: they are sources
+ *     only (it matters where L = 0 on a flat stain lets another seed arrive at distance 0).
+ *   A pixel that is not passable, or has no path, gets out = 0 and D = 2^64 - 1.
+ * Y * X <= 2^23, else ALIBY_ERR_INVALID: with that bound D < 2^48 and (D << 16) | label fits one 64-bit word, the key the kernels
+ * minimise.  Nothing crosses a tile edge; 65535 is a label like any other.  "Distance - B" is threshold = 0 with distance = N: the
+ * reachable set is that of "Distance - N" (the digital segment to the nearest seed stays within N) and the stain only divides it.
+ * Worked examples:
+ *   regularization 0.05, image_max 65535: L = llrint(3276.75^2) = 10 737 091.  On a flat image P = 0: a straight step costs
+ *     isqrt(256 L) = 52 428, a diagonal one isqrt(512 L) = 74 144 (two straight steps cost more: paths cut corners).
+ *   the row [7 0 0 0 0 0 0 0 3] on a flat image: D = [0 52428 104856 157284 209712 157284 104856 52428 0], out = [7 7 7 7 3 3 3 3 3]
+ *     (the middle pixel is 4 steps from either seed: the smaller label).
+ *   P at the corner (0, 0) of a tile towards (0, 1): the offsets o = (., -1) of p read column 0 (clamped), those of q columns 0, 1, 2,
+ *     and the offsets o = (-1, .) read row 0 again: P = 2 (|I00 - I00| + |I00 - I01| + |I01 - I02|) + (|I10 - I10| + |I10 - I11| +
+ *     |I11 - I12|).
+ * threshold in 0..65535, distance 0 (none) or in 1..64, else ALIBY_ERR_INVALID.  workspace [dev, 8-byte aligned]: the caller's, at
+ * least aliby_propagate_workspace_bytes(F, Y, X) = 32 F Y X + 256 bytes (two key buffers, four weight planes, the flags; with a
+ * distance the reach pass's words lie over the weight planes); a smaller one, and out_labels == primary, are ALIBY_ERR_INVALID, and no
+ * refused call writes anything.  F * Y * X == 0 is a successful no-op that needs no buffers.  out_dist [dev, F x Y x X uint64] may be
+ * NULL.  stats_host [host, int32 x 2] may be NULL: the rounds that changed a key, and the reads of the change flags.  A round runs
+ * every 32 x 32 region of every tile to its fixed point inside LDS against a halo from the buffer no region writes; the call reads the
+ * flags of eight rounds at a time and so waits on `stream`.  More than Y * X + 1 changing rounds is ALIBY_ERR_TOO_LARGE, never a
+ * result (found at the read of the flags that passes the bound, up to seven rounds later; stats_host then holds the counts so far;
+ * every other refusal leaves it zero).  Uses no context scratch.  Not built: automatic thresholds, filling holes, discarding border objects, float32 images, a
+ * volume form.  Kernels: csrc/feat_propagate.hip. */
+size_t aliby_propagate_workspace_bytes(int F, int Y, int X);
+int aliby_propagate_labels(aliby_ctx* ctx, const uint16_t* primary, const uint16_t* image, int F, int Y, int X, int threshold,
+                           uint64_t lambda2, int distance, void* workspace, size_t workspace_bytes, uint16_t* out_labels,
+                           uint64_t* out_dist, int32_t* stats_host, void* stream);
 /* trap.imBackground / trap.background_max5 (src/extraction/core/functions/trap.py:6-43): per tile, over the pixels of
  * `channel` under NO mask (labels == 0): out[f*2] = their median (numpy.median), out[f*2+1] = the mean of the five largest
  * (of all of them when fewer); NaN for a tile without background. */
