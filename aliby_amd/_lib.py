@@ -166,6 +166,9 @@ _SIGNATURES = {
     "aliby_secondary_volume": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "aliby_propagate_workspace_bytes": (_sz, [_i, _i, _i]),
     "aliby_propagate_labels": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, C.c_uint64, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "aliby_propagate_labels_per_tile": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, C.c_uint64, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "aliby_auto_threshold_workspace_bytes": (_sz, [_i]),
+    "aliby_auto_threshold": (_i, [_vp, _vp, _i, _i, _i, _i, _i, C.c_double, _i, _i, _vp, _sz, _vp, _vp, _vp]),
     "aliby_features_cell": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "aliby_features_coloc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _i, _i, _i, _i,
                                   C.c_double, C.c_double, _vp, _vp, _vp]),

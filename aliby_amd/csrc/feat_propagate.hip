@@ -61,6 +61,7 @@ struct PropagateArgs {
   u16* out_labels;
   u64* out_dist;
   u64 lambda2;
+  const int* thresholds;  // [F], one per tile, or null: `threshold` for every tile
   int F, Y, X, threshold;
   int regions_x, regions_y;
 };
@@ -92,6 +93,7 @@ __global__ __launch_bounds__(PROPAGATE_BLOCK) void k_propagate_weights(Propagate
   const PropagateRegion g = propagate_region(a);
   const u16* image = a.image + g.tile;
   const u16* primary = a.primary + g.tile;
+  const int threshold = a.thresholds ? a.thresholds[blockIdx.x / (unsigned int)(a.regions_x * a.regions_y)] : a.threshold;
   for (int i = tid; i < (PROPAGATE_R + 4) * (PROPAGATE_R + 4); i += PROPAGATE_BLOCK) {
     const int r = i / (PROPAGATE_R + 4), c = i % (PROPAGATE_R + 4);
     const int y = min(max(g.y0 - 2 + r, 0), Y - 1), x = min(max(g.x0 - 2 + c, 0), X - 1);
@@ -103,7 +105,7 @@ __global__ __launch_bounds__(PROPAGATE_BLOCK) void k_propagate_weights(Propagate
     bool ok = false;
     if (y >= 0 && y < Y && x >= 0 && x < X) {
       const size_t p = (size_t)y * X + x;
-      ok = primary[p] != 0 || ((int)image[p] >= a.threshold && (a.reach == nullptr || a.reach[g.tile + p] != 0));
+      ok = primary[p] != 0 || ((int)image[p] >= threshold && (a.reach == nullptr || a.reach[g.tile + p] != 0));
     }
     pass[r][c] = ok ? 1 : 0;
   }
@@ -239,9 +241,10 @@ extern "C" size_t aliby_propagate_workspace_bytes(int F, int Y, int X) {
   return (size_t)F * (size_t)Y * (size_t)X * 32 + PROPAGATE_FLAG_BYTES;
 }
 
-extern "C" int aliby_propagate_labels(aliby_ctx* ctx, const uint16_t* primary, const uint16_t* image, int F, int Y, int X, int threshold,
-                                      uint64_t lambda2, int distance, void* workspace, size_t workspace_bytes, uint16_t* out_labels,
-                                      uint64_t* out_dist, int32_t* stats_host, void* stream) {
+// the body of both entries: `thresholds` [dev, F] or null for the scalar
+static int propagate_labels(aliby_ctx* ctx, const uint16_t* primary, const uint16_t* image, int F, int Y, int X, int threshold,
+                            const int32_t* thresholds, uint64_t lambda2, int distance, void* workspace, size_t workspace_bytes,
+                            uint16_t* out_labels, uint64_t* out_dist, int32_t* stats_host, void* stream) {
   ARG_CHECK(ctx != nullptr, "ctx is NULL");
   ARG_CHECK(F >= 0 && Y >= 0 && X >= 0, "bad shape");
   ARG_CHECK((long long)Y * X <= PROPAGATE_MAX_PIXELS, "a tile has more than 2^23 pixels (the packed key holds distances below 2^48)");
@@ -262,7 +265,7 @@ extern "C" int aliby_propagate_labels(aliby_ctx* ctx, const uint16_t* primary, c
   a.weights = reinterpret_cast<uint32_t*>(a.keys[1] + n);
   a.flags = reinterpret_cast<int*>(a.weights + 4 * n);
   a.out_labels = out_labels; a.out_dist = reinterpret_cast<u64*>(out_dist);
-  a.lambda2 = lambda2; a.F = F; a.Y = Y; a.X = X; a.threshold = threshold;
+  a.lambda2 = lambda2; a.thresholds = thresholds; a.F = F; a.Y = Y; a.X = X; a.threshold = threshold;
   a.regions_x = (X + PROPAGATE_R - 1) / PROPAGATE_R;
   a.regions_y = (Y + PROPAGATE_R - 1) / PROPAGATE_R;
   const long long blocks = (long long)F * a.regions_y * a.regions_x;
@@ -311,4 +314,21 @@ extern "C" int aliby_propagate_labels(aliby_ctx* ctx, const uint16_t* primary, c
   hipLaunchKernelGGL(k_propagate_finish, dim3(fgrid), block, 0, s, a.keys[from], n, out_labels, a.out_dist);
   KERNEL_CHECK();
   return ALIBY_OK;
+}
+
+extern "C" int aliby_propagate_labels(aliby_ctx* ctx, const uint16_t* primary, const uint16_t* image, int F, int Y, int X, int threshold,
+                                      uint64_t lambda2, int distance, void* workspace, size_t workspace_bytes, uint16_t* out_labels,
+                                      uint64_t* out_dist, int32_t* stats_host, void* stream) {
+  return propagate_labels(ctx, primary, image, F, Y, X, threshold, nullptr, lambda2, distance, workspace, workspace_bytes, out_labels,
+                          out_dist, stats_host, stream);
+}
+
+// one threshold per tile, read on the device by k_propagate_weights (aliby_auto_threshold's output); a value above 65535 passes nothing
+extern "C" int aliby_propagate_labels_per_tile(aliby_ctx* ctx, const uint16_t* primary, const uint16_t* image, int F, int Y, int X,
+                                               const int32_t* thresholds, uint64_t lambda2, int distance, void* workspace,
+                                               size_t workspace_bytes, uint16_t* out_labels, uint64_t* out_dist, int32_t* stats_host,
+                                               void* stream) {
+  ARG_CHECK(thresholds != nullptr || F <= 0 || Y <= 0 || X <= 0, "thresholds is NULL");
+  return propagate_labels(ctx, primary, image, F, Y, X, 0, thresholds, lambda2, distance, workspace, workspace_bytes, out_labels, out_dist,
+                          stats_host, stream);
 }

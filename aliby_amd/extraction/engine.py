@@ -812,7 +812,36 @@ class FeatureEngine:
             self._launch("secondary3d", "aliby_secondary_volume", _ptr(primary), F, Z, Y, X, n, sz, sy, sx, _ptr(work), nbytes, _ptr(out))
         return out
 
-    def propagate_labels(self, primary, image, threshold=0, regularization=0.05, distance=None, image_max=65535, return_distances=False):
+    def auto_threshold(self, image, method="otsu", classes=2, middle=None, correction=1.0, bounds=(0, 65535), return_details=False):
+        """image uint16 [F,Y,X] on the device -> device int32 [F] (aliby_auto_threshold), with return_details (thresholds, details
+        int32 [F,4] = (lo, hi, t1, t2) raw): Otsu's threshold of every tile on its own, over all its pixels — CellProfiler's automatic
+        threshold for IdentifySecondaryObjects.  Two classes: the smallest grey level t that maximises s0^2/n0 + s1^2/n1 over the
+        classes {v < t}, {v >= t} of the 65 536-level histogram.  Three classes: the same criterion over pairs of 256 bins of the
+        occupied range lo..hi; middle="foreground" (the default) takes the lower threshold, "background" the upper.  Then
+        min(max(rint(t * correction), bounds[0]), bounds[1]).  The arguments are those of features.auto_threshold_args.  The result
+        stays on the device: propagate_labels(thresholds=...) reads it there.  A tensor that is not uint16 [F,Y,X] on the device is a
+        ValueError; a float32 image is refused by name; views need not be contiguous.  Exact integers and correctly rounded float64:
+        the same bits whatever the batch and the stream, equal to tests/threshold_ref.py.  PARITY UNPINNED (include/aliby_hip.h).
+        Stream-ordered: no wait, no context scratch (its 256 KiB-per-tile histogram is allocated here)."""
+        args = feat.auto_threshold_args(method, classes, middle, correction, bounds)
+        if isinstance(image, torch.Tensor) and image.dtype == torch.float32:
+            raise ValueError("auto_threshold: a float32 image is not built (the histogram is over uint16 grey levels): pass the uint16 pixels")
+        F, Y, X = self._label_blocks("auto_threshold", "F,Y,X", {"image": image})
+        if F > 65535 or Y * X >= 1 << 32:
+            raise ValueError(f"auto_threshold: at most 65535 tiles of fewer than 2^32 pixels in one call, got {F} of {Y} x {X}")
+        image = image.contiguous()
+        out = torch.zeros(F, dtype=torch.int32, device=image.device)
+        details = torch.zeros((F, 4), dtype=torch.int32, device=image.device) if return_details else None
+        if image.numel():
+            nbytes = int(self.lib.aliby_auto_threshold_workspace_bytes(F))
+            work = torch.empty(nbytes // 4, dtype=torch.int32, device=image.device)
+            self._launch("auto_threshold", "aliby_auto_threshold", _ptr(image), F, Y, X, args.classes,
+                         args.middle_code, args.correction, args.bounds[0], args.bounds[1], _ptr(work), nbytes,
+                         _ptr(out), _ptr(details) if details is not None else None)
+        return (out, details) if return_details else out
+
+    def propagate_labels(self, primary, image, threshold=0, regularization=0.05, distance=None, image_max=65535, return_distances=False,
+                         thresholds=None):
         """primary, image uint16 [F,Y,X] on the device -> device uint16 [F,Y,X] (aliby_propagate_labels), with return_distances
         (labels, D uint64 [F,Y,X]): CellProfiler's IdentifySecondaryObjects, method "Propagation" — the primary labels grow along the
         stain `image`.  A pixel is passable if it is labelled, or image >= threshold and (with `distance`) within that many pixels
@@ -823,8 +852,13 @@ class FeatureEngine:
         crosses a tile edge; a tile may hold at most 2^23 pixels.  Tensors that are not uint16 [F,Y,X] on the device and of one
         shape are ValueErrors; a float32 image is refused by name.  Exact integers: the same bits whatever the batch and the stream.
         PARITY UNPINNED (include/aliby_hip.h).  Waits on the stream between chunks of rounds; `propagate_stats` keeps the last call's
-        (rounds that changed a key, flag reads).  Uses no context scratch (its 32-bytes-per-pixel workspace is allocated here)."""
+        (rounds that changed a key, flag reads).  Uses no context scratch (its 32-bytes-per-pixel workspace is allocated here).
+        `thresholds`: a device int32 [F] tensor with one threshold per tile in place of `threshold` (auto_threshold's result, read
+        on the device: aliby_propagate_labels_per_tile); a value above 65535 lets no unlabelled pixel of its tile pass.  Together
+        with a non-zero `threshold`, or of another dtype, shape or device, it is a ValueError."""
         args = feat.propagate_args(threshold, regularization, distance, image_max)
+        if thresholds is not None and args.threshold != 0:
+            raise ValueError(f"propagate_labels: give threshold or thresholds, not both (threshold={threshold!r})")
         thr, n, lambda2 = args.threshold, args.distance, args.lambda2
         if isinstance(image, torch.Tensor) and image.dtype == torch.float32:
             raise ValueError("propagate_labels: a float32 image is not built (the metric is an exact integer on uint16 grey levels): "
@@ -832,6 +866,13 @@ class FeatureEngine:
         F, Y, X = self._label_blocks("propagate_labels", "F,Y,X", {"primary": primary, "image": image}, "primary and image")
         if Y * X > 1 << 23:
             raise ValueError(f"propagate_labels: a tile may hold at most 2^23 pixels, got {Y} x {X}")
+        if thresholds is not None:
+            if not isinstance(thresholds, torch.Tensor) or thresholds.dtype != torch.int32 or tuple(thresholds.shape) != (F,) \
+                    or thresholds.device != primary.device:
+                got = (thresholds.dtype, tuple(thresholds.shape), str(thresholds.device)) if isinstance(thresholds, torch.Tensor) \
+                    else type(thresholds).__name__
+                raise ValueError(f"propagate_labels: thresholds must be an int32 [{F}] tensor on the device of the labels, got {got}")
+            thresholds = thresholds.contiguous()
         primary, image = primary.contiguous(), image.contiguous()
         out = torch.empty_like(primary)
         dist = torch.empty(primary.shape, dtype=torch.uint64, device=primary.device) if return_distances else None
@@ -839,7 +880,8 @@ class FeatureEngine:
         if out.numel():
             nbytes = int(self.lib.aliby_propagate_workspace_bytes(F, Y, X))
             work = torch.empty(nbytes // 8, dtype=torch.int64, device=primary.device)
-            self._launch("propagate", "aliby_propagate_labels", _ptr(primary), _ptr(image), F, Y, X, thr, lambda2, n or 0, _ptr(work), nbytes,
+            entry, level = ("aliby_propagate_labels", thr) if thresholds is None else ("aliby_propagate_labels_per_tile", _ptr(thresholds))
+            self._launch("propagate", entry, _ptr(primary), _ptr(image), F, Y, X, level, lambda2, n or 0, _ptr(work), nbytes,
                          _ptr(out), _ptr(dist) if dist is not None else None, _ptr(stats))
         self.propagate_stats = (int(stats[0]), int(stats[1]))
         return (out, dist) if return_distances else out

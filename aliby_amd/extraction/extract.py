@@ -370,18 +370,30 @@ def secondary_masks(primary, distance, who="secondary"):
     return tiles if isinstance(primary, (list, tuple)) else tiles[0]
 
 
-def propagate_masks(primary, pixels, channel, threshold=0, regularization=0.05, distance=None, image_max=65535, who="propagate"):
+def propagate_masks(primary, pixels, channel, threshold=0, regularization=0.05, distance=None, image_max=65535, who="propagate",
+                    auto_threshold=None, chosen=None):
     """The propagated labels of one segment result along a stain (FeatureEngine.propagate_labels: CellProfiler's "Propagation", the
     cell around a nucleus where the cell channel says it ends) in the container `primary` came in: one [Y,X] uint16 image or a list
     of them, each with its device copy attached (devcache, kind="labels"), so that an extract step after it measures them as it
     measures a segment step's.  `pixels` is the tile step's [F,C,Z,Y,X] block; the stain is its channel `channel`, max-projected
     over Z on the device (engine.reduce_z): the image the "max" reducer measures.  float32 pixels, a channel that is not one of
-    the block's, a tile count or shape that does not match `primary`, and bad parameters are ValueErrors."""
+    the block's, a tile count or shape that does not match `primary`, and bad parameters are ValueErrors.  `auto_threshold`: an option
+    dict of features.auto_threshold_args ({} for two-class Otsu) — every tile is then thresholded at its own Otsu level, computed on
+    the projected stain and read by the propagation on the device; with a non-zero `threshold` it is a ValueError.  `chosen`: a list
+    that receives the tiles' thresholds as Python ints (downloaded after the call, 4 bytes per tile)."""
     from aliby_amd import _lib
     from aliby_amd.extraction.engine import FeatureEngine
-    from aliby_amd.extraction.features import propagate_args
+    from aliby_amd.extraction.features import auto_threshold_options, propagate_args
 
-    propagate_args(threshold, regularization, distance, image_max)
+    checked = propagate_args(threshold, regularization, distance, image_max)
+    auto = None
+    if auto_threshold is not None:
+        try:
+            auto = auto_threshold_options(auto_threshold)
+        except ValueError as e:
+            raise ValueError(f"{who}: {e}") from None
+        if checked.threshold != 0:
+            raise ValueError(f"{who}: give threshold or auto_threshold, not both (threshold={threshold!r})")
     labels = _stack_masks(_tile_list(who, primary))
     if not hasattr(pixels, "ndim") or pixels.ndim != 5:
         raise ValueError(f"{who}: pixels must be the tile step's [F,C,Z,Y,X] block, got {getattr(pixels, 'shape', type(pixels).__name__)}")
@@ -395,8 +407,11 @@ def propagate_masks(primary, pixels, channel, threshold=0, regularization=0.05, 
     image = engine.reduce_z(dev[:, int(channel)].contiguous(), _lib.RED_MAX, _lib.U16, _lib.U16)
     if tuple(image.shape) != tuple(labels.shape):
         raise ValueError(f"{who}: 'primary' is {tuple(labels.shape)} [F,Y,X], the pixels give {tuple(image.shape)}: they do not match")
-    out = engine.propagate_labels(labels, image, threshold, regularization, distance, image_max)
+    thresholds = engine.auto_threshold(image, **auto._asdict()) if auto is not None else None
+    out = engine.propagate_labels(labels, image, threshold, regularization, distance, image_max, thresholds=thresholds)
     host = out.cpu().numpy()
+    if chosen is not None:
+        chosen[:] = [checked.threshold] * host.shape[0] if thresholds is None else [int(t) for t in thresholds.cpu().tolist()]
     tiles = [devcache.attach(host[k], out[k], kind="labels") for k in range(host.shape[0])]
     return tiles if isinstance(primary, (list, tuple)) else tiles[0]
 

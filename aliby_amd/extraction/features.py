@@ -276,6 +276,69 @@ def propagate_args(threshold=0, regularization=0.05, distance=None, image_max=65
                          int(round(scaled * scaled)))
 
 
+AUTO_THRESHOLD_OPTIONS = ("method", "classes", "middle", "correction", "bounds")  # the keys of an `auto_threshold` option dict
+AUTO_THRESHOLD_NOT_BUILT = ("mce", "minimum_cross_entropy", "li")
+AUTO_THRESHOLD_MIDDLE = ("foreground", "background")  # ALIBY_THRESHOLD_MIDDLE_* of include/aliby_hip.h, by index
+AUTO_THRESHOLD_MAX_CORRECTION = 16.0
+
+
+class AutoThresholdArgs(NamedTuple):
+    method: str
+    classes: int
+    middle: str | None  # None with two classes, which have no middle class
+    correction: float
+    bounds: tuple
+
+    def options(self, given=AUTO_THRESHOLD_OPTIONS) -> dict:
+        """The checked values of the options named in `given`, by name (bounds as a list: what a saved step holds; no `middle` with
+        two classes).  auto_threshold_options takes the dict back."""
+        values = {**self._asdict(), "bounds": list(self.bounds)}
+        return {key: values[key] for key in AUTO_THRESHOLD_OPTIONS if key in given and values[key] is not None}
+
+    @property
+    def middle_code(self) -> int:
+        """ALIBY_THRESHOLD_MIDDLE_* of include/aliby_hip.h (not used with two classes: foreground)."""
+        return AUTO_THRESHOLD_MIDDLE.index(self.middle or "foreground")
+
+
+def auto_threshold_args(method="otsu", classes=2, middle=None, correction=1.0, bounds=(0, 65535)) -> AutoThresholdArgs:
+    """(method, classes, middle, correction, bounds) of FeatureEngine.auto_threshold and the `auto_threshold` option of a
+    `propagate_<name>` step, checked, as a named tuple.  method: "otsu" (minimum cross-entropy — "mce", "minimum_cross_entropy", "li" —
+    is not built).  classes: 2 or 3.  middle: with three classes, "foreground" (the default: the middle class counts as foreground,
+    the lower threshold) or "background" (the upper one); with two classes it must not be given and stays None in the tuple, so
+    that a checked tuple, and its options(), pass these checks again.  correction: a finite float in
+    (0, 16], CellProfiler's threshold correction factor.  bounds: two whole numbers 0 <= lo <= hi <= 65535 that the corrected
+    threshold is clamped to.  A bool, a str in a number's place and anything out of range are ValueErrors that say what is allowed.
+    Needs no device."""
+    if not isinstance(method, str) or method != "otsu":
+        if isinstance(method, str) and method in AUTO_THRESHOLD_NOT_BUILT:
+            raise ValueError(f"auto_threshold: method {method!r} (minimum cross-entropy) is not built: only 'otsu' is")
+        raise ValueError(f"auto_threshold: method must be 'otsu', got {method!r}")
+    if isinstance(classes, bool) or not isinstance(classes, numbers.Integral) or int(classes) not in (2, 3):
+        raise ValueError(f"auto_threshold: classes must be 2 or 3, got {classes!r}")
+    if int(classes) == 2 and middle is not None:
+        raise ValueError(f"auto_threshold: middle is an option of three classes only (classes=3), got {middle!r} with classes=2")
+    if middle is None and int(classes) == 3:
+        middle = "foreground"
+    if middle is not None and (not isinstance(middle, str) or middle not in AUTO_THRESHOLD_MIDDLE):
+        raise ValueError(f"auto_threshold: middle must be 'foreground' or 'background', got {middle!r}")
+    if isinstance(correction, bool) or not isinstance(correction, numbers.Real) or not math.isfinite(float(correction)) \
+            or not 0.0 < float(correction) <= AUTO_THRESHOLD_MAX_CORRECTION:
+        raise ValueError(f"auto_threshold: correction must be a finite number in (0, 16], got {correction!r}")
+    if not isinstance(bounds, (tuple, list)) or len(bounds) != 2 or not all(_whole_number(b) for b in bounds) \
+            or not 0 <= int(bounds[0]) <= int(bounds[1]) <= 65535:
+        raise ValueError(f"auto_threshold: bounds must be two whole numbers (lo, hi) with 0 <= lo <= hi <= 65535, got {bounds!r}")
+    return AutoThresholdArgs("otsu", int(classes), middle, float(correction), (int(bounds[0]), int(bounds[1])))
+
+
+def auto_threshold_options(options) -> AutoThresholdArgs:
+    """auto_threshold_args of an option dict {"method", "classes", "middle", "correction", "bounds"}; anything but a dict, and an
+    unknown key, are ValueErrors that name the keys allowed."""
+    if not isinstance(options, dict) or set(options) - set(AUTO_THRESHOLD_OPTIONS):
+        raise ValueError(f"auto_threshold: the options must be a dict with keys of {list(AUTO_THRESHOLD_OPTIONS)}, got {options!r}")
+    return auto_threshold_args(**options)
+
+
 def relate_names(other: str) -> list[str]:
     """Columns of `FeatureEngine.relate` for rows related to the object set `other` (csrc/feat_relate.hip): CellProfiler's
     RelateObjects — the parent in `other`, the overlap that chose it, the number of children in `other`, the distance between the

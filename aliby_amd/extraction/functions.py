@@ -125,18 +125,42 @@ def secondary_objects(primary_labels, distance) -> np.ndarray:
     return FeatureEngine().secondary_labels(_label_tile("primary_labels", primary_labels), distance)[0].cpu().numpy()
 
 
-def propagate_objects(primary_labels, image, threshold=0, regularization=0.05, distance=None, image_max=65535) -> np.ndarray:
+def auto_threshold(image, method="otsu", classes=2, middle=None, correction=1.0, bounds=(0, 65535)) -> int:
+    """One uint16 image [Y, X] -> its automatic threshold, a Python int: Otsu's threshold with two or three classes over all the
+    image's pixels, times `correction`, clamped to `bounds` (FeatureEngine.auto_threshold, csrc/feat_threshold.hip; the arguments are
+    those of features.auto_threshold_args).  Not in the reference: CellProfiler's automatic threshold of IdentifySecondaryObjects,
+    PARITY UNPINNED (the definition is in include/aliby_hip.h)."""
+    image = np.asarray(image)
+    if image.dtype != np.uint16 or image.ndim != 2:
+        raise ValueError(f"image must be one uint16 [Y, X] image (float32 images are not built), got {image.dtype} {image.shape}")
+    if image.size == 0:
+        raise ValueError("image holds no pixel: it has no threshold")
+    return int(FeatureEngine().auto_threshold(to_device_u16(image[None]), method, classes, middle, correction, bounds).cpu()[0])
+
+
+def propagate_objects(primary_labels, image, threshold=0, regularization=0.05, distance=None, image_max=65535,
+                      auto_threshold=None) -> np.ndarray:
     """One label image [Y, X] and one uint16 stain image [Y, X] -> uint16 [Y, X]: the labels grown along the stain, every passable
     pixel (labelled, or image >= threshold and, with `distance`, within that many pixels of a labelled one) taking the label of the
     cheapest path over the integer metric of include/aliby_hip.h, ties to the smaller label (FeatureEngine.propagate_labels,
     csrc/feat_propagate.hip).  The cell around a nucleus is propagate_objects(nuclei, cell_stain, threshold=t), and the cytoplasm
     tertiary_objects(that, nuclei).  Not in the reference: CellProfiler's IdentifySecondaryObjects, method "Propagation" (with a
-    distance and threshold 0: "Distance - B"), PARITY UNPINNED."""
+    distance and threshold 0: "Distance - B"), PARITY UNPINNED.  `auto_threshold`: an option dict of features.auto_threshold_args
+    ({} for two-class Otsu) — the threshold is then the image's own, computed and used on the device; together with a non-zero
+    `threshold` it is a ValueError."""
+    from aliby_amd.extraction.features import auto_threshold_options, propagate_args
+
     image = np.asarray(image)
     if image.dtype != np.uint16 or image.ndim != 2:
         raise ValueError(f"image must be one uint16 [Y, X] image (float32 images are not built), got {image.dtype} {image.shape}")
-    return FeatureEngine().propagate_labels(_label_tile("primary_labels", primary_labels), to_device_u16(image[None]), threshold, regularization,
-                                            distance, image_max)[0].cpu().numpy()
+    checked = propagate_args(threshold, regularization, distance, image_max)
+    auto = None if auto_threshold is None else auto_threshold_options(auto_threshold)
+    if auto is not None and checked.threshold != 0:
+        raise ValueError(f"give threshold or auto_threshold, not both (threshold={threshold!r})")
+    engine, stain = FeatureEngine(), to_device_u16(image[None])
+    thresholds = None if auto is None else engine.auto_threshold(stain, **auto._asdict())
+    return engine.propagate_labels(_label_tile("primary_labels", primary_labels), stain, threshold, regularization, distance, image_max,
+                                   thresholds=thresholds)[0].cpu().numpy()
 
 
 def _label_stack(name: str, labels):

@@ -84,7 +84,7 @@ def _volume_secondary_sets(secondary, volume_secondary, volume_features):
 def _propagate_sets(objects, secondary, propagate):
     """The `propagate` keyword of build_pipeline_steps, checked against the segmented and the secondary object sets:
     {name: (primary, channel, {option: checked value})}."""
-    from aliby_amd.extraction.features import PROPAGATE_OPTIONS, propagate_args, propagate_channel, relate_names
+    from aliby_amd.extraction.features import PROPAGATE_OPTIONS, auto_threshold_options, propagate_args, propagate_channel, relate_names
 
     if propagate is None:
         return {}
@@ -102,10 +102,16 @@ def _propagate_sets(objects, secondary, propagate):
         primary, channel, options = (*entry, {})[:3]
         if primary not in objects:
             raise ValueError(f"propagate['{name}']: the primary {primary!r} is not a segmented object set of {objects}")
-        if not isinstance(options, dict) or set(options) - set(PROPAGATE_OPTIONS):
-            raise ValueError(f"propagate['{name}']: the options must be a dict with keys of {list(PROPAGATE_OPTIONS)}, got {options!r}")
+        allowed = (*PROPAGATE_OPTIONS, "auto_threshold")
+        if not isinstance(options, dict) or set(options) - set(allowed):
+            raise ValueError(f"propagate['{name}']: the options must be a dict with keys of {list(allowed)}, got {options!r}")
         try:
-            values = propagate_args(**options).options()
+            values = propagate_args(**{key: value for key, value in options.items() if key != "auto_threshold"}).options()
+            if "auto_threshold" in options:
+                auto = options["auto_threshold"]
+                values["auto_threshold"] = auto_threshold_options(auto).options(auto)  # (the keys given, checked)
+                if values["threshold"] != 0:
+                    raise ValueError(f"give threshold or auto_threshold, not both (threshold={options['threshold']!r})")
             checked[name] = (primary, propagate_channel(channel), {key: values[key] for key in options})  # (in the entry's order)
         except ValueError as e:
             raise ValueError(f"propagate['{name}']: {e}") from None
@@ -212,7 +218,9 @@ def build_pipeline_steps(
     `propagate`, {name: (primary, channel)} or {name: (primary, channel, options)}, adds a `propagate_<name>` step
     {"channel": c, **options} right after the secondary steps and before any tertiary step: the primary's labels grown along the stain
     in channel c of the tile's pixels, max-projected over Z.  options: "threshold", "regularization", "distance", "image_max"
-    (features.propagate_args; {"distance": N} alone is "Distance - B").  The step is saved like a segment step, its passed_data are
+    (features.propagate_args; {"distance": N} alone is "Distance - B"), and "auto_threshold", an option dict of
+    features.auto_threshold_args in place of "threshold" ({"classes": 3, "middle": "foreground", "correction": 0.7}: every tile at its
+    own three-class Otsu level, computed on the device), written into the step checked.  The step is saved like a segment step, its passed_data are
     [("masks", "segment_<primary>", "primary"), ("pixels", "tile")], and `extract_<name>` / `extractmulti_<name>` steps with the
     shared specs measure it: rows with metadata_object = <name> whose metadata_label is the primary object's.  A propagated name may
     be the outer or inner set of a `tertiary` entry and a member of a `relate` pair: propagate={"cell": ("nuclei", 0, {"threshold":

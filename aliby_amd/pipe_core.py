@@ -331,11 +331,14 @@ def _init_propagate(step_name: str, parameters: dict) -> Callable:
     cell stain says it ends; extraction.extract.propagate_masks), in the container the primary segment step returned, so that
     `extract_<name>` / `extractmulti_<name>` steps measure it like a segment step's labels and a `tertiary_` step may take it as its
     outer set.  `channel` is required: a non-negative integer.  Optional: `threshold`, `regularization`, `distance`, `image_max`
-    (features.propagate_args; a `distance` alone is "Distance - B")."""
+    (features.propagate_args; a `distance` alone is "Distance - B"), and `auto_threshold`, an option dict of
+    features.auto_threshold_args ("method", "classes", "middle", "correction", "bounds"; {} is two-class Otsu) in place of
+    `threshold`: every tile is thresholded at its own Otsu level, computed on the device.  The callable keeps the last call's
+    thresholds, one Python int per tile, in its attribute `thresholds`."""
     from aliby_amd.extraction.extract import propagate_masks
-    from aliby_amd.extraction.features import PROPAGATE_OPTIONS, propagate_args, propagate_channel
+    from aliby_amd.extraction.features import PROPAGATE_OPTIONS, auto_threshold_options, propagate_args, propagate_channel
 
-    unknown = set(parameters) - {"channel", *PROPAGATE_OPTIONS}
+    unknown = set(parameters) - {"channel", "auto_threshold", *PROPAGATE_OPTIONS}
     if unknown:
         raise ValueError(f"Step '{step_name}': unknown parameters {sorted(unknown)}.")
     if "channel" not in parameters:
@@ -343,6 +346,10 @@ def _init_propagate(step_name: str, parameters: dict) -> Callable:
     try:
         channel = propagate_channel(parameters["channel"])
         checked = propagate_args(**{key: parameters[key] for key in PROPAGATE_OPTIONS if key in parameters}).options()
+        if "auto_threshold" in parameters:
+            checked["auto_threshold"] = auto_threshold_options(parameters["auto_threshold"]).options()
+            if checked["threshold"] != 0:
+                raise ValueError(f"propagate: give threshold or auto_threshold, not both (threshold={parameters['threshold']!r})")
     except ValueError as e:
         raise ValueError(f"Step '{step_name}': {e}") from None
 
@@ -351,8 +358,9 @@ def _init_propagate(step_name: str, parameters: dict) -> Callable:
         if missing:
             raise ValueError(f"Step '{step_name}': no input for {missing}: 'passed_data' must hand it the masks of a segment step under "
                              "the alias 'primary' and the pixels of the tile step.")
-        return propagate_masks(primary, pixels, channel, **checked, who=f"Step '{step_name}'")
+        return propagate_masks(primary, pixels, channel, **checked, who=f"Step '{step_name}'", chosen=propagate_step.thresholds)
 
+    propagate_step.thresholds = []  # the last call's threshold of every tile
     return propagate_step
 
 

@@ -15,10 +15,14 @@ priority queue the parity is unpinned.  Grown pixels carry the nucleus's label, 
 `profiles/<name>.parquet` join on `metadata_label` by construction.  Such a pipeline runs position by position through
 `run_pipeline_and_post` (the batched `run_positions` refuses it).
 
+With --auto nothing is hand-picked: the options become {"auto_threshold": {"classes": 3, "middle": "foreground"}} and every tile is
+thresholded at its own three-class Otsu level (times --correction), computed on the device and read there by the propagation; the
+step keeps the thresholds it chose, which the script prints.
+
 Segmentation needs Cellpose weights; none are obtainable offline.  The script draws a synthetic field of view (nuclei, and a cell
 stain in channel 1) and feeds the dynamics the analytic flow fields of its ground truth through `flows_override`.
 
-    python examples/propagated_objects.py [--size 256] [--cells 12] [--percentile 60] [--distance 0] [--out DIR]
+    python examples/propagated_objects.py [--size 256] [--cells 12] [--percentile 60 | --auto [--correction 1.0]] [--distance 0] [--out DIR]
 """
 
 from __future__ import annotations
@@ -38,6 +42,8 @@ def main():
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--cells", type=int, default=12)
     ap.add_argument("--percentile", type=float, default=60.0, help="the threshold, as a percentile of the stain")
+    ap.add_argument("--auto", action="store_true", help="an automatic threshold per tile (three-class Otsu) in place of the percentile")
+    ap.add_argument("--correction", type=float, default=1.0, help="with --auto: the threshold correction factor")
     ap.add_argument("--distance", type=int, default=0, help="keep the cells within this many pixels of their nuclei (0: no bound)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
@@ -46,12 +52,15 @@ def main():
     import torch
 
     from aliby_amd import synth
-    from aliby_amd.pipe import run_pipeline_and_post
+    from aliby_amd.pipe import init_step, run_pipeline_and_post
     from aliby_amd.pipe_builder import build_pipeline_steps
 
     fov = synth.make_fov(2, 3, shape=(args.size, args.size), n_channels=2, n_target=args.cells)
     dP, prob = synth.analytic_flows(fov["nuclei"])
-    options = {"threshold": int(np.percentile(fov["pixels"][1].max(axis=0), args.percentile))}
+    if args.auto:
+        options = {"auto_threshold": {"classes": 3, "middle": "foreground", "correction": args.correction}}
+    else:
+        options = {"threshold": int(np.percentile(fov["pixels"][1].max(axis=0), args.percentile))}
     if args.distance:
         options["distance"] = args.distance
 
@@ -68,7 +77,14 @@ def main():
         flows_override=lambda x: (torch.from_numpy(dP[None]).cuda(), torch.from_numpy(prob[None]).cuda()))
 
     out = Path(args.out) if args.out else Path(mkdtemp(prefix="aliby_propagate_out_"))
-    profiles, _ = run_pipeline_and_post(pipeline=pipeline, pipeline_name="position", output_path=out)
+    made = {}  # the step callables, by name: the propagate step keeps the thresholds of its last call
+
+    def keep(name, parameters, other_steps=None):
+        made[name] = init_step(name, parameters, other_steps)
+        return made[name]
+
+    profiles, _ = run_pipeline_and_post(pipeline=pipeline, pipeline_name="position", output_path=out, init_step_fn=keep)
+    print("propagate_cell options:", pipeline["steps"]["propagate_cell"], "-> thresholds per tile:", made["propagate_cell"].thresholds)
     print(f"profiles/position.parquet: {profiles.num_rows} rows x {len(profiles.column_names)} columns -> {out}")
     print("saved masks:", sorted(p.name for p in (out / "steps" / "position").iterdir()))
 

@@ -675,12 +675,62 @@ int aliby_secondary_volume(aliby_ctx* ctx, const uint16_t* primary, int F, int Z
  * every 32 x 32 region of every tile to its fixed point inside LDS against a halo from the buffer no region writes; the call reads the
  * flags of eight rounds at a time and so waits on `stream`.  More than Y * X + 1 changing rounds is ALIBY_ERR_TOO_LARGE, never a
  * result (found at the read of the flags that passes the bound, up to seven rounds later; stats_host then holds the counts so far;
- * every other refusal leaves it zero).  Uses no context scratch.  Not built: automatic thresholds, filling holes, discarding border objects, float32 images, a
+ * every other refusal leaves it zero).  Uses no context scratch.  (A threshold per tile: aliby_propagate_labels_per_tile, below.)  Not built: filling holes, discarding border objects, float32 images, a
  * volume form.  Kernels: csrc/feat_propagate.hip. */
 size_t aliby_propagate_workspace_bytes(int F, int Y, int X);
 int aliby_propagate_labels(aliby_ctx* ctx, const uint16_t* primary, const uint16_t* image, int F, int Y, int X, int threshold,
                            uint64_t lambda2, int distance, void* workspace, size_t workspace_bytes, uint16_t* out_labels,
                            uint64_t* out_dist, int32_t* stats_host, void* stream);
+/* aliby_propagate_labels with one threshold per tile: thresholds [dev, F int32] stands where `threshold` stood, and k_propagate_weights
+ * reads thresholds[f] for tile f on the device — the output of aliby_auto_threshold on the same stream, never read back.  The values
+ * are not range-checked: one above 65535 means that no unlabelled pixel of that tile is passable, a negative one that all are.
+ * thresholds == NULL is ALIBY_ERR_INVALID (unless F * Y * X == 0); everything else is aliby_propagate_labels', the workspace included. */
+int aliby_propagate_labels_per_tile(aliby_ctx* ctx, const uint16_t* primary, const uint16_t* image, int F, int Y, int X,
+                                    const int32_t* thresholds, uint64_t lambda2, int distance, void* workspace, size_t workspace_bytes,
+                                    uint16_t* out_labels, uint64_t* out_dist, int32_t* stats_host, void* stream);
+/* "auto threshold": the threshold a `propagate` call takes, computed per tile on the device — CellProfiler's automatic threshold,
+ * method Otsu with two or three classes, its correction factor and its bounds.  PARITY UNPINNED: CellProfiler, scikit-image and
+ * centrosome bin 0..1 floats into 256 classes after a log transform; here the two-class search is over all 65 536 grey levels, the
+ * three-class search over 256 bins of the occupied range, and the criterion's order of operations is this library's.
+ * Every tile f of image [dev, F x Y x X uint16] is handled on its own.  h[v] = the number of pixels of grey level v among all Y * X
+ * pixels (labelled ones included); lo, hi = the smallest and largest v with h[v] > 0.  Counts and sums of v h[v] are exact integers
+ * below 2^48 (Y * X < 2^32), so each converts to float64 exactly; every float64 operation below is IEEE round-to-nearest, in the
+ * order written, without contraction.
+ *   Two classes.  For t in lo + 1 .. hi: class 0 = {v < t}, class 1 = {v >= t}, n_i and s_i their counts and sums of v,
+ *     J(t) = (double)s0 * (double)s0 / (double)n0 + (double)s1 * (double)s1 / (double)n1   (maximal where the between-class variance is).
+ *     raw = the SMALLEST t that attains the maximum: where empty levels lie between two occupied ones, the level just above the
+ *     dark class.  lo == hi (a constant tile): raw = lo.
+ *   Three classes.  256 bins over the occupied range: W = hi - lo + 1, bin(v) = ((v - lo) * 256) / W (integer division), per-bin
+ *     counts and sums of v from h.  For 0 <= k1 < k2 <= 254: class 0 = bins <= k1, class 1 = bins in (k1, k2], class 2 = bins > k2,
+ *     all three non-empty; J = s0^2 / n0 + s1^2 / n1 + s2^2 / n2, each term as above, summed from the left.  The maximum, ties to the
+ *     smallest k1, then the smallest k2.  t_i = lo + ceil((k_i + 1) * W / 256), the first grey level of the next bin.  No valid pair
+ *     (fewer than three occupied bins): t1 = t2 = the two-class raw threshold.  middle = ALIBY_THRESHOLD_MIDDLE_FOREGROUND takes
+ *     raw = t1 (the middle class counts as foreground), ALIBY_THRESHOLD_MIDDLE_BACKGROUND raw = t2.  With two classes t1 = t2 = raw
+ *     and `middle` is not used.
+ *   thresholds[f] = min(max(llrint(min(raw * correction, 65535.0)), bound_lo), bound_hi): the product in float64, the rounding half
+ *     to even.  details [dev, F x 4 int32], may be NULL: (lo, hi, t1, t2), raw.
+ * Worked examples (pixels -> raw):
+ *   10 x 100 and 10 x 200: every t in 101..200 has the same J; raw = 101.
+ *   10 each of 100, 200, 300: the splits after 100 and after 200 tie at J = 1 350 000; raw = 101.  Three classes: W = 201, the bins
+ *     of 100, 200, 300 are 0, 127, 254; (k1, k2) = (0, 127): (t1, t2) = (101, 201).
+ *   [10, 20, 30]: raw = 11; three classes: W = 21, bins 0, 121, 243: (11, 21).
+ *   [0, 65535]: raw = 1; three classes fall back: (1, 1).
+ *   [32767, 32768, 32768]: raw = 32768.
+ *   raw 101 with correction 0.5: 50.5 rounds to even, 50.
+ * classes 2 or 3, middle one of the two constants, correction in (0, 16], 0 <= bound_lo <= bound_hi <= 65535, F <= 65535 and
+ * Y * X < 2^32 (the limits of aliby_crop_hist_u16, whose histogram this is), else ALIBY_ERR_INVALID.  workspace [dev, 16-byte
+ * aligned]: the caller's, at least aliby_auto_threshold_workspace_bytes(F) = 262144 F bytes (the [F, 65536] uint32 histogram); a
+ * smaller one is ALIBY_ERR_INVALID, and no refused call writes anything.  F * Y * X == 0 is a successful no-op that needs no buffers.
+ * Stream-ordered: no context scratch, no wait on `stream`.  Not built: minimum cross-entropy (its criterion needs log, which is
+ * not bit-reproducible between the device and NumPy: it needs a tolerance of its own), the log transform and smoothing before
+ * thresholding, adaptive (windowed) thresholds, one threshold over the whole batch, masks, float32 images.
+ * Kernels: csrc/feat_threshold.hip (the search), csrc/tile_crop.hip (the histogram). */
+#define ALIBY_THRESHOLD_MIDDLE_FOREGROUND 0
+#define ALIBY_THRESHOLD_MIDDLE_BACKGROUND 1
+size_t aliby_auto_threshold_workspace_bytes(int F);
+int aliby_auto_threshold(aliby_ctx* ctx, const uint16_t* image, int F, int Y, int X, int classes, int middle, double correction,
+                         int bound_lo, int bound_hi, void* workspace, size_t workspace_bytes, int32_t* thresholds, int32_t* details,
+                         void* stream);
 /* trap.imBackground / trap.background_max5 (src/extraction/core/functions/trap.py:6-43): per tile, over the pixels of
  * `channel` under NO mask (labels == 0): out[f*2] = their median (numpy.median), out[f*2+1] = the mean of the five largest
  * (of all of them when fewer); NaN for a tile without background. */
